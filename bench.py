@@ -22,10 +22,16 @@ the timed region (--root-slots auto: candidate weighted patterns timed, the
 fastest kept and reported).  At N=1 the same step runs with a local conversion.
 value = frame fragments (summed over ranks) x steps / max-over-ranks time.
 
-At N=1 the line also carries `extra`: the metric's literal configuration
-(1M triangles at 1920x1080), C2, C5 (with a VALU roofline beside the HBM one)
-and host-delivered frame rates (--deliver host: every step ends with the
-frame on the host, as the video caller needs it), each measured the same way.
+A plain run does what the headline needs: set-up, one counted frame, clock
+settle and warmup, the timed steps, --dump-outputs DIR (the last timed step's
+frame output and samples of its framebuffer and depth as DIR/<name>.npy; the
+inputs are the same from run to run) and the line.  --full adds the rest, as
+every run did before: per-kernel and roofline passes, the last timed frame
+verified against the oracle's digests, the CPU baseline, and at N=1 `extra`:
+the metric's literal configuration (1M triangles at 1920x1080), C2, C5 (with a
+VALU roofline beside the HBM one) and host-delivered frame rates (--deliver
+host: every step ends with the frame on the host, as the video caller needs
+it), each measured the same way.
 
 Prints ONE JSON line on rank 0.
 """
@@ -393,6 +399,50 @@ class Runner:
             out["fragments_match_oracle"] = int(round(self.frags)) == ref["fragments"]
         return out
 
+    def kernel_passes(self, steps, share):
+        """--full: the per-kernel figures, from two passes of K frames each
+        before the timed region."""
+        ctx = self.ctx
+        names = ("tri_count", "tri_scan", "tri_emit", "tri_sort", "tile_ranges", "vis_init", "tile_raster",
+                 "resolve", "fill", "output", "gather")
+        # (1) breakdown pass: HIP events around every kernel (they add launch
+        #     gaps, so this pass is not the headline)
+        ctx.reset_kernel_timing()
+        ctx.set_kernel_timing_filter("")
+        ctx.enable_kernel_timing(True)
+        for i in range(steps):
+            self.frame(i)
+        self.drain()
+        ctx.enable_kernel_timing(False)
+        kernels = {}
+        for name in names:
+            tot, cnt = ctx.get_kernel_timing(name)
+            if cnt:
+                kernels[name] = round(tot / cnt * 1e3, 2)   # us per launch
+        kb = kernel_bytes(self.cfg, self.n_tri, ctx.last_raster_path(), share, self.frame_output)
+        dom = max((k for k in kb if k in kernels), key=lambda k: kernels[k])
+
+        # (2) kernel pass: K frames with only the dominant kernel timed: the
+        #     raster stamps its own execution span on the device's 100 MHz
+        #     clock (first workgroups' start, last workgroup's end; no packet
+        #     on the stream -- events around or bound to the launch also
+        #     counted the launch gap, profiles/r06/ab_event_every.txt).  The
+        #     timed region below carries no timing at all.
+        dom_us, cnt = kernels[dom], 0
+        if not self.args.no_kernel_timing:
+            ctx.reset_kernel_timing()
+            ctx.set_kernel_timing_filter(dom)
+            ctx.enable_kernel_timing(True)
+            for i in range(steps):
+                self.frame(i)
+            self.drain()
+            ctx.enable_kernel_timing(False)
+            tot, cnt = ctx.get_kernel_timing(dom)
+            if cnt:
+                dom_us = round(tot / cnt * 1e3, 2)
+            ctx.reset_kernel_timing()
+        return kernels, dom, dom_us, cnt, kb
+
     def run(self, steps, warmup, calibrate=False):
         import torch
         ctx, dist = self.ctx, self.dist
@@ -444,48 +494,12 @@ class Runner:
             self.frame(i)
         self.drain()
 
-        names = ("tri_count", "tri_scan", "tri_emit", "tri_sort", "tile_ranges", "vis_init", "tile_raster",
-                 "resolve", "fill", "output", "gather")
-        # (1) breakdown pass: HIP events around every kernel (they add launch
-        #     gaps, so this pass is not the headline)
-        ctx.reset_kernel_timing()
-        ctx.set_kernel_timing_filter("")
-        ctx.enable_kernel_timing(True)
-        for i in range(steps):
-            self.frame(i)
-        self.drain()
-        ctx.enable_kernel_timing(False)
-        kernels = {}
-        for name in names:
-            tot, cnt = ctx.get_kernel_timing(name)
-            if cnt:
-                kernels[name] = round(tot / cnt * 1e3, 2)   # us per launch
-        path = ctx.last_raster_path()
         from libnativecpurenderer_amd import sharding
         slots = self.slots_for(self.root_k) if self.nsh > 1 else None
         share = len(sharding.owned_rows(self.H, self.nsh, self.me, slots=slots)) / self.H
-        kb = kernel_bytes(self.cfg, self.n_tri, path, share, self.frame_output)
-        dom = max((k for k in kb if k in kernels), key=lambda k: kernels[k])
-
-        # (2) kernel pass: K frames with only the dominant kernel timed: the
-        #     raster stamps its own execution span on the device's 100 MHz
-        #     clock (first workgroups' start, last workgroup's end; no packet
-        #     on the stream -- events around or bound to the launch also
-        #     counted the launch gap, profiles/r06/ab_event_every.txt).  The
-        #     timed region below carries no timing at all.
-        dom_us, cnt = kernels[dom], 0
-        if not self.args.no_kernel_timing:
-            ctx.reset_kernel_timing()
-            ctx.set_kernel_timing_filter(dom)
-            ctx.enable_kernel_timing(True)
-            for i in range(steps):
-                self.frame(i)
-            self.drain()
-            ctx.enable_kernel_timing(False)
-            tot, cnt = ctx.get_kernel_timing(dom)
-            if cnt:
-                dom_us = round(tot / cnt * 1e3, 2)
-            ctx.reset_kernel_timing()
+        full = self.args.full
+        if full:
+            kernels, dom, dom_us, cnt, kb = self.kernel_passes(steps, share)
 
         # (3) timed region: K frames, nothing but the frames
         self.sync()
@@ -501,6 +515,25 @@ class Runner:
         warm_frames = ctx.warm_batch_count() - warm0
         loose_frames = ctx.loose_batch_count() - loose0
         ms = dt / steps * 1e3
+        path = ctx.last_raster_path()
+        B = algorithmic_bytes(self.cfg, self.n_tri, frame_out=self.frame_output)   # whole frame
+        out = {
+            "value": round(frags * steps / dt / 1e6, 1),
+            "ms_per_step": round(ms, 4),
+            "fps": round(1e3 / ms, 1),
+            "fragments_per_frame": int(round(frags)),
+            # (a plain run: the frame-level figures, which need no pass of their own)
+            "roofline": {"bound": "hbm", "unit": "GB/s", "rank_share_of_frame": round(share, 6),
+                         **frame_roofline(B, share, ms, self.world)},
+            "raster_path": path,
+            "slots": slots,
+            "calib": calib,
+            "warm_binned_frames": warm_frames,
+            "loose_binned_frames": loose_frames,
+            "clock_settle": {"ms": self.args.clock_settle_ms, "frames": self.settle_frames},
+        }
+        if not full:
+            return out
         # the last timed frame against the oracle's digests (outside the timed region)
         ver = self.verify(steps - 1)
         if dist is not None:   # every rank's verdict: false if any rank mismatched
@@ -508,7 +541,6 @@ class Runner:
                 ver["verified"] = False
             ver["warm_failures"] = int(self.max_over_ranks(float(ver["warm_failures"])))
         achieved = kb[dom] / (dom_us * 1e-6) / 1e9
-        B = algorithmic_bytes(self.cfg, self.n_tri, frame_out=self.frame_output)   # whole frame
         ksym = "k_tile_raster" if path == "ordered" else "k_vis"
         # (at N>1 the PMC summary of rank 0's share, taken as an emulated share on one GPU)
         traffic, traffic_src = load_pmc_traffic(self.cfg_name, self.nsh, slots, self.frame_output, ksym)
@@ -522,21 +554,7 @@ class Runner:
                                      f"the timed region" if cnt else "breakdown pass"),
                 "algorithmic_bytes_per_launch": kb[dom], "rank_share_of_frame": round(share, 6),
                 **frame_roofline(B, share, ms, self.world)}
-        out = {
-            "value": round(frags * steps / dt / 1e6, 1),
-            "ms_per_step": round(ms, 4),
-            "fps": round(1e3 / ms, 1),
-            "fragments_per_frame": int(round(frags)),
-            "roofline": roof,
-            "raster_path": path,
-            "kernel_us": kernels,
-            "slots": slots,
-            "calib": calib,
-            "warm_binned_frames": warm_frames,
-            "loose_binned_frames": loose_frames,
-            "clock_settle": {"ms": self.args.clock_settle_ms, "frames": self.settle_frames},
-            **ver,
-        }
+        out.update({"roofline": roof, "kernel_us": kernels, **ver})
         if path == "ordered" and self.cfg.get("soup", (0, 0, None))[2] is not None:
             # C5: the blend loop is bound by f64 VALU issue, not by HBM (per
             # rank: frags is this context's count at N=1, the ranks' sum at N>1)
@@ -550,6 +568,39 @@ class Runner:
         return out
 
 
+DUMP_FRAME_ELEMS = 12_500_000   # f32 frame output: 50 MB of the 64 MB all dumped files may take
+DUMP_PIXELS = 200_000           # framebuffer (f64 x ipp) and depth samples: 6.4 MB at ipp = 3
+
+
+def dump_sample(n, k, seed):
+    """Sorted indices of a fixed, seeded sample of k of n elements (all when n <= k)."""
+    if n <= k:
+        return slice(None)
+    return np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, size=k, replace=False))
+
+
+def dump_outputs(run, last_i, out_dir):
+    """--dump-outputs: what the timed path computed in its last step, as
+    <name>.npy.  frame_output (f32, exact for u8): the frame output the step
+    hands its caller -- the host frame when it is delivered there, else the
+    one in HBM -- whole up to DUMP_FRAME_ELEMS elements, else a seeded sample
+    of that many.  At N=1, unsharded: framebuffer (f64, DUMP_PIXELS x ipp) and
+    depth (f64, exact for u32), the same seeded sample of pixels of both."""
+    os.makedirs(out_dir, exist_ok=True)
+    ctx = run.ctx
+    n_out = int(np.prod(ctx.frame_output_shape()))
+    if run.host is not None:
+        frame = np.asarray(run.host[last_i % 2].array()).reshape(-1)[:n_out]
+    else:
+        frame = ctx.get_frame_u8().reshape(-1)
+    np.save(os.path.join(out_dir, "frame_output.npy"), frame[dump_sample(n_out, DUMP_FRAME_ELEMS, 1)].astype(np.float32))
+    if run.world == 1 and run.nsh == 1:
+        px = dump_sample(run.W * run.H, DUMP_PIXELS, 2)
+        fb = ctx.get_buffer_numpy()
+        np.save(os.path.join(out_dir, "framebuffer.npy"), fb.reshape(run.W * run.H, -1)[px])
+        np.save(os.path.join(out_dir, "depth.npy"), ctx.get_depth_buffer().reshape(-1)[px].astype(np.float64))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -560,10 +611,19 @@ def parse_args(argv=None):
                     help="untimed frames first, until the GPU has rendered this long (its clocks ramp after idle), "
                          "then the --warmup steps")
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-kernel and roofline passes before the timed region, the last "
+                         "timed frame verified against the oracle's digests, the CPU baseline and (N=1) the "
+                         "'extra' configurations.  A plain run sets up, warms up, times the steps and prints "
+                         "the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(rank 0): frame_output, the frame as the step hands it over, and at N=1 seeded "
+                         "samples of the f64 framebuffer and the depth buffer")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--extra", dest="extra", action="store_true", default=None,
-                    help="also time the metric's literal config (1M tris at 1080p), c2, c5 and host-delivered "
-                         "frames, reported under 'extra' (default at N=1)")
+                    help="--full: also time the metric's literal config (1M tris at 1080p), c2, c5 and "
+                         "host-delivered frames, reported under 'extra' (default at N=1)")
     ap.add_argument("--no-extra", dest="extra", action="store_false")
     ap.add_argument("--deliver", default="none", choices=("none", "host", "bands"),
                     help="host: every step ends with the frame output on the host (pinned buffers, D2H of frame k "
@@ -624,8 +684,11 @@ def main():
         run.comm = sharding.make_comm(dist, world, rank)
     res = run.run(args.steps, args.warmup, calibrate=world > 1 and args.root_slots == "auto")
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(run, args.steps - 1, args.dump_outputs)
+
     extra = {}
-    do_extra = args.extra if args.extra is not None else (world == 1 and nsh == 1)
+    do_extra = args.full and (args.extra if args.extra is not None else (world == 1 and nsh == 1))
     if do_extra and world == 1:
         jobs = [("c3_1080p", "none", None), ("c3_animated", "none", None), ("c2", "none", None), ("c5", "none", None),
                 (args.config, "none", "rgb"), (args.config, "host", None), (args.config, "host", "rgb"),
@@ -692,19 +755,24 @@ def main():
                       if nsh > 1 else {})},
         "roofline": res["roofline"],
         "raster_path": res["raster_path"],
-        "kernel_us": res["kernel_us"],
         "clock_settle": res["clock_settle"],
-        **{k: res[k] for k in VERIFY_KEYS if k in res},
-        "kernel_us_note": "kernel_us: per-launch averages from a breakdown pass with events around every kernel "
-                          "(the rasters by their device-clock span); roofline.kernel_us: the dominant kernel's "
-                          "device-clock span over a K-frame pass of its own (roofline.kernel_us_source); the "
-                          "timed region carries no timing",
+        "full": args.full,
     }
+    if args.full:
+        result.update({
+            "kernel_us": res["kernel_us"],
+            **{k: res[k] for k in VERIFY_KEYS if k in res},
+            "kernel_us_note": "kernel_us: per-launch averages from a breakdown pass with events around every kernel "
+                              "(the rasters by their device-clock span); roofline.kernel_us: the dominant kernel's "
+                              "device-clock span over a K-frame pass of its own (roofline.kernel_us_source); the "
+                              "timed region carries no timing"})
+    if args.dump_outputs:
+        result["dumped_outputs"] = args.dump_outputs
     if "valu_roofline" in res:
         result["valu_roofline"] = res["valu_roofline"]
     if extra:
         result["extra"] = extra
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         result["cpu_baseline"] = cpu_baseline(cfg, run.xy, run.z, run.c)
         result["vs_cpu"] = round(result["value"] / result["cpu_baseline"]["value"], 1)
     print(json.dumps(result))

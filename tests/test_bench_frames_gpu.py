@@ -167,3 +167,33 @@ def test_bench_other_configs_match_oracle(gpu, config):
     run.frags = frags
     ver = run.verify(5)
     assert ver["verified"] is True, ver
+
+
+def test_plain_bench_run_dumps_the_last_timed_frame(gpu, tmp_path):
+    """A plain `bench.py` run (C2, 3 steps) prints the headline line without
+    what --full adds, times --steps steps, and --dump-outputs writes the last
+    timed frame: the YUV420P planes whole, framebuffer and depth at the seeded
+    sample of pixels -- each equal to the oracle's frame."""
+    import json
+    import subprocess
+    import sys
+    b = _bench()
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--config", "c2", "--clock-settle-ms", "0", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+    assert d["unit"] == "Mpixels/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    for k in ("extra", "cpu_baseline", "kernel_us", "verified"):
+        assert k not in d, k
+    f64, depth, u8, frags = _oracle_frame(b, "c2")
+    assert d["config"]["fragments_per_frame"] == frags
+    W, H = b.CONFIGS["c2"]["W"], b.CONFIGS["c2"]["H"]
+    got = {f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir)}
+    assert sorted(got) == ["depth", "frame_output", "framebuffer"]
+    assert got["frame_output"].dtype == np.float32 and np.array_equal(got["frame_output"], scenes.yuv420p(u8))
+    px = b.dump_sample(W * H, b.DUMP_PIXELS, 2)
+    assert scenes.bits_equal(got["framebuffer"], f64.reshape(W * H, -1)[px])
+    assert np.array_equal(got["depth"], depth.reshape(-1)[px].astype(np.float64))

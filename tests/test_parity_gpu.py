@@ -740,7 +740,7 @@ def test_bench_multi_rank_orchestration_on_one_gpu(gpu, tmp_path, deliver):
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(scenes.ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "5", "--warmup", "1", "--gloo-test", "--config", "c2", "--deliver", deliver]
+           "--gpus", "2", "--steps", "5", "--warmup", "1", "--full", "--gloo-test", "--config", "c2", "--deliver", deliver]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

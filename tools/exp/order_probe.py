@@ -15,7 +15,7 @@ def main():
     k = int(sys.argv[1]) if len(sys.argv) > 1 else 4
     keep = len(sys.argv) > 2 and sys.argv[2] == "keep"
     settle = sys.argv[3] if len(sys.argv) > 3 else str(bench.CLOCK_SETTLE_MS)
-    args = bench.parse_args(["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-extra",
+    args = bench.parse_args(["--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extra",
                              "--clock-settle-ms", settle])
     if os.environ.get("PROBE_LIB"):   # a variant build (tools/exp/<name>.so)
         from libnativecpurenderer_amd import _lib

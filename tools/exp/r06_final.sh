@@ -3,7 +3,7 @@
 # (profiles/pmc_<tag>.json).  Usage (gpurun): bash tools/exp/r06_final.sh TAG
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}" || exit 1
 T=${1:-r06fin}
-TAG=$T bash tools/gpu_session.sh test smoke "bench:--steps,20,--warmup,5" "stats:--steps,20,--warmup,5" \
+TAG=$T bash tools/gpu_session.sh test smoke "bench:--steps,20,--warmup,5,--full" "stats:--steps,20,--warmup,5" \
   "stats:--steps,20,--warmup,5,--config,c3_animated" \
   "bench:--steps,20,--warmup,5,--no-extra,--no-cpu-baseline,--emulate-shards,8,--root-slots,equal" \
   "bench:--steps,20,--warmup,5,--no-extra,--no-cpu-baseline,--emulate-shards,4,--root-slots,equal" \

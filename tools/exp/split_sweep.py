@@ -17,7 +17,7 @@ cfg = sys.argv[1]
 pairs = [tuple(int(v) for v in p.split(":")) for p in sys.argv[2].split(",")]
 nsh = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 args = types.SimpleNamespace(no_kernel_timing=False, force_ordered=False, clock_settle_ms=60.0, root_slots="equal", frame_output="yuv420p",
-                             emulate_shards=nsh)
+                             emulate_shards=nsh, full=True)
 R.set_device(0)
 for rep in range(2):
     for sa, ds in pairs:

@@ -4,7 +4,8 @@
 # that crashes, times out or faults -- exit status > 2):
 #   test            pytest -m gpu (whole GPU suite)
 #   smoke           __graft_entry__.smoke()
-#   bench[:ARGS]    python bench.py ARGS  (ARGS: comma-separated, e.g. bench:--config,c2,--steps,20)
+#   bench[:ARGS]    python bench.py ARGS  (ARGS: comma-separated, e.g. bench:--config,c2,--steps,20; add --full for
+#                   the per-kernel, roofline, verification, CPU-baseline and extra figures)
 #   trace[:ARGS]    rocprofv3 --kernel-trace --hip-runtime-trace of bench.py ARGS (+ timeline.py)
 #   ktrace[:ARGS]   rocprofv3 --kernel-trace of bench.py ARGS (+ timeline.py), no runtime trace
 #   ctrace[:ARGS]   rocprofv3 --kernel-trace --memory-copy-trace of bench.py ARGS

@@ -6,8 +6,8 @@ the next frame's binning does not run beside the raster, and the raster is
 ~10 % faster than in the steady state that the kernel pass and the timed region
 measure (binning beside the raster, profiles/r06/README.md).  This prints, per
 kernel, the average over all dispatches and over the last N dispatches (the
-kernel pass + timed region + verification frames of a --steps K run: N = 2K +
-a few).
+timed region of a plain --steps K run: N = K; with --full the kernel pass +
+timed region + verification frames: N = 2K + a few).
 
     python tools/trace_steady.py run_kernel_trace.csv [N] [name-regex]
 """
