@@ -144,6 +144,18 @@ TriangleBuffer* CreateTriangleBuffer(i64 n, const f64* xy, const f64* z, const f
 void DestroyTriangleBuffer(TriangleBuffer* tb);                          /* NEW */
 void DrawTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb);         /* NEW */
 i64 GetTriangleBufferCount(TriangleBuffer* tb);                          /* NEW */
+/* NEW: textured triangles.  uv: n*6 per-vertex texture coordinates in texel units (u0 v0 u1 v1 u2 v2),
+   interpolated like a Gouraud channel (affine) and sampled with DrawTexture's nearest sampler (a NaN
+   coordinate samples texel 0); blended by ApplyPixel.  A NULL texture, one narrower or lower than 2
+   texels, or one on another device latches an error and draws nothing. */
+void DrawTexturedTriangles(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv,
+                           i64 n);                                        /* NEW: host arrays */
+void DrawTexturedTrianglesDevice(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv,
+                                 i64 n);                                  /* NEW: device pointers (as DrawTrianglesDevice) */
+TriangleBuffer* CreateTexturedTriangleBuffer(i64 n, const f64* xy, const f64* z,
+                                             const f64* uv);              /* NEW: one H2D upload; no texture bound */
+void DrawTexturedTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb, Texture* tex);   /* NEW: texture chosen per
+                                 draw; a colour buffer here, or a textured one in DrawTriangleBuffer, latches an error */
 void SetFragmentCounting(RenderContext* ctx, bool on);                   /* NEW: covered-fragment counter */
 i64 GetFragmentCount(RenderContext* ctx);                                /* NEW */
 i64 GetLastRasterPath(RenderContext* ctx);                               /* NEW: 1 order-free tiled, 2 ordered, 3 order-free frame */

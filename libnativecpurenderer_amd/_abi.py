@@ -76,6 +76,10 @@ DEVICE_ABI = {
     "DestroyTriangleBuffer": (None, (P,)),
     "DrawTriangleBuffer": (None, (P, P)),
     "GetTriangleBufferCount": (L, (P,)),
+    "DrawTexturedTriangles": (None, (P, P, P, P, P, L)),
+    "DrawTexturedTrianglesDevice": (None, (P, P, P, P, P, L)),
+    "CreateTexturedTriangleBuffer": (P, (L, P, P, P)),
+    "DrawTexturedTriangleBuffer": (None, (P, P, P)),
     "SetFragmentCounting": (None, (P, B)),
     "GetFragmentCount": (L, (P,)),
     "GetLastRasterPath": (L, (P,)),

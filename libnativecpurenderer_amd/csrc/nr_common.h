@@ -234,8 +234,10 @@ struct TriangleBuffer {
     bool gouraud = false;
     f64* xy = nullptr;    // n*6   (x0,y0,x1,y1,x2,y2)
     f64* z = nullptr;     // n*3 or null
-    f64* rgba = nullptr;  // n*4 (flat) or n*12 (Gouraud)
-    bool opaque = false;  // every vertex alpha == 1 (known at upload)
+    f64* rgba = nullptr;  // n*4 (flat) or n*12 (Gouraud); null for a textured buffer
+    f64* uv = nullptr;    // textured buffer (CreateTexturedTriangleBuffer): n*6 texel coordinates
+    bool textured = false;
+    bool opaque = false;  // every vertex alpha == 1 (known at upload; textured: decided per draw by the texture)
     int device = 0;
     // totals of the last validated binning of this buffer (nr_tri_free.hip):
     // a draw under the same key is sized from them and needs no validation
@@ -259,6 +261,15 @@ constexpr int NR_CLUSTER = 64;
 
 // host helpers shared across translation units
 Texture* nr_new_texture(i64 w, i64 h, bool alpha);   // device texels, current device
+// Texture source for a draw into ctx (nr_prims.hip): the texels, or -- for a
+// texture that aliases ctx's own framebuffer -- a snapshot of them taken on the
+// context's stream (tmp, released by nr_tex_release once the draw is enqueued).
+struct TexSrc {
+    const f64* ptr = nullptr;
+    f64* tmp = nullptr;
+};
+TexSrc nr_tex_source(RenderContext* ctx, Texture* tex);
+void nr_tex_release(RenderContext* ctx, TexSrc& s);
 void nr_dist_sync(RenderContext* ctx);      // wait for the frame-assembly stream
 u64 nr_shard_mask(const RenderContext* ctx, int rank);   // bit k: pattern slot k belongs to rank
 void nr_dist_release(RenderContext* ctx);   // free the frame-output buffers

@@ -335,10 +335,6 @@ struct ImmediateScope {
 // Texture source for a draw.  An alias of the destination framebuffer is read
 // while being written in the reference (order-dependent result); here the
 // draw samples a snapshot taken before it starts.
-struct TexSrc {
-    const f64* ptr = nullptr;
-    f64* tmp = nullptr;
-};
 static TexSrc tex_source(RenderContext* ctx, Texture* tex) {
     TexSrc s;
     if (tex->aliasOf) nr_materialize_color(tex->aliasOf);
@@ -376,6 +372,9 @@ static void fast_range(f64 x, f64 w, i64 limit, i64* lo, i64* hi) {
 }
 
 }  // namespace
+
+TexSrc nr_tex_source(RenderContext* ctx, Texture* tex) { return tex_source(ctx, tex); }
+void nr_tex_release(RenderContext* ctx, TexSrc& s) { tex_release(ctx, s); }
 
 extern "C" {
 

@@ -4,7 +4,8 @@
 // in the reference's idiom, DESIGN.md §3, restated by the CPU oracle):
 //   vertices -> context transform (cpp:446-453) -> screen space;
 //   coverage = even-odd pointInPolygon (cpp:822-845) at integer pixels;
-//   w1,w2 barycentric in f64, attr = a0 + (a1-a0)*w1 + (a2-a0)*w2;
+//   w1,w2 barycentric in f64, attr = a0 + (a1-a0)*w1 + (a2-a0)*w2 (a colour
+//   channel, or a texture coordinate whose texel is then the colour);
 //   depth u32 LESS, written only when test+write are on;
 //   blend = ApplyPixel (cpp:515-549) in submission order.
 //
@@ -22,13 +23,38 @@ namespace nrtri {
 constexpr int TW = 64;   // tile width  (= one wave's lanes)
 constexpr int TH = 32;   // tile height
 
+// Per-triangle attribute of a batch: one colour, a colour per vertex, or a
+// texture coordinate per vertex (texel units) sampled from FrameParams::tex.
+enum AttrMode { ATTR_FLAT = 0, ATTR_GOURAUD = 1, ATTR_TEX = 2 };
+
 struct TriSrc {
     const f64* xy;    // n*6
     const f64* z;     // n*3 or null
-    const f64* rgba;  // n*4 flat / n*12 Gouraud
-    int gouraud;
+    const f64* attr;  // by mode: colours n*4 flat / n*12 Gouraud, or uv n*6 textured (u0 v0 u1 v1 u2 v2)
+    int mode;         // AttrMode
     i64 n;
+    __host__ __device__ const f64* rgba() const { return attr; }   // (flat / Gouraud batches)
+    __host__ __device__ const f64* uv() const { return attr; }     // (textured batches)
 };
+// doubles of the attribute array per triangle
+__host__ __device__ inline int attr_stride(int mode) { return mode == ATTR_GOURAUD ? 12 : (mode == ATTR_TEX ? 6 : 4); }
+
+// The texture a textured batch samples (nearest, tex_index): texels as the
+// framebuffer stores them, ipp doubles each, w >= 2 and h >= 2 (a side below
+// 2^29, so the pitch fits an int: check_texture).  The sampler's clamp bounds (f64)(w-2), (f64)(h-2)
+// are formed on the host -- the same values -- so that they arrive as scalar
+// kernel arguments: converted in the kernel they are loop-invariant vector
+// values, which the compiler hoists and keeps live (or spills) across the
+// whole raster; the view is 8 scalar registers.
+struct TexView {
+    const f64* ptr;
+    f64 xlast, ylast;   // w-2, h-2
+    int pitch, ipp;     // doubles per row / per texel
+};
+inline TexView tex_view(const f64* ptr, i64 w, i64 h, bool alpha) {
+    const int ipp = alpha ? 4 : 3;
+    return TexView{ptr, (f64)(w - 2), (f64)(h - 2), (int)w * ipp, ipp};
+}
 
 struct BinParams {
     TriSrc src;
@@ -355,7 +381,23 @@ struct FrameParams {
     u32 tileEpoch;    // RenderContext::tileStamp) and writes only its frame output
     u64* tstamp;      // non-null (kernel timing): {~first start, last end} of the raster on the device's
                       // 100 MHz clock (raster_stamp_begin / _end, nr_timing_stamp)
+    TexView tex;      // ATTR_TEX batches: the texture (a snapshot when it aliases fb)
 };
+
+// Texel of a fragment's interpolated (u, v), as an offset in doubles: the
+// texel the reference sampler picks (cpp:555-573: x < 0 -> 0, x >= w-1 ->
+// w-2, then y the same way, texel ((i64)y, (i64)x)).  Its two clamps and the
+// truncation are one max and one min here: for x < 0 both give 0; for 0 <= x <
+// w-2 neither changes x; for w-2 <= x < w-1 the reference keeps x, which
+// truncates to w-2 = min(x, w-2); for x >= w-1 both give w-2.  A NaN
+// coordinate is undefined in the reference ((i64)NaN) and defined here as
+// coordinate 0: fmax(NaN, 0) is 0.  With w, h >= 2 the offset
+// is in range for every input: column in [0, w-2], row in [0, h-2].
+__device__ __forceinline__ i64 tex_index(const TexView& tv, f64 x, f64 y) {
+    const int xi = (int)fmin(fmax(x, 0.0), tv.xlast);
+    const int yi = (int)fmin(fmax(y, 0.0), tv.ylast);
+    return (i64)yi * tv.pitch + xi * tv.ipp;
+}
 
 // Kernel timing of the rasters by the device's constant 100 MHz clock
 // (s_memrealtime): the first workgroups dispatched on each XCD (blockIdx < 8)
@@ -475,7 +517,7 @@ bool grow_set(T* (&ptrs)[K], size_t* cap, size_t need) {
 }
 bool grow_temp(TriScratch& sc, size_t need);
 
-FrameParams frame_params(RenderContext* ctx, const TriSrc& src);
+FrameParams frame_params(RenderContext* ctx, const TriSrc& src, const TexView* tex = nullptr);
 void finish_batch(RenderContext* ctx, const FrameParams& fp);
 u32* tile_stamps(RenderContext* ctx, i64 ntiles);   // the context's tile stamps, next epoch (nr_tri.hip)
 
@@ -485,7 +527,8 @@ u32* tile_stamps(RenderContext* ctx, i64 ntiles);   // the context's tile stamps
 // ORD_BIN_TILES tiles, each tile's list sorted in LDS (k_tile_sort); the
 // global-sort path (draw_ordered_sorted) otherwise, and for a batch with a tile
 // of more than ORD_SORT_CAP triangles (detected by the plan, re-run)
-void draw_ordered(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned);
+void draw_ordered(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned,
+                  const TexView* tex = nullptr);
 void draw_ordered_sorted(RenderContext* ctx, const TriSrc& src, const FrameParams& fp, const BinParams& bp);
 // the same kernels for a deferred re-run (nr_settle): the batch's snapshot only, context flags untouched
 void rerun_ordered_sorted(RenderContext* ctx, const TriSrc& src, const FrameParams& fp, const BinParams& bp);
@@ -502,7 +545,8 @@ void launch_ordered_binned(const FrameParams& fp, const u32* list, const u32* of
 // callerOwned: the arrays are the caller's device memory (DrawTrianglesDevice),
 // so the batch is sized exactly in the call -- an overflow re-run never reads
 // them after it returns
-void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, bool ordered = false);
+void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, bool ordered = false,
+               const TexView* tex = nullptr);
 void settle(RenderContext* ctx);
 
 }  // namespace nrtri

@@ -9,6 +9,7 @@
 #include "nr_tri.h"
 
 #include <algorithm>
+#include <string>
 #include <vector>
 #include <atomic>
 #include <cmath>
@@ -28,7 +29,7 @@ bool grow_temp(TriScratch& sc, size_t need) {
     return true;
 }
 
-FrameParams frame_params(RenderContext* ctx, const TriSrc& src) {
+FrameParams frame_params(RenderContext* ctx, const TriSrc& src, const TexView* tex) {
     TriScratch& sc = ctx->tri;
     if (!sc.h_total) NR_CHECK(hipHostMalloc((void**)&sc.h_total, 4 * sizeof(u64)));
     if (ctx->depthTest) nr_ensure_depth(ctx);
@@ -58,6 +59,7 @@ FrameParams frame_params(RenderContext* ctx, const TriSrc& src) {
     fp.tileStamp = nullptr;
     fp.tileEpoch = 0;
     fp.tstamp = nullptr;
+    fp.tex = tex ? *tex : tex_view(nullptr, 2, 2, false);
     if (ctx->countFragments) {
         if (!sc.d_frag) NR_CHECK(hipMalloc(&sc.d_frag, sizeof(u64)));
         NR_CHECK(hipMemsetAsync(sc.d_frag, 0, sizeof(u64), ctx->stream));
@@ -175,8 +177,8 @@ Opacity device_opacity(RenderContext* ctx, const TriSrc& src) {
     if (!sc.d_flag) NR_CHECK(hipMalloc(&sc.d_flag, sizeof(u32)));
     if (!sc.h_total) NR_CHECK(hipHostMalloc((void**)&sc.h_total, 4 * sizeof(u64)));
     NR_CHECK(hipMemsetAsync(sc.d_flag, 0, sizeof(u32), ctx->stream));
-    hipLaunchKernelGGL(k_opacity, dim3((unsigned)((src.n + 255) / 256)), dim3(256), 0, ctx->stream, src.rgba, src.n,
-                       src.gouraud, sc.d_flag);
+    hipLaunchKernelGGL(k_opacity, dim3((unsigned)((src.n + 255) / 256)), dim3(256), 0, ctx->stream, src.rgba(), src.n,
+                       src.mode == ATTR_GOURAUD ? 1 : 0, sc.d_flag);
     NR_CHECK(hipGetLastError());
     u32* h = reinterpret_cast<u32*>(&sc.h_total[3]);
     NR_CHECK(hipMemcpyAsync(h, sc.d_flag, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
@@ -184,17 +186,49 @@ Opacity device_opacity(RenderContext* ctx, const TriSrc& src) {
     return *h ? OPQ_BLENDED : OPQ_OPAQUE;
 }
 
-void draw(RenderContext* ctx, const f64* xy, const f64* z, const f64* rgba, i64 n, bool gouraud, Opacity opq,
-          TriangleBuffer* tb = nullptr, bool callerOwned = false) {
+// attr: the batch's colours (mode ATTR_FLAT / ATTR_GOURAUD) or its texture
+// coordinates (ATTR_TEX, sampled from *tex).
+void draw(RenderContext* ctx, const f64* xy, const f64* z, const f64* attr, i64 n, int mode, Opacity opq,
+          TriangleBuffer* tb = nullptr, bool callerOwned = false, const TexView* tex = nullptr) {
     NR_CHECK(hipSetDevice(ctx->device));
     settle(ctx);
     if (n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
     if (!ctx->depthTest) nr_materialize_depth(ctx);
-    TriSrc src{xy, z, rgba, gouraud ? 1 : 0, n};
+    TriSrc src;
+    src.xy = xy; src.z = z; src.attr = attr; src.mode = mode; src.n = n;
     const bool freeEligible = ctx->ct[3] == 1 && ctx->forceOrdered == 0;
     if (freeEligible && opq == OPQ_UNKNOWN) opq = device_opacity(ctx, src);
-    if (freeEligible && opq == OPQ_OPAQUE) draw_free(ctx, src, tb, callerOwned);
-    else draw_ordered(ctx, src, tb, callerOwned);
+    if (freeEligible && opq == OPQ_OPAQUE) draw_free(ctx, src, tb, callerOwned, false, tex);
+    else draw_ordered(ctx, src, tb, callerOwned, tex);
+}
+
+// A textured batch: the texture is checked (the sampler's clamp to w-2 / h-2
+// needs two texels each way), a texture aliasing the target is sampled from a
+// snapshot (as DrawTexture), and the batch is opaque exactly when the texture
+// has no alpha (every texel's alpha is then 1) -- no scan of the batch.
+// Recorded primitive draws run first.  While the batch is pending the texture
+// must stay alive as for DrawTexture (DestroyTexture settles every context).
+bool check_texture(RenderContext* ctx, const Texture* tex, const char* what) {
+    const char* why = nullptr;
+    if (!tex || !tex->buffer) why = "NULL texture";
+    else if (tex->width < 2 || tex->height < 2) why = "texture narrower or lower than 2 texels";
+    else if (tex->width >= (1 << 29) || tex->height >= (1 << 29)) why = "texture side of 2^29 texels or more";
+    else if (tex->device != ctx->device) why = "texture on another device";
+    if (!why) return true;
+    nr_set_error_msg((std::string(what) + ": " + why).c_str());
+    return false;
+}
+
+void draw_textured(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv, i64 n,
+                   TriangleBuffer* tb, bool callerOwned) {
+    settle(ctx);   // (a re-run of the pending batch comes before a snapshot of the target)
+    TexSrc ts = nr_tex_source(ctx, tex);
+    const TexView tv = tex_view(ts.ptr, tex->width, tex->height, tex->enableAlpha);
+    draw(ctx, xy, z, uv, n, ATTR_TEX, tex->enableAlpha ? OPQ_BLENDED : OPQ_OPAQUE, tb, callerOwned, &tv);
+    if (ts.tmp) {   // (rare: the snapshot must outlive the batch and any re-run of it)
+        settle(ctx);
+        nr_tex_release(ctx, ts);
+    }
 }
 
 }  // namespace
@@ -270,10 +304,10 @@ void DrawTrianglesDevice(RenderContext* ctx, const f64* xy, const f64* z, const 
         f64* dc = dz + zn;
         NR_CHECK(hipMemcpyAsync(dxy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
         NR_CHECK(hipMemcpyAsync(dc, rgba, (size_t)n * ncol * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
-        draw(ctx, dxy, z, dc, n, gouraud, OPQ_UNKNOWN, nullptr, z != nullptr);   // z stays the caller's
+        draw(ctx, dxy, z, dc, n, gouraud ? ATTR_GOURAUD : ATTR_FLAT, OPQ_UNKNOWN, nullptr, z != nullptr);   // z stays the caller's
         return;
     }
-    draw(ctx, xy, z, rgba, n, gouraud, OPQ_UNKNOWN, nullptr, true);
+    draw(ctx, xy, z, rgba, n, gouraud ? ATTR_GOURAUD : ATTR_FLAT, OPQ_UNKNOWN, nullptr, true);
 }
 
 // New: triangles from host arrays (copied to HBM first).
@@ -294,27 +328,71 @@ void DrawTriangles(RenderContext* ctx, const f64* xy, const f64* z, const f64* r
     if (z) NR_CHECK(hipMemcpyAsync(dz, z, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
     NR_CHECK(hipMemcpyAsync(dc, rgba, (size_t)n * ncol * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
     NR_CHECK(hipStreamSynchronize(ctx->stream));   // caller may reuse its arrays on return
-    draw(ctx, dxy, z ? dz : nullptr, dc, n, gouraud, host_opacity(rgba, n, gouraud), nullptr, false);
+    draw(ctx, dxy, z ? dz : nullptr, dc, n, gouraud ? ATTR_GOURAUD : ATTR_FLAT, host_opacity(rgba, n, gouraud), nullptr,
+         false);
+}
+
+// New: textured triangles from host arrays (uv: n*6 texel coordinates).
+void DrawTexturedTriangles(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv, i64 n) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    nr_settle(ctx);   // a pending batch may still read the staging buffer; recorded draws come first
+    if (!check_texture(ctx, tex, "DrawTexturedTriangles") || n <= 0) return;
+    const size_t zn = ((size_t)n * 3 + 1) & ~(size_t)1;   // keeps the uv 16-byte aligned
+    f64* stage_buf[1] = {ctx->tri.stage};
+    if (!grow_set(stage_buf, &ctx->tri.stage_cap, (size_t)n * 12 + zn)) return;
+    ctx->tri.stage = stage_buf[0];
+    f64* dxy = ctx->tri.stage;
+    f64* dz = dxy + (size_t)n * 6;
+    f64* duv = dz + zn;
+    NR_CHECK(hipMemcpyAsync(dxy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    if (z) NR_CHECK(hipMemcpyAsync(dz, z, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    NR_CHECK(hipMemcpyAsync(duv, uv, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    NR_CHECK(hipStreamSynchronize(ctx->stream));   // caller may reuse its arrays on return
+    draw_textured(ctx, tex, dxy, z ? dz : nullptr, duv, n, nullptr, false);
+}
+
+// New: textured triangles from device-resident arrays (as DrawTrianglesDevice).
+void DrawTexturedTrianglesDevice(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv,
+                                 i64 n) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    nr_settle(ctx);
+    if (!check_texture(ctx, tex, "DrawTexturedTrianglesDevice") || n <= 0) return;
+    if (((uintptr_t)xy | (uintptr_t)uv) & 15) {   // (16-byte vector loads: re-stage, as DrawTrianglesDevice)
+        const size_t zn = ((size_t)n * 3 + 1) & ~(size_t)1;
+        f64* stage_buf[1] = {ctx->tri.stage};
+        if (!grow_set(stage_buf, &ctx->tri.stage_cap, (size_t)n * 12 + zn)) return;
+        ctx->tri.stage = stage_buf[0];
+        f64* dxy = ctx->tri.stage;
+        f64* duv = dxy + (size_t)n * 6 + zn;
+        NR_CHECK(hipMemcpyAsync(dxy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
+        NR_CHECK(hipMemcpyAsync(duv, uv, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
+        draw_textured(ctx, tex, dxy, z, duv, n, nullptr, z != nullptr);
+        return;
+    }
+    draw_textured(ctx, tex, xy, z, uv, n, nullptr, true);
 }
 
 // New: a device-resident triangle soup (the H2D point; drawn many times).
-TriangleBuffer* CreateTriangleBuffer(i64 n, const f64* xy, const f64* z, const f64* rgba, bool gouraud) {
+static TriangleBuffer* create_buffer(i64 n, const f64* xy, const f64* z, const f64* rgba, bool gouraud,
+                                     const f64* uv) {
     static std::atomic<u64> g_uid{0};
     TriangleBuffer* tb = new TriangleBuffer();
     tb->uid = ++g_uid;
     tb->n = n;
     tb->gouraud = gouraud;
-    tb->opaque = n > 0 && host_opacity(rgba, n, gouraud) == OPQ_OPAQUE;
+    tb->textured = uv != nullptr;
+    tb->opaque = !uv && n > 0 && host_opacity(rgba, n, gouraud) == OPQ_OPAQUE;
     std::vector<f64> cb;
     if (n > 0) cb = host_cluster_boxes(xy, n);
     NR_CHECK(hipGetDevice(&tb->device));
     hipStream_t s = nr_stream_for(tb->device);
-    const size_t ncol = gouraud ? 12 : 4;
+    const size_t ncol = uv ? 6 : (gouraud ? 12 : 4);
     if (n > 0) {
+        f64** attr = uv ? &tb->uv : &tb->rgba;
         NR_CHECK(hipMalloc(&tb->xy, (size_t)n * 6 * sizeof(f64)));
-        NR_CHECK(hipMalloc(&tb->rgba, (size_t)n * ncol * sizeof(f64)));
+        NR_CHECK(hipMalloc(attr, (size_t)n * ncol * sizeof(f64)));
         NR_CHECK(hipMemcpyAsync(tb->xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, s));
-        NR_CHECK(hipMemcpyAsync(tb->rgba, rgba, (size_t)n * ncol * sizeof(f64), hipMemcpyHostToDevice, s));
+        NR_CHECK(hipMemcpyAsync(*attr, uv ? uv : rgba, (size_t)n * ncol * sizeof(f64), hipMemcpyHostToDevice, s));
         if (z) {
             NR_CHECK(hipMalloc(&tb->z, (size_t)n * 3 * sizeof(f64)));
             NR_CHECK(hipMemcpyAsync(tb->z, z, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, s));
@@ -334,6 +412,22 @@ TriangleBuffer* CreateTriangleBuffer(i64 n, const f64* xy, const f64* z, const f
     return tb;
 }
 
+TriangleBuffer* CreateTriangleBuffer(i64 n, const f64* xy, const f64* z, const f64* rgba, bool gouraud) {
+    return create_buffer(n, xy, z, rgba, gouraud, nullptr);
+}
+
+// New: a device-resident textured triangle soup (uv: n*6 texel coordinates).
+// No texture is bound: DrawTexturedTriangleBuffer names one per draw, and the
+// buffer's binning (which reads only xy) stays warm across textures.
+TriangleBuffer* CreateTexturedTriangleBuffer(i64 n, const f64* xy, const f64* z, const f64* uv) {
+    if (!uv && n > 0) {
+        nr_set_error_msg("CreateTexturedTriangleBuffer: NULL uv");
+        return nullptr;
+    }
+    static const f64 none[6] = {0, 0, 0, 0, 0, 0};
+    return create_buffer(n, xy, z, nullptr, false, uv ? uv : none);
+}
+
 void DestroyTriangleBuffer(TriangleBuffer* tb) {
     if (!tb) return;
     // a context's pending batch may reference tb: the stream sync below
@@ -345,6 +439,7 @@ void DestroyTriangleBuffer(TriangleBuffer* tb) {
     if (tb->xy) NR_CHECK(hipFree(tb->xy));
     if (tb->z) NR_CHECK(hipFree(tb->z));
     if (tb->rgba) NR_CHECK(hipFree(tb->rgba));
+    if (tb->uv) NR_CHECK(hipFree(tb->uv));
     if (tb->cbox) NR_CHECK(hipFree(tb->cbox));
     delete tb;
 }
@@ -352,8 +447,25 @@ void DestroyTriangleBuffer(TriangleBuffer* tb) {
 i64 GetTriangleBufferCount(TriangleBuffer* tb) { return tb->n; }
 
 void DrawTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb) {
+    if (tb->textured) {
+        nr_set_error_msg("DrawTriangleBuffer: a textured buffer (use DrawTexturedTriangleBuffer)");
+        return;
+    }
     // a TriangleBuffer never changes: its binning may overlap the previous batch's raster
-    draw(ctx, tb->xy, tb->z, tb->rgba, tb->n, tb->gouraud, tb->opaque ? OPQ_OPAQUE : OPQ_BLENDED, tb, false);
+    draw(ctx, tb->xy, tb->z, tb->rgba, tb->n, tb->gouraud ? ATTR_GOURAUD : ATTR_FLAT,
+         tb->opaque ? OPQ_OPAQUE : OPQ_BLENDED, tb, false);
+}
+
+// New: a textured TriangleBuffer sampled from `tex` (chosen per draw).
+void DrawTexturedTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb, Texture* tex) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    if (!tb || !tb->textured) {
+        nr_set_error_msg("DrawTexturedTriangleBuffer: not a textured buffer (use DrawTriangleBuffer)");
+        return;
+    }
+    if (ctx->recording) nr_settle(ctx);   // recorded draws come first
+    if (!check_texture(ctx, tex, "DrawTexturedTriangleBuffer")) return;
+    draw_textured(ctx, tex, tb->xy, tb->z, tb->uv, tb->n, tb, false);
 }
 
 // New: count covered on-screen pixel x triangle pairs (the "shaded+Z-tested

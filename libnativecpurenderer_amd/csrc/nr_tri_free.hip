@@ -753,7 +753,7 @@ constexpr int HTS_WIDE = 1024;     // hash slots of the 512-thread instance (its
 constexpr int MAXPROBE = 16;       // linear-probe limit: a winner not placed / found within it loads directly
 constexpr int OVF_Q = 1;           // directly loaded records in flight per thread (0: one at a time, in pass 3)
 
-template <bool GOURAUD, int HS = HTS>
+template <int MODE, int HS = HTS>
 struct ShadeStage {
     // Gouraud record: sx0 sy0 e1x e1y e2x e2y inv | c0 rgb | (c1-c0) rgb | (c2-c0) rgb
     // flat record: rgb.  Alpha is not staged: every batch routed here has
@@ -763,9 +763,9 @@ struct ShadeStage {
     // The records of the shading pass overwrite the keys (each thread keeps
     // its pixels' winners in registers by then) and run on into `extra`, so
     // a tile stages RT records in KEY_BYTES + EXTRA bytes.
-    static constexpr int REC = RecLen<GOURAUD>::REC;
+    static constexpr int REC = RecLen<MODE>::REC;
     static constexpr int KEY_BYTES = TH * (TW + 1) * 8;
-    static constexpr int EXTRA = GOURAUD ? REC_EXTRA : 0;
+    static constexpr int EXTRA = MODE != ATTR_FLAT ? REC_EXTRA : 0;
     static constexpr int RT_RAW = (KEY_BYTES + EXTRA) / (REC * 8);
     static constexpr int RT = RT_RAW < TH * TW ? RT_RAW : TH * TW;   // staged records per tile
     static constexpr int HT = 0, HIDX = HS * 4, DIDX = HS * 6;
@@ -776,6 +776,22 @@ struct ShadeStage {
 template <int HS>
 __device__ __forceinline__ u32 ht_hash(u32 id) { return (id * 2654435761u) >> (32 - __builtin_ctz(HS)); }
 
+// Dense index of winner `id` among the tile's staged records (pass 1's hash
+// table), or `none` when it is not staged (its record is loaded directly).
+// (The textured pass 3 uses it; the flat / Gouraud loop keeps its own inline
+// probe: calling this there changes the register figures of 13 of the existing
+// Gouraud k_vis instances, which are to stay as they are.)
+template <int HS>
+__device__ __forceinline__ int staged_record(const u32* ht, const unsigned short* hidx, u32 id, int none) {
+    u32 h = ht_hash<HS>(id);
+    for (int probe = 0; probe < MAXPROBE; ++probe, h = (h + 1) & (HS - 1)) {
+        const u32 cur = ht[h];
+        if (cur == id) return hidx[h];
+        if (cur == 0) break;
+    }
+    return none;
+}
+
 // Shades the tile from its LDS keys (`key` at row stride KS).  Pass 1: each
 // thread takes its PPT pixels (p = tid + k*NT), stores their depth, keeps
 // their winners in registers and enters the distinct winners in an LDS hash
@@ -783,14 +799,14 @@ __device__ __forceinline__ u32 ht_hash(u32 id) { return (id * 2654435761u) >> (3
 // global loads: one latency round), written over the keys.  Pass 3: colour,
 // ApplyPixel, framebuffer (+ u8 frame) written once.  A winner past the RT
 // staged records (or not placed within MAXPROBE probes) loads its own record.
-template <int ZMODE, bool GOURAUD, int NT, int HS>
+template <int ZMODE, int MODE, int NT, int HS>
 __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0, int wlim, int hlim,
                                            const u64* key, unsigned char* lds, u32& nU) {
-    using St = ShadeStage<GOURAUD, HS>;
+    using St = ShadeStage<MODE, HS>;
     constexpr int PPT = TH * TW / NT;
     static_assert(PPT <= 32, "overflow bitmask");
     const int tid = opaque_tid();
-    if constexpr (!GOURAUD) {
+    if constexpr (MODE == ATTR_FLAT) {
         // Flat: a winner's colour is its rgb -- no record to stage, so no
         // winner dedup: each pixel loads its winner's colour itself (the few
         // distinct winners of a tile stay in L2), FQ pixels' loads in flight
@@ -810,7 +826,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                 id[j] = (u32)kv;
                 store_depth<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, kv);
                 if (id[j]) {
-                    const f64* q = fp.src.rgba + ((i64)id[j] - 1) * 4;
+                    const f64* q = fp.src.rgba() + ((i64)id[j] - 1) * 4;
                     const double2 rg = *reinterpret_cast<const double2*>(q);
                     c[j][0] = rg.x; c[j][1] = rg.y; c[j][2] = q[2];
                 }
@@ -889,57 +905,121 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
     const u32 U = nU < (u32)St::RT ? nU : (u32)St::RT;
     // two winners per thread per round, both records' loads in flight
     for (u32 u = tid; u < U; u += 2 * NT) {
-        RecordSrc<GOURAUD> s0, s1;
+        RecordSrc<MODE> s0, s1;
         const bool two = u + NT < U;
-        load_record_src<GOURAUD>(fp, (i64)didx[u] - 1, s0);
-        if (two) load_record_src<GOURAUD>(fp, (i64)didx[u + NT] - 1, s1);
-        build_record<GOURAUD>(fp, s0, rec + u * St::REC);
-        if (two) build_record<GOURAUD>(fp, s1, rec + (u + NT) * St::REC);
+        load_record_src<MODE>(fp, (i64)didx[u] - 1, s0);
+        if (two) load_record_src<MODE>(fp, (i64)didx[u + NT] - 1, s1);
+        build_record<MODE>(fp, s0, rec + u * St::REC);
+        if (two) build_record<MODE>(fp, s1, rec + (u + NT) * St::REC);
     }
     __syncthreads();
     NR_PROBE_STAMP(5);
+    const TexView& tv = fp.tex;   // (textured batches)
+    if constexpr (MODE == ATTR_TEX) {
+        // Textured: a pixel's colour is a dependent gather (record -> u, v ->
+        // texel, 24 B), so a thread first forms the texel offsets of TQ of its
+        // pixels, then issues their loads together, and only then consumes
+        // them (as the flat path keeps FQ loads in flight).  Ordinary cached
+        // loads: the texture is read again by other tiles.
+        static_assert(OVF_Q > 0, "unstaged winners are shaded in pass 3b");
+        constexpr int TQ = 2;
+        static_assert(PPT % TQ == 0, "pixel groups");
 #pragma unroll 1
-    for (int k = 0; k < PPT; ++k) {
-        const int p = tid + k * NT, lx = p & (TW - 1), ly = p / TW;
-        if (lx >= wlim || ly >= hlim) continue;
-        const i64 px = x0 + lx, py = y0 + ly;
-        const i64 gp = py * fp.W + px;
-        u32 id = 0;
+        for (int k0 = 0; k0 < PPT; k0 += TQ) {
+            i64 ti[TQ];   // texel offset, or -1: nothing to fetch
 #pragma unroll
-        for (int q = 0; q < PPT; ++q)
-            if (q == k) id = ids[q];
-        if (!id) {
-            if (fp.pendColor) {
-                const f64 v = fp.pendColorValue;
-                store_colour(fp, gp, px, py, v, v, v, v);
+            for (int j = 0; j < TQ; ++j) {
+                const int k = k0 + j;
+                ti[j] = -1;
+                const int p = tid + k * NT, lx = p & (TW - 1), ly = p / TW;
+                if (lx >= wlim || ly >= hlim) continue;
+                const i64 px = x0 + lx, py = y0 + ly;
+                u32 id = 0;
+#pragma unroll
+                for (int q = 0; q < PPT; ++q)
+                    if (q == k) id = ids[q];
+                if (!id) {
+                    if (fp.pendColor) {
+                        const f64 v = fp.pendColorValue;
+                        store_colour(fp, py * fp.W + px, px, py, v, v, v, v);
+                    }
+                    continue;
+                }
+                if ((ovf >> k) & 1u) continue;
+                const int d = staged_record<HS>(ht, hidx, id, St::RT);
+                NR_DEV_CHECK(d >= St::RT || (u32)d < U,
+                             "shade_tile: pixel (%ld, %ld) reads record %d of %u staged (winner %u)", (long)px, (long)py, d,
+                             U, id);
+                NR_DEV_CHECK(id <= (u32)fp.src.n, "shade_tile: pixel (%ld, %ld) winner %u of %ld triangles", (long)px,
+                             (long)py, id, (long)fp.src.n);
+                if (d >= St::RT) {
+                    ovf |= 1u << k;
+                    continue;
+                }
+                ti[j] = record_texel(tv, rec + d * St::REC, px, py);
             }
-            continue;
+            f64 c[TQ][3];
+#pragma unroll
+            for (int j = 0; j < TQ; ++j) {
+                if (ti[j] < 0) continue;
+                const f64* q = tv.ptr + ti[j];
+                c[j][0] = q[0]; c[j][1] = q[1]; c[j][2] = q[2];
+            }
+#pragma unroll
+            for (int j = 0; j < TQ; ++j) {
+                if (ti[j] < 0) continue;
+                const int p = tid + (k0 + j) * NT, lx = p & (TW - 1), ly = p / TW;
+                const i64 px = x0 + lx, py = y0 + ly;
+                const i64 gp = py * fp.W + px;
+                f64 cr = c[j][0], cg = c[j][1], cb = c[j][2], ca = 1.0;
+                apply_winner(fp, gp, cr, cg, cb, ca);
+                store_colour(fp, gp, px, py, cr, cg, cb, ca);
+            }
         }
-        if ((ovf >> k) & 1u) continue;
-        int d = St::RT;
-        u32 h = ht_hash<HS>(id);
-        for (int probe = 0; probe < MAXPROBE; ++probe, h = (h + 1) & (HS - 1)) {
-            const u32 cur = ht[h];
-            if (cur == id) { d = hidx[h]; break; }
-            if (cur == 0) break;
+    } else {
+#pragma unroll 1
+        for (int k = 0; k < PPT; ++k) {
+            const int p = tid + k * NT, lx = p & (TW - 1), ly = p / TW;
+            if (lx >= wlim || ly >= hlim) continue;
+            const i64 px = x0 + lx, py = y0 + ly;
+            const i64 gp = py * fp.W + px;
+            u32 id = 0;
+#pragma unroll
+            for (int q = 0; q < PPT; ++q)
+                if (q == k) id = ids[q];
+            if (!id) {
+                if (fp.pendColor) {
+                    const f64 v = fp.pendColorValue;
+                    store_colour(fp, gp, px, py, v, v, v, v);
+                }
+                continue;
+            }
+            if ((ovf >> k) & 1u) continue;
+            int d = St::RT;
+            u32 h = ht_hash<HS>(id);
+            for (int probe = 0; probe < MAXPROBE; ++probe, h = (h + 1) & (HS - 1)) {
+                const u32 cur = ht[h];
+                if (cur == id) { d = hidx[h]; break; }
+                if (cur == 0) break;
+            }
+            f64 cr, cg, cb, ca;
+            NR_DEV_CHECK(d >= St::RT || (u32)d < U, "shade_tile: pixel (%ld, %ld) reads record %d of %u staged (winner %u)",
+                         (long)px, (long)py, d, U, id);
+            NR_DEV_CHECK(id <= (u32)fp.src.n, "shade_tile: pixel (%ld, %ld) winner %u of %ld triangles", (long)px, (long)py, id,
+                         (long)fp.src.n);
+            if (d < St::RT) {
+                record_colour<MODE>(tv, rec + d * St::REC, px, py, cr, cg, cb, ca);
+            } else if (OVF_Q) {
+                ovf |= 1u << k;
+                continue;
+            } else {   // overflow: load this pixel's winner directly
+                f64 r[St::REC];
+                make_record<MODE>(fp, (i64)id - 1, r);
+                record_colour<MODE>(tv, r, px, py, cr, cg, cb, ca);
+            }
+            apply_winner(fp, gp, cr, cg, cb, ca);
+            store_colour(fp, gp, px, py, cr, cg, cb, ca);
         }
-        f64 cr, cg, cb, ca;
-        NR_DEV_CHECK(d >= St::RT || (u32)d < U, "shade_tile: pixel (%ld, %ld) reads record %d of %u staged (winner %u)",
-                     (long)px, (long)py, d, U, id);
-        NR_DEV_CHECK(id <= (u32)fp.src.n, "shade_tile: pixel (%ld, %ld) winner %u of %ld triangles", (long)px, (long)py, id,
-                     (long)fp.src.n);
-        if (d < St::RT) {
-            record_colour<GOURAUD>(rec + d * St::REC, px, py, cr, cg, cb, ca);
-        } else if (OVF_Q) {
-            ovf |= 1u << k;
-            continue;
-        } else {   // overflow: load this pixel's winner directly
-            f64 r[St::REC];
-            make_record<GOURAUD>(fp, (i64)id - 1, r);
-            record_colour<GOURAUD>(r, px, py, cr, cg, cb, ca);
-        }
-        apply_winner(fp, gp, cr, cg, cb, ca);
-        store_colour(fp, gp, px, py, cr, cg, cb, ca);
     }
     // pass 3b: pixels whose winner is not staged, OVF_Q at a time: their
     // records' loads are independent and in flight together
@@ -948,7 +1028,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
         while (ovf) {
             constexpr int Q = OVF_Q > 0 ? OVF_Q : 1;
             int kq[Q];
-            RecordSrc<GOURAUD> src[Q];
+            RecordSrc<MODE> src[Q];
 #pragma unroll
             for (int j = 0; j < Q; ++j) {
                 kq[j] = -1;
@@ -959,7 +1039,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
 #pragma unroll
                 for (int q = 0; q < PPT; ++q)
                     if (q == kq[j]) id = ids[q];
-                load_record_src<GOURAUD>(fp, (i64)id - 1, src[j]);
+                load_record_src<MODE>(fp, (i64)id - 1, src[j]);
             }
 #pragma unroll
             for (int j = 0; j < Q; ++j) {
@@ -968,9 +1048,9 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                 const i64 px = x0 + lx, py = y0 + ly;
                 const i64 gp = py * fp.W + px;
                 f64 r[St::REC];
-                build_record<GOURAUD>(fp, src[j], r);
+                build_record<MODE>(fp, src[j], r);
                 f64 cr, cg, cb, ca;
-                record_colour<GOURAUD>(r, px, py, cr, cg, cb, ca);
+                record_colour<MODE>(tv, r, px, py, cr, cg, cb, ca);
                 apply_winner(fp, gp, cr, cg, cb, ca);
                 store_colour(fp, gp, px, py, cr, cg, cb, ca);
             }
@@ -1080,7 +1160,7 @@ __device__ __forceinline__ void warm_report(const WarmCheck& wc, u32 why, u32 a,
     __hip_atomic_store(&wc.hfail[0], why, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-template <int ZMODE, bool COUNT, bool GOURAUD, bool FLAT, int NT>   // ZMODE 0: no test, 1: LESS+write, 2: LESS no write
+template <int ZMODE, bool COUNT, int MODE, bool FLAT, int NT>   // ZMODE 0: no test, 1: LESS+write, 2: LESS no write
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) void k_vis(const FrameParams fp, const uint4* __restrict__ items,
                                              const u32* __restrict__ list,
                                              u64* __restrict__ kslot, u32* __restrict__ done,
@@ -1094,8 +1174,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
     // the 512-thread instance has LDS to spare for a larger hash table (two
     // workgroups per CU)
     constexpr int HS = NT > VWG ? HTS_WIDE : HTS;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[ShadeStage<GOURAUD, HS>::BYTES];
-    u64* const key = reinterpret_cast<u64*>(lds + ShadeStage<GOURAUD, HS>::KEY_OFF);
+    __shared__ __attribute__((aligned(16))) unsigned char lds[ShadeStage<MODE, HS>::BYTES];
+    u64* const key = reinterpret_cast<u64*>(lds + ShadeStage<MODE, HS>::KEY_OFF);
     __shared__ u32 zin[ZMODE == 2 ? TH * KS : 1];
     __shared__ u32 nU;
     __shared__ int sLast;
@@ -1283,8 +1363,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
             // rows the f32 bound cannot decide: C2 -2 %, one rank's 8-way C3
             // share -3 % (k_vis 44 -> 40 us; profiles/r03_c3/ab_span32.txt).
             // Flat batches keep the f64 spans (the f32 ones cost the flat
-            // instances 8-24 B/lane of spills).
-            constexpr bool SPAN32 = GOURAUD && ZMODE != 2 && !COUNT;
+            // instances 8-24 B/lane of spills), and so do textured batches in
+            // the lane raster (with the f32 spans its LESS + write instances
+            // need 12 B/lane of scratch; with the f64 ones 119 VGPRs, none).
+            constexpr bool SPAN32 = (MODE == ATTR_GOURAUD || (MODE == ATTR_TEX && FLAT)) && ZMODE != 2 && !COUNT;
             if constexpr (FLAT) {
                 // rows: the chunk's (triangle, row) pairs, 64 per window
                 const u32 nr = r0 < r1 ? (u32)(r1 - r0) : 0u;
@@ -1293,7 +1375,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
                 const int r0x = r0 - (int)rex;   // (row of slot s: s + r0x of its triangle's lane)
                 Span32 S32;
                 if (SPAN32) S32 = span32_setup(sx, sy, sl, (f64)x0, (f64)y0);
-                u32* const mk = reinterpret_cast<u32*>(lds + ShadeStage<GOURAUD, HS>::HT) + wave * 64;
+                u32* const mk = reinterpret_cast<u32*>(lds + ShadeStage<MODE, HS>::HT) + wave * 64;
                 int rcar = -1;
                 for (u32 rb = 0; rb < R; rb += 64) {
                     const int o = window_owner(mk, lane, rex, nr, rb, rcar);
@@ -1426,7 +1508,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         NR_PROBE_STAMP(2);
         if (!multi) {   // the whole list was in this slice: shade now
             if (rlo < rcap)
-                shade_tile<ZMODE, GOURAUD, NT, HS>(fp, x0, y0 + rlo, wlim, rcap - rlo, key + rlo * KS, lds, nU);
+                shade_tile<ZMODE, MODE, NT, HS>(fp, x0, y0 + rlo, wlim, rcap - rlo, key + rlo * KS, lds, nU);
             continue;
         }
         // split tile (a dense tile's slice): the slice's keys go to its own
@@ -1495,7 +1577,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         }
         __syncthreads();
         NR_PROBE_STAMP(3);
-        shade_tile<ZMODE, GOURAUD, NT, HS>(fp, x0, y0, wlim, hlim, key, lds, nU);
+        shade_tile<ZMODE, MODE, NT, HS>(fp, x0, y0, wlim, hlim, key, lds, nU);
     }   // work items
 #if NR_PROBE
     if (tid == 0 && pr_item != ~0u) probe_item(pr_item, pr_d, pr_t0, __builtin_amdgcn_s_memrealtime(), NT);
@@ -1536,7 +1618,7 @@ struct VisArgs {
     WarmCheck wc;   // (a warm batch's checks; zero: a cold batch)
 };
 
-template <int Z, bool C, bool G>
+template <int Z, bool C, int G>
 void launch_vis(const FrameParams& fp, const TriScratch& sc, const VisArgs& va, u32 grid, hipStream_t s,
                 hipEvent_t start, hipEvent_t stop) {
     const WarmCheck wc = va.wc;
@@ -1561,7 +1643,7 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const VisArgs& va, 
 #undef NR_VIS
 }
 
-template <int Z, bool G>
+template <int Z, int G>
 void launch_vis_z(const FrameParams& fp, const TriScratch& sc, const VisArgs& va, u32 grid, hipStream_t s,
                   hipEvent_t start, hipEvent_t stop) {
     if (fp.fragCounter) launch_vis<Z, true, G>(fp, sc, va, grid, s, start, stop);
@@ -1569,9 +1651,10 @@ void launch_vis_z(const FrameParams& fp, const TriScratch& sc, const VisArgs& va
 }
 
 static void launch_vis_any(const FrameParams& fp, const TriScratch& sc, const VisArgs& va, u32 grid, hipStream_t s,
-                           hipEvent_t start, hipEvent_t stop, int zmode, bool g) {
-#define NR_VZ(ZM) (g ? launch_vis_z<ZM, true>(fp, sc, va, grid, s, start, stop) \
-                     : launch_vis_z<ZM, false>(fp, sc, va, grid, s, start, stop))
+                           hipEvent_t start, hipEvent_t stop, int zmode, int mode) {
+#define NR_VZ(ZM) (mode == ATTR_TEX ? launch_vis_z<ZM, ATTR_TEX>(fp, sc, va, grid, s, start, stop) \
+                 : mode == ATTR_GOURAUD ? launch_vis_z<ZM, ATTR_GOURAUD>(fp, sc, va, grid, s, start, stop) \
+                 : launch_vis_z<ZM, ATTR_FLAT>(fp, sc, va, grid, s, start, stop))
     if (zmode == 1) NR_VZ(1);
     else if (zmode == 2) NR_VZ(2);
     else NR_VZ(0);
@@ -1676,7 +1759,7 @@ static int free_enqueue(RenderContext* ctx, const TriSrc& src, const FrameParams
     TriScratch::FreeSet& F = sc.fset[si];
     const int ntiles = fp.tiles_x * fp.tiles_y;
     const int zmode = fp.depthTest ? (fp.depthWrite ? 1 : 2) : 0;
-    const bool g = src.gouraud != 0;
+    const int mode = src.mode;
     if (!F.evBin) { F.evBin = sync_event(); F.evVis = sync_event(); }
     if (sb == sa) main_after_side_binning(ctx);
     // the set's buffers are rewritten (binning stream) only after the raster
@@ -1882,7 +1965,7 @@ static int free_enqueue(RenderContext* ctx, const TriSrc& src, const FrameParams
         visDone = true;
     } else if (grid > 0) {
         launch_vis_any(fpt, sc, VisArgs{F.fitems, F.flist, F.dplan, WarmCheck{nullptr, nullptr, nullptr, 0u, 0u, nullptr, 0u}},
-                       grid, sa, nullptr, F.evVis, zmode, g);
+                       grid, sa, nullptr, F.evVis, zmode, mode);
         NR_CHECK(hipGetLastError());
         visDone = true;
     }
@@ -2292,7 +2375,7 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
         fpt.tstamp = nr_timing_stamp(ctx, NRK_TILE_RASTER);
         const WarmCheck wc{wstat, F.fcur, binOff, tag, epoch + 1, sc.dfail, (u32)loose};
         launch_vis_any(fpt, sc, VisArgs{S.items, F.flist, visPlan, wc}, std::min<u32>(S.nitems, 8192), sa, nullptr,
-                       F.evVis, zmode, fp.src.gouraud != 0);
+                       F.evVis, zmode, fp.src.mode);
         NR_CHECK(hipGetLastError());
         visDone = true;
     }
@@ -2305,8 +2388,9 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
 
 // ordered: the batch is rasterised by the ordered raster (blending, Z test
 // without write...): the same binning, each tile's list sorted in LDS.
-void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, bool ordered) {
-    FrameParams fp = frame_params(ctx, src);
+void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, bool ordered,
+               const TexView* tex) {
+    FrameParams fp = frame_params(ctx, src, tex);
     if (ctx->frameOutput && fp.pendColor) {
         const size_t n = (size_t)nr_frame_bytes(ctx);
         if (n <= ctx->frameU8cap) fp.frameU8 = ctx->frameU8;

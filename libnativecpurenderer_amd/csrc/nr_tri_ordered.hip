@@ -96,9 +96,9 @@ enum {
     S_X0 = 0, S_Y0, S_X1, S_Y1, S_X2, S_Y2,   // screen-space vertices
     S_E1X, S_E1Y, S_E2X, S_E2Y, S_INV,         // barycentric setup
     S_Z0, S_DZ1, S_DZ2,                        // depth: z0, z1-z0, z2-z0
-    S_C0,                                      // colour c0[4] (flat: the colour)
-    S_D1 = S_C0 + 4,                           // c1-c0 [4] (Gouraud)
-    S_D2 = S_D1 + 4,                           // c2-c0 [4] (Gouraud)
+    S_C0,                                      // colour c0[4] (flat: the colour; textured: u0 v0)
+    S_D1 = S_C0 + 4,                           // c1-c0 [4] (Gouraud; textured: u1-u0 v1-v0)
+    S_D2 = S_D1 + 4,                           // c2-c0 [4] (Gouraud; textured: u2-u0 v2-v0)
     // flat: ApplyPixel's per-triangle terms (cpp:529-535), formed once at setup
     S_FR = S_D2 + 4, S_FG, S_FB, S_FA,         // src * colourTransform
     S_OM, S_RA, S_GA, S_BA,                    // 1 - a, src * a
@@ -126,11 +126,17 @@ __device__ __forceinline__ u64 window_bits(int xs, int xe) {
 // by k_tile_sort (tstart = the plan's list offsets: [off[tile], off[tile + 1]));
 // the batch is a no-op unless plan[3] (fits); otherwise [tstart, tend) of the
 // globally sorted pairs.
+// MODE (AttrMode): a textured batch interpolates (u, v) where a Gouraud batch
+// interpolates its colour, fetches the texel (tex_index; rgb, and alpha from
+// an RGBA texture) and blends it by the same ApplyPixel arithmetic.  Its colour
+// varies over the triangle, so it takes none of the flat shortcuts.
 // 4 waves per SIMD (6: 80 VGPRs, 85 spilled -- C5 raster 740 -> 1355 us)
-template <bool GOURAUD, bool DEPTH, bool COUNT, bool RGBA, bool BINNED>
+template <int MODE, bool DEPTH, bool COUNT, bool RGBA, bool BINNED>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_tile_raster(const FrameParams fp, const u32* __restrict__ list,
                                                     const u32* __restrict__ tstart, const u32* __restrict__ tend,
                                                     const f64* __restrict__ rec, const u32* __restrict__ plan) {
+    constexpr bool GOURAUD = MODE == ATTR_GOURAUD, TEX = MODE == ATTR_TEX;
+    constexpr bool FLATC = MODE == ATTR_FLAT;   // one colour per triangle: the per-triangle blend terms apply
     const int tile = blockIdx.x;
     const int tx = tile % fp.tiles_x, ty = tile / fp.tiles_x;
     const i64 x0 = (i64)tx * TW, y0 = (i64)ty * TH;
@@ -211,7 +217,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
     // or off: C5's common case).
     auto setup = [&](u32 cb, int sb) -> bool {
         const int cnt = (le - cb) < (u32)CH ? (int)(le - cb) : CH;
-        bool blendOnly = !GOURAUD;
+        bool blendOnly = FLATC;
         if (lane < cnt) {
             const int k = lane;
             const i64 t = list[cb + k];
@@ -234,8 +240,14 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                 zok = !fp.depthWrite && zb < zTileMin;   // zpass_all
                 ZPASS[sb][k] = zok;
             }
-            if (GOURAUD) {
-                const f64* c = fp.src.rgba + t * 12;
+            if (TEX) {
+                f64 uv[6];
+                load_tri_xy(fp.src.uv(), t, uv);
+                S[sb][S_C0][k] = uv[0]; S[sb][S_C0 + 1][k] = uv[1];
+                S[sb][S_D1][k] = uv[2] - uv[0]; S[sb][S_D1 + 1][k] = uv[3] - uv[1];
+                S[sb][S_D2][k] = uv[4] - uv[0]; S[sb][S_D2 + 1][k] = uv[5] - uv[1];
+            } else if (GOURAUD) {
+                const f64* c = fp.src.rgba() + t * 12;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     S[sb][S_C0 + j][k] = c[j];
@@ -243,7 +255,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                     S[sb][S_D2 + j][k] = c[8 + j] - c[j];
                 }
             } else {
-                const f64* c = fp.src.rgba + t * 4;
+                const f64* c = fp.src.rgba() + t * 4;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) S[sb][S_C0 + j][k] = c[j];
                 const f64 fR = c[0] * ct0, fG = c[1] * ct1, fB = c[2] * ct2, fA = c[3] * ct3;
@@ -331,7 +343,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
         // over the triangle (flat: src * colourTransform, src * a, 1 - a) is
         // formed once there: the same rounded values in the same expression
         // trees, so the result is bit-identical to the per-pixel form.
-        if (!GOURAUD && allBlend) {
+        if (FLATC && allBlend) {
             // every triangle of the chunk: ApplyPixel from the per-triangle
             // terms on the covered lanes (a loop with one path, so the pixel
             // registers are updated in place), only the triangles touching
@@ -369,7 +381,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
             }
             // (uniform: read into scalar registers, so the branches below are scalar)
             const bool ztest = DEPTH && !__builtin_amdgcn_readfirstlane((int)ZPASS[sb][k]);   // the depth expression is needed
-            if (!GOURAUD && !ztest) {
+            if (FLATC && !ztest) {
                 // flat colour, no per-pixel depth: ApplyPixel from the
                 // per-triangle terms on the covered lanes of each step
                 const f64 fA = __longlong_as_double((long long)uniform_u64((u64)__double_as_longlong(S[sb][S_FA][k])));
@@ -400,13 +412,13 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
             const f64 e1x = S[sb][S_E1X][k], e1y = S[sb][S_E1Y][k], e2x = S[sb][S_E2X][k], e2y = S[sb][S_E2Y][k];
             const f64 inv = S[sb][S_INV][k];
             f64 pa = 0, pb = 0;   // dx * e2y, dx * e1y of this lane's column
-            if (ztest || GOURAUD) {
+            if (ztest || !FLATC) {
                 const f64 dx = X - sx0;
                 pa = dx * e2y;
                 pb = dx * e1y;
             }
             f64 fR = 0, fG = 0, fB = 0, fA = 1, om = 0, RA = 0, GA = 0, BA = 0;
-            if (!GOURAUD) {   // ApplyPixel's per-triangle terms (cpp:529-535), formed at setup
+            if (FLATC) {   // ApplyPixel's per-triangle terms (cpp:529-535), formed at setup
                 fR = S[sb][S_FR][k]; fG = S[sb][S_FG][k]; fB = S[sb][S_FB][k]; fA = S[sb][S_FA][k];
                 om = S[sb][S_OM][k];
                 RA = S[sb][S_RA][k]; GA = S[sb][S_GA][k]; BA = S[sb][S_BA][k];
@@ -415,7 +427,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
             for (int r = 0; r < RPW; ++r) {
                 if (!__builtin_amdgcn_inverse_ballot_w64(lm[r])) continue;
                 f64 w1 = 0, w2 = 0;
-                if (ztest || GOURAUD) {
+                if (ztest || !FLATC) {
                     const f64 dy = (f64)(y0 + lrow0 + r * SR) - sy0;
                     w1 = (pa - e2x * dy) * inv;
                     w2 = (e1x * dy - pb) * inv;
@@ -426,7 +438,22 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                     zq = nr_quantize_depth_hw(zz);
                     if (!(zq < cz[r])) continue;
                 }
-                if (GOURAUD) {
+                if (TEX) {
+                    const f64 u = S[sb][S_C0 + 0][k] + S[sb][S_D1 + 0][k] * w1 + S[sb][S_D2 + 0][k] * w2;
+                    const f64 v = S[sb][S_C0 + 1][k] + S[sb][S_D1 + 1][k] * w1 + S[sb][S_D2 + 1][k] * w2;
+                    const f64* tq = fp.tex.ptr + tex_index(fp.tex, u, v);
+                    f64 R = tq[0], G = tq[1], B = tq[2];
+                    f64 A = fp.tex.ipp == 4 ? tq[3] : 1.0;
+                    // ApplyPixel (cpp:529-547) on the register-resident pixel
+                    R *= ct0; G *= ct1; B *= ct2; A *= ct3;
+                    if (A != 1) {
+                        R = cr[r] * (1 - A) + R * A;
+                        G = cg[r] * (1 - A) + G * A;
+                        B = cb[r] * (1 - A) + B * A;
+                    }
+                    cr[r] = R; cg[r] = G; cb[r] = B;
+                    if (RGBA) ca[r] = A;
+                } else if (GOURAUD) {
                     f64 R = S[sb][S_C0 + 0][k] + S[sb][S_D1 + 0][k] * w1 + S[sb][S_D2 + 0][k] * w2;
                     f64 G = S[sb][S_C0 + 1][k] + S[sb][S_D1 + 1][k] * w1 + S[sb][S_D2 + 1][k] * w2;
                     f64 B = S[sb][S_C0 + 2][k] + S[sb][S_D1 + 2][k] * w1 + S[sb][S_D2 + 2][k] * w2;
@@ -457,7 +484,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
     int buf = 0;
     bool allB = false;
     if (ls < le) {   // the first chunk: set up by wave 0
-        const bool bo = wave == 0 ? setup(ls, 0) : !GOURAUD;
+        const bool bo = wave == 0 ? setup(ls, 0) : FLATC;
         allB = __syncthreads_and(bo ? 1 : 0) != 0;
         spans(ls, 0);
         __syncthreads();
@@ -466,7 +493,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
     for (u32 base = ls; base < le; base += CH, buf ^= 1, ++ci) {
         const u32 nb = base + CH;
         const bool more = nb < le;
-        bool bo = !GOURAUD;
+        bool bo = FLATC;
         if (more && wave == (int)((ci + 1) & (NWAVE - 1))) bo = setup(nb, buf ^ 1);
         blend(buf, allB);
         if (more) {
@@ -524,7 +551,7 @@ __global__ __launch_bounds__(SORT_T) void k_tile_sort(const u32* __restrict__ of
     for (u32 i = tid; i < n; i += SORT_T) list[ls + i] = SL[i];
 }
 
-template <bool G, bool D, bool C, bool B>
+template <int G, bool D, bool C, bool B>
 void launch_raster(const FrameParams& fp, const u32* list, const u32* ts, const u32* te, int ntiles, hipStream_t s,
                    const f64* rec, const u32* plan, hipEvent_t start, hipEvent_t stop) {
     if (fp.ipp == 4)
@@ -539,11 +566,13 @@ template <bool C, bool B>
 void launch_raster_c(const FrameParams& fp, const u32* list, const u32* ts, const u32* te, int ntiles,
                      hipStream_t s, const f64* rec, const u32* plan = nullptr, hipEvent_t start = nullptr,
                      hipEvent_t stop = nullptr) {
-    const bool g = fp.src.gouraud != 0, d = fp.depthTest != 0;
-    if (g && d) launch_raster<true, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
-    else if (g) launch_raster<true, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
-    else if (d) launch_raster<false, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
-    else launch_raster<false, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    const bool g = fp.src.mode == ATTR_GOURAUD, t = fp.src.mode == ATTR_TEX, d = fp.depthTest != 0;
+    if (t && d) launch_raster<ATTR_TEX, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (t) launch_raster<ATTR_TEX, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (g && d) launch_raster<ATTR_GOURAUD, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (g) launch_raster<ATTR_GOURAUD, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (d) launch_raster<ATTR_FLAT, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else launch_raster<ATTR_FLAT, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
 }
 
 }  // namespace
@@ -558,13 +587,13 @@ void launch_ordered_binned(const FrameParams& fp, const u32* list, const u32* of
     else launch_raster_c<false, true>(fp, list, off, nullptr, ntiles, s, rec, plan, start, stop);
 }
 
-void draw_ordered(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned) {
+void draw_ordered(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, const TexView* tex) {
     const i64 ntiles = (i64)((ctx->width + TW - 1) / TW) * ((ctx->height + TH - 1) / TH);
     if (ntiles <= ORD_BIN_TILES) {
-        draw_free(ctx, src, tb, callerOwned, true);
+        draw_free(ctx, src, tb, callerOwned, true, tex);
         return;
     }
-    FrameParams fp = frame_params(ctx, src);
+    FrameParams fp = frame_params(ctx, src, tex);
     BinParams bp;
     bp.src = src;
     for (int k = 0; k < 6; ++k) bp.m[k] = ctx->m[k];
@@ -624,7 +653,7 @@ void ordered_sorted_kernels(RenderContext* ctx, const TriSrc& src, const FramePa
         b.n = src.n - a.n;
         b.xy = src.xy + a.n * 6;
         b.z = src.z ? src.z + a.n * 3 : nullptr;
-        b.rgba = src.rgba + a.n * (src.gouraud ? 12 : 4);
+        b.attr = src.attr + a.n * attr_stride(src.mode);
         BinParams ba = bp, bb = bp;
         ba.src = a; bb.src = b;
         FrameParams fa = fp, fb = fp;

@@ -27,10 +27,12 @@
 namespace nrtri {
 
 // Doubles of a shading record (build_record): Gouraud sx0 sy0 e1x e1y e2x e2y
-// inv | c0 rgb | (c1-c0) rgb | (c2-c0) rgb; flat rgb.
-template <bool GOURAUD>
+// inv | c0 rgb | (c1-c0) rgb | (c2-c0) rgb; flat rgb; textured the same 7
+// geometry terms | u0 v0 | (u1-u0) (v1-v0) | (u2-u0) (v2-v0): 13 doubles in
+// the Gouraud record's 16-double slot.  MODE: AttrMode.
+template <int MODE>
 struct RecLen {
-    static constexpr int REC = GOURAUD ? 16 : 3;
+    static constexpr int REC = MODE != ATTR_FLAT ? 16 : 3;
 };
 
 // Depth of a shaded pixel (winner kv; (u32)kv == 0: no fragment won it):
@@ -83,28 +85,43 @@ __device__ __forceinline__ void store_clear(const FrameParams& fp, i64 p, i64 px
 // A winner's source data for its shading record: vertices and the rgb of
 // each vertex (alpha is not needed, see ShadeStage), loaded as 16 + 8 bytes
 // per vertex colour.
-template <bool GOURAUD>
+template <int MODE>
 struct RecordSrc {
-    f64 p[GOURAUD ? 6 : 1];
-    f64 c[GOURAUD ? 9 : 3];
+    f64 p[MODE != ATTR_FLAT ? 6 : 1];
+    f64 c[MODE == ATTR_GOURAUD ? 9 : (MODE == ATTR_TEX ? 6 : 3)];   // textured: the six uv
 };
 
-template <bool GOURAUD>
-__device__ __forceinline__ void load_record_src(const FrameParams& fp, i64 t, RecordSrc<GOURAUD>& s) {
-    if constexpr (GOURAUD) load_tri_xy(fp.src.xy, t, s.p);
+template <int MODE>
+__device__ __forceinline__ void load_record_src(const FrameParams& fp, i64 t, RecordSrc<MODE>& s) {
+    constexpr bool GOURAUD = MODE == ATTR_GOURAUD;
+    if constexpr (MODE != ATTR_FLAT) load_tri_xy(fp.src.xy, t, s.p);
+    if constexpr (MODE == ATTR_TEX) {
+        load_tri_xy(fp.src.uv(), t, s.c);   // (the same 3 x 16-byte layout)
+        return;
+    }
     const int nv = GOURAUD ? 3 : 1, stride = GOURAUD ? 12 : 4;
 #pragma unroll
     for (int v = 0; v < nv; ++v) {
-        const f64* q = fp.src.rgba + t * stride + 4 * v;
+        const f64* q = fp.src.rgba() + t * stride + 4 * v;
         const double2 rg = *reinterpret_cast<const double2*>(q);
         s.c[3 * v] = rg.x; s.c[3 * v + 1] = rg.y; s.c[3 * v + 2] = q[2];
     }
 }
 
 // Shading record from its source (the expressions of the per-pixel path, once).
-template <bool GOURAUD>
-__device__ __forceinline__ void build_record(const FrameParams& fp, const RecordSrc<GOURAUD>& s, f64* r) {
-    if constexpr (GOURAUD) {
+template <int MODE>
+__device__ __forceinline__ void build_record(const FrameParams& fp, const RecordSrc<MODE>& s, f64* r) {
+    if constexpr (MODE == ATTR_TEX) {
+        f64 sx[3], sy[3];
+#pragma unroll
+        for (int v = 0; v < 3; ++v) nr_xform(fp.m, s.p[2 * v], s.p[2 * v + 1], sx[v], sy[v]);
+        const f64 e1x = sx[1] - sx[0], e1y = sy[1] - sy[0], e2x = sx[2] - sx[0], e2y = sy[2] - sy[0];
+        r[0] = sx[0]; r[1] = sy[0]; r[2] = e1x; r[3] = e1y; r[4] = e2x; r[5] = e2y;
+        r[6] = 1.0 / (e1x * e2y - e2x * e1y);
+        r[7] = s.c[0]; r[8] = s.c[1];
+        r[9] = s.c[2] - s.c[0]; r[10] = s.c[3] - s.c[1];
+        r[11] = s.c[4] - s.c[0]; r[12] = s.c[5] - s.c[1];
+    } else if constexpr (MODE == ATTR_GOURAUD) {
         f64 sx[3], sy[3];
 #pragma unroll
         for (int v = 0; v < 3; ++v) nr_xform(fp.m, s.p[2 * v], s.p[2 * v + 1], sx[v], sy[v]);
@@ -123,17 +140,34 @@ __device__ __forceinline__ void build_record(const FrameParams& fp, const Record
 }
 
 // Shading record of triangle t.
-template <bool GOURAUD>
+template <int MODE>
 __device__ __forceinline__ void make_record(const FrameParams& fp, i64 t, f64* r) {
-    RecordSrc<GOURAUD> s;
-    load_record_src<GOURAUD>(fp, t, s);
-    build_record<GOURAUD>(fp, s, r);
+    RecordSrc<MODE> s;
+    load_record_src<MODE>(fp, t, s);
+    build_record<MODE>(fp, s, r);
 }
 
-// Colour of pixel (px, py) from a record.
-template <bool GOURAUD>
-__device__ __forceinline__ void record_colour(const f64* r, i64 px, i64 py, f64& cr, f64& cg, f64& cb, f64& ca) {
-    if (GOURAUD) {
+// Texel (tex_index) of pixel (px, py) from a textured record: u and v by the
+// expression of a Gouraud channel.
+__device__ __forceinline__ i64 record_texel(const TexView& tv, const f64* r, i64 px, i64 py) {
+    const f64 dx = (f64)px - r[0], dy = (f64)py - r[1];
+    const f64 w1 = (dx * r[5] - r[4] * dy) * r[6];
+    const f64 w2 = (r[2] * dy - dx * r[3]) * r[6];
+    const f64 u = r[7] + r[9] * w1 + r[11] * w2;
+    const f64 v = r[8] + r[10] * w1 + r[12] * w2;
+    return tex_index(tv, u, v);
+}
+
+// Colour of pixel (px, py) from a record.  (Textured: the texel's rgb from
+// the view tv, an ordinary cached load; alpha is 1 -- only textures without
+// alpha are routed to the order-free raster.)
+template <int MODE>
+__device__ __forceinline__ void record_colour(const TexView& tv, const f64* r, i64 px, i64 py, f64& cr, f64& cg,
+                                              f64& cb, f64& ca) {
+    if constexpr (MODE == ATTR_TEX) {
+        const f64* q = tv.ptr + record_texel(tv, r, px, py);
+        cr = q[0]; cg = q[1]; cb = q[2]; ca = 1.0;
+    } else if (MODE == ATTR_GOURAUD) {
         const f64 dx = (f64)px - r[0], dy = (f64)py - r[1];
         const f64 w1 = (dx * r[5] - r[4] * dy) * r[6];
         const f64 w2 = (r[2] * dy - dx * r[3]) * r[6];

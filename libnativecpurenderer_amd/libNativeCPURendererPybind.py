@@ -284,8 +284,42 @@ class RenderContext:
             return a.data_ptr() if hasattr(a, "data_ptr") else int(a)
         lib.DrawTrianglesDevice(self._ptr, addr(xy), addr(z), addr(rgba), int(n), bool(gouraud))
 
-    def draw_triangle_buffer(self, buf: "TriangleBuffer"):
-        lib.DrawTriangleBuffer(self._ptr, buf._ptr)
+    def draw_triangle_buffer(self, buf: "TriangleBuffer", texture: typing.Optional["Texture"] = None):
+        """Draws a TriangleBuffer: a colour buffer as it is, a textured one
+        (TriangleBuffer(xy, uv=...)) from `texture`, chosen per draw."""
+        if buf.textured:
+            if texture is None:
+                raise ValueError("a textured TriangleBuffer is drawn with a texture")
+            lib.DrawTexturedTriangleBuffer(self._ptr, buf._ptr, texture._ptr)
+        else:
+            if texture is not None:
+                raise ValueError("a colour TriangleBuffer takes no texture")
+            lib.DrawTriangleBuffer(self._ptr, buf._ptr)
+
+    def draw_textured_triangles(self, tex: "Texture", xy, uv, z=None):
+        """Draws n textured triangles in the current transform.
+
+        xy: (n, 3, 2) or (n, 6) vertex positions; uv: (n, 3, 2) or (n, 6)
+        per-vertex texture coordinates in texels of `tex` (interpolated like a
+        Gouraud channel, sampled with draw_texture's nearest sampler, tinted
+        by the colour transform); z: (n, 3) depths in [0, 1] or None."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 6)
+        n = xy.shape[0]
+        uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(n, 6)
+        zp = None
+        if z is not None:
+            z = np.ascontiguousarray(z, dtype=np.float64).reshape(n, 3)
+            zp = _f64_ptr(z)
+        lib.DrawTexturedTriangles(self._ptr, tex._ptr, _f64_ptr(xy), zp, _f64_ptr(uv), n)
+
+    def draw_textured_triangles_device(self, tex: "Texture", xy, uv, n: int, z=None):
+        """DrawTexturedTrianglesDevice: xy / uv / z are device addresses or
+        objects with .data_ptr(), as for draw_triangles_device."""
+        def addr(a):
+            if a is None:
+                return None
+            return a.data_ptr() if hasattr(a, "data_ptr") else int(a)
+        lib.DrawTexturedTrianglesDevice(self._ptr, tex._ptr, addr(xy), addr(z), addr(uv), int(n))
 
     # ---- additions: sync, device interop, measurement ------------------
     def flush(self):
@@ -776,9 +810,28 @@ class PtrCreatedTexture(Texture):
 class TriangleBuffer:
     """Device-resident triangle soup (new): uploaded once, drawn per frame."""
 
-    def __init__(self, xy, rgba, z=None, gouraud: typing.Optional[bool] = None):
+    def __init__(self, xy, rgba=None, z=None, gouraud: typing.Optional[bool] = None, uv=None):
+        """Exactly one of rgba (a colour buffer) and uv (a textured buffer:
+        (n, 3, 2) or (n, 6) texel coordinates; the texture is chosen per draw,
+        RenderContext.draw_triangle_buffer(buf, texture))."""
+        if (rgba is None) == (uv is None):
+            raise ValueError("exactly one of rgba and uv")
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 6)
         n = xy.shape[0]
+        self.textured = uv is not None
+        if self.textured:
+            uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(n, 6)
+            zp = None
+            if z is not None:
+                z = np.ascontiguousarray(z, dtype=np.float64).reshape(n, 3)
+                zp = _f64_ptr(z)
+            self.n = n
+            self.gouraud = False
+            self._can_release = False
+            self._ptr = _check(lib.CreateTexturedTriangleBuffer(n, _f64_ptr(xy), zp, _f64_ptr(uv)),
+                               "CreateTexturedTriangleBuffer")
+            self._can_release = True
+            return
         rgba = np.ascontiguousarray(rgba, dtype=np.float64)
         if gouraud is None:
             gouraud = rgba.size == 12 * n and n > 0
