@@ -156,6 +156,26 @@ TriangleBuffer* CreateTexturedTriangleBuffer(i64 n, const f64* xy, const f64* z,
                                              const f64* uv);              /* NEW: one H2D upload; no texture bound */
 void DrawTexturedTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb, Texture* tex);   /* NEW: texture chosen per
                                  draw; a colour buffer here, or a textured one in DrawTriangleBuffer, latches an error */
+/* NEW: indexed 3D meshes (DESIGN §3 "Vertex stage").  nv vertices pos (px, py, pz), n triangles as u32 index
+   triples, one per-vertex attribute: RGBA nv*4 (flat = the colour of a triangle's first index, or Gouraud) or
+   texel-unit UVs nv*2.  Uploaded once; each draw transforms the vertices on the device by a row-major 4x4
+   matrix16 with the viewport baked in (NULL = identity): c = M * (px, py, pz, 1), a vertex with cw <= 0 becomes
+   NaN (its triangles are dropped; no near-plane clipping), otherwise (x, y, z) = (cx, cy, cz) / cw.  The assembled
+   soup is then drawn like DrawTrianglesDevice's: the context's 2D transform, depth state and colour transform
+   apply, attributes stay affine in screen space.  Creation returns NULL and latches an error for an index >= nv,
+   a NULL attribute array with n > 0, or nv beyond 32 bits; n == 0 is a valid mesh that draws nothing.  A mesh on
+   another device than the context's, or the wrong draw call for its kind, latches an error and draws nothing. */
+typedef struct Mesh Mesh;
+Mesh* CreateMesh(i64 nv, const f64* pos, i64 n, const uint32_t* idx, const f64* rgba, bool gouraud);   /* NEW */
+Mesh* CreateTexturedMesh(i64 nv, const f64* pos, i64 n, const uint32_t* idx, const f64* uv);           /* NEW */
+void DestroyMesh(Mesh* m);                                               /* NEW */
+i64 GetMeshVertexCount(Mesh* m);                                         /* NEW */
+i64 GetMeshTriangleCount(Mesh* m);                                       /* NEW */
+bool UpdateMeshPositions(Mesh* m, const f64* pos);                       /* NEW: deforming meshes, H2D of nv*3 positions only */
+void DrawMesh(RenderContext* ctx, Mesh* m, const f64* matrix16);         /* NEW: a colour mesh */
+void DrawTexturedMesh(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrix16);   /* NEW: texture chosen per draw */
+bool AssembleMesh(RenderContext* ctx, Mesh* m, const f64* matrix16, f64* xy_out, f64* z_out);   /* NEW: DrawMesh's
+                                 vertex stage and assembly alone, the soup (xy n*6, z n*3) copied to the host; a sync point */
 void SetFragmentCounting(RenderContext* ctx, bool on);                   /* NEW: covered-fragment counter */
 i64 GetFragmentCount(RenderContext* ctx);                                /* NEW */
 i64 GetLastRasterPath(RenderContext* ctx);                               /* NEW: 1 order-free tiled, 2 ordered, 3 order-free frame */

@@ -80,6 +80,15 @@ DEVICE_ABI = {
     "DrawTexturedTrianglesDevice": (None, (P, P, P, P, P, L)),
     "CreateTexturedTriangleBuffer": (P, (L, P, P, P)),
     "DrawTexturedTriangleBuffer": (None, (P, P, P)),
+    "CreateMesh": (P, (L, P, L, P, P, B)),
+    "CreateTexturedMesh": (P, (L, P, L, P, P)),
+    "DestroyMesh": (None, (P,)),
+    "GetMeshVertexCount": (L, (P,)),
+    "GetMeshTriangleCount": (L, (P,)),
+    "UpdateMeshPositions": (B, (P, P)),
+    "DrawMesh": (None, (P, P, P)),
+    "DrawTexturedMesh": (None, (P, P, P, P)),
+    "AssembleMesh": (B, (P, P, P, P, P)),
     "SetFragmentCounting": (None, (P, B)),
     "GetFragmentCount": (L, (P,)),
     "GetLastRasterPath": (L, (P,)),

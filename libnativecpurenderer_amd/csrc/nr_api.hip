@@ -327,7 +327,8 @@ u64* nr_timing_stamp(RenderContext* ctx, int kid) {
 
 static const char* kKernelNames[NRK_COUNT_] = {"tri_count", "tri_scan",    "tri_emit", "tri_sort",
                                                "tile_ranges", "tile_raster", "prim",     "fill",
-                                               "resolve",   "vis_init",    "output",   "gather"};
+                                               "resolve",   "vis_init",    "output",   "gather",
+                                               "mesh_vertex", "mesh_assemble"};
 
 extern "C" {
 
@@ -384,7 +385,7 @@ void DestroyRenderContext(RenderContext* ctx) {
     TriScratch& t = ctx->tri;
     void* ptrs[] = {ctx->buffer, ctx->depth, t.cnt,  t.off,        t.keys[0], t.keys[1], t.vals[0],
                     t.vals[1],   t.tile_start, t.tile_end, t.temp, t.stage, t.d_frag, t.d_flag, ctx->u8buf,
-                    t.fdone,     t.kslot, t.orec, ctx->tileStamp};
+                    t.fdone,     t.kslot, t.orec, ctx->tileStamp, t.mstage};
     for (void* p : ptrs)
         if (p) NR_CHECK(hipFree(p));
     for (auto& F : t.fset) {
@@ -806,7 +807,8 @@ void EnableKernelTiming(RenderContext* ctx, bool on) {
 }
 
 // Sum and count of the named kernel's durations since the last reset
-// (names: tri_count tri_scan tri_emit tri_sort tile_ranges tile_raster prim fill resolve vis_init).
+// (names: tri_count tri_scan tri_emit tri_sort tile_ranges tile_raster prim fill resolve vis_init output gather
+// mesh_vertex mesh_assemble).
 bool GetKernelTiming(RenderContext* ctx, const char* name, f64* total_ms, i64* count) {
     NR_CHECK(hipSetDevice(ctx->device));
     timing_collect(ctx);

@@ -89,6 +89,9 @@ struct TriScratch {
     int coopMode = 0;                       // k_vis variant: 0 auto, 1 coop, 2 lane-only (SetCoopRaster)
     u32 splitAt = 0, dslice = 0;            // dense-tile split limits (SetSplitLimits; 0: NR_SPLIT_AT / NR_DSLICE)
     f64* stage = nullptr; size_t stage_cap = 0;   // DrawTriangles() with host arrays
+    // DrawMesh (nr_mesh.hip): the draw's transformed vertices and assembled soup -- (x, y) nv*2, z nv (padded
+    // to an even count), xy n*6, z n*3; read by the batch until it is settled, like `stage`
+    f64* mstage = nullptr; size_t mstage_cap = 0;
     // warm binning (nr_tri_free.hip): the tile offsets, k_vis work items and
     // plan totals of the last validated binning of one TriangleBuffer under
     // one binning key -- a later draw of the same buffer under the same key
@@ -142,7 +145,7 @@ struct TriScratch {
 
 enum NRKernelId { NRK_TRI_COUNT = 0, NRK_TRI_SCAN, NRK_TRI_EMIT, NRK_TRI_SORT, NRK_TILE_RANGES,
                   NRK_TILE_RASTER, NRK_PRIM, NRK_FILL, NRK_RESOLVE, NRK_VIS_INIT, NRK_OUTPUT, NRK_GATHER,
-                  NRK_COUNT_ };
+                  NRK_MESH_VERTEX, NRK_MESH_ASSEMBLE, NRK_COUNT_ };
 
 struct RenderContext {
     i64 width = 0, height = 0;

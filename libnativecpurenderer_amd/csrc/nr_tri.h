@@ -549,4 +549,13 @@ void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool c
                const TexView* tex = nullptr);
 void settle(RenderContext* ctx);
 
+// the batch entry points behind every triangle draw call (nr_tri.hip), shared with the mesh front end
+// (nr_mesh.hip): draw picks the raster; draw_textured resolves the texture first (check_texture: its
+// preconditions, an error latched under the caller's name `what` when one fails)
+void draw(RenderContext* ctx, const f64* xy, const f64* z, const f64* attr, i64 n, int mode, Opacity opq,
+          TriangleBuffer* tb = nullptr, bool callerOwned = false, const TexView* tex = nullptr);
+bool check_texture(RenderContext* ctx, const Texture* tex, const char* what);
+void draw_textured(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv, i64 n,
+                   TriangleBuffer* tb, bool callerOwned);
+
 }  // namespace nrtri

@@ -186,10 +186,12 @@ Opacity device_opacity(RenderContext* ctx, const TriSrc& src) {
     return *h ? OPQ_BLENDED : OPQ_OPAQUE;
 }
 
+}  // namespace
+
 // attr: the batch's colours (mode ATTR_FLAT / ATTR_GOURAUD) or its texture
 // coordinates (ATTR_TEX, sampled from *tex).
 void draw(RenderContext* ctx, const f64* xy, const f64* z, const f64* attr, i64 n, int mode, Opacity opq,
-          TriangleBuffer* tb = nullptr, bool callerOwned = false, const TexView* tex = nullptr) {
+          TriangleBuffer* tb, bool callerOwned, const TexView* tex) {
     NR_CHECK(hipSetDevice(ctx->device));
     settle(ctx);
     if (n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
@@ -231,7 +233,6 @@ void draw_textured(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z
     }
 }
 
-}  // namespace
 }  // namespace nrtri
 
 using namespace nrtri;

@@ -321,6 +321,39 @@ class RenderContext:
             return a.data_ptr() if hasattr(a, "data_ptr") else int(a)
         lib.DrawTexturedTrianglesDevice(self._ptr, tex._ptr, addr(xy), addr(z), addr(uv), int(n))
 
+    @staticmethod
+    def _matrix16(matrix):
+        if matrix is None:
+            return None, None
+        m = np.ascontiguousarray(matrix, dtype=np.float64).reshape(16)
+        return m, _f64_ptr(m)
+
+    def draw_mesh(self, mesh: "Mesh", matrix=None, texture: typing.Optional["Texture"] = None):
+        """Draws a Mesh under the row-major 4x4 `matrix` (None: the identity;
+        the viewport is baked into it), transformed on the device; then the
+        context's transform, depth state and colour transform as for
+        draw_triangles.  A textured mesh (Mesh(..., uv=...)) takes `texture`."""
+        m, mp = self._matrix16(matrix)
+        if mesh.textured:
+            if texture is None:
+                raise ValueError("a textured Mesh is drawn with a texture")
+            lib.DrawTexturedMesh(self._ptr, mesh._ptr, texture._ptr, mp)
+        else:
+            if texture is not None:
+                raise ValueError("a colour Mesh takes no texture")
+            lib.DrawMesh(self._ptr, mesh._ptr, mp)
+
+    def assemble_mesh(self, mesh: "Mesh", matrix=None):
+        """(xy (n, 6), z (n, 3)): the triangle soup draw_mesh would rasterise
+        under `matrix` -- its vertex stage and assembly alone (a sync point)."""
+        m, mp = self._matrix16(matrix)
+        n = mesh.triangle_count
+        xy = np.empty((n, 6), dtype=np.float64)
+        z = np.empty((n, 3), dtype=np.float64)
+        if not lib.AssembleMesh(self._ptr, mesh._ptr, mp, _f64_ptr(xy), _f64_ptr(z)):
+            raise RuntimeError("AssembleMesh failed: " + _lib.last_error())
+        return xy, z
+
     # ---- additions: sync, device interop, measurement ------------------
     def flush(self):
         lib.Flush(self._ptr)
@@ -852,6 +885,60 @@ class TriangleBuffer:
     def __del__(self):
         if getattr(self, "_can_release", False):
             lib.DestroyTriangleBuffer(self._ptr)
+            self._can_release = False
+
+
+class Mesh:
+    """Device-resident indexed mesh (new): vertices + indices uploaded once,
+    drawn per frame under a 4x4 matrix (RenderContext.draw_mesh)."""
+
+    def __init__(self, positions, indices, colors=None, uv=None, gouraud: typing.Optional[bool] = None):
+        """positions: (nv, 3); indices: (n, 3) integers < nv (stored as
+        uint32); exactly one of colors ((nv, 4) RGBA per vertex; gouraud
+        (default) interpolates them, flat takes each triangle's first index)
+        and uv ((nv, 2) texel coordinates: a textured mesh)."""
+        if (colors is None) == (uv is None):
+            raise ValueError("exactly one of colors and uv")
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        nv = pos.shape[0]
+        ind = np.asarray(indices)
+        if ind.size and (ind.min() < 0 or ind.max() > 0xFFFFFFFF):
+            raise ValueError("indices must fit uint32")
+        idx = np.ascontiguousarray(ind, dtype=np.uint32).reshape(-1, 3)
+        n = idx.shape[0]
+        self.textured = uv is not None
+        self._can_release = False
+        ip = idx.ctypes.data_as(ctypes.c_void_p)
+        if self.textured:
+            uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(nv, 2)
+            self.gouraud = False
+            self._ptr = _check(lib.CreateTexturedMesh(nv, _f64_ptr(pos), n, ip, _f64_ptr(uv)), "CreateTexturedMesh")
+        else:
+            colors = np.ascontiguousarray(colors, dtype=np.float64).reshape(nv, 4)
+            self.gouraud = True if gouraud is None else bool(gouraud)
+            self._ptr = _check(lib.CreateMesh(nv, _f64_ptr(pos), n, ip, _f64_ptr(colors), self.gouraud), "CreateMesh")
+        self._can_release = True
+
+    @property
+    def vertex_count(self) -> int:
+        return lib.GetMeshVertexCount(self._ptr)
+
+    @property
+    def triangle_count(self) -> int:
+        return lib.GetMeshTriangleCount(self._ptr)
+
+    def update_positions(self, positions):
+        """New positions (nv, 3) for the next draws (an upload of the
+        positions only); draws already issued keep the old ones."""
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        if pos.shape[0] != self.vertex_count:
+            raise ValueError("update_positions: the vertex count is fixed at creation")
+        if not lib.UpdateMeshPositions(self._ptr, _f64_ptr(pos)):
+            raise RuntimeError("UpdateMeshPositions failed: " + _lib.last_error())
+
+    def __del__(self):
+        if getattr(self, "_can_release", False):
+            lib.DestroyMesh(self._ptr)
             self._can_release = False
 
 
