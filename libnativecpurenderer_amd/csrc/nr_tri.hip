@@ -193,7 +193,7 @@ Opacity device_opacity(RenderContext* ctx, const TriSrc& src) {
 void draw(RenderContext* ctx, const f64* xy, const f64* z, const f64* attr, i64 n, int mode, Opacity opq,
           TriangleBuffer* tb, bool callerOwned, const TexView* tex) {
     NR_CHECK(hipSetDevice(ctx->device));
-    settle(ctx);
+    nr_settle(ctx);   // recorded draws come first (the colour entry points reach here with their list still queued)
     if (n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
     if (!ctx->depthTest) nr_materialize_depth(ctx);
     TriSrc src;

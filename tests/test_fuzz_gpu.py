@@ -16,7 +16,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
-hypothesis = pytest.importorskip("hypothesis")
+import hypothesis  # noqa: F401  (a missing package fails the module: the GPU tests never skip)
 from hypothesis import HealthCheck, given, settings, strategies as st  # noqa: E402
 
 import scenes  # noqa: E402

@@ -1,0 +1,207 @@
+"""Whole frames that mix every draw kind, on every raster path, against the
+CPU oracle bit for bit: f64 framebuffer, u32 depth, u8 readback, the frame
+output (u8 image / YUV420P planes) and every mid-frame probe.
+
+A frame is plain data of tests/frame_ops.py's vocabulary (colour soups from
+host arrays, TriangleBuffers and device arrays; textured soups; indexed meshes
+with update_positions; primitives, textures, pixels; snapshots of the frame
+and of an auxiliary context; state; probes; command recording; the frame
+output; the testing knobs of the rasters), run by its one interpreter on the
+library and on the oracle.  frame_ops.py states how the oracle, which has no
+textured draw, mesh, buffer or recording, runs each operation;
+tests/test_frame_ops.py checks the lowerings and that the generated frames
+are worth running, on exactly the examples drawn here.
+
+Two property tests draw the frames (hypothesis, derandomized); the fixed
+sequences below them are the hand-offs between kinds named one by one, in the
+same data, so that a failing fuzz frame (printed with its knobs) can be added
+as one more entry of FIXED.
+
+Running time, measured with --durations on one MI355X (call phase, two runs):
+    tests/test_fuzz_gpu.py::test_random_frames_match_oracle         1.74 s, 1.62 s (400 examples)
+    tests/test_fuzz_gpu.py::test_random_large_frames_match_oracle   1.03 s, 1.01 s (40 examples)
+    test_random_mixed_frames_match_oracle                           0.83 s (200 examples)
+    test_random_mixed_large_frames_match_oracle                     0.62 s (50 examples)
+The example counts (frame_ops.SMALL_EXAMPLES = 200, LARGE_EXAMPLES = 50) are above the floor of 150 small and 20
+large frames and keep each test shorter than its old counterpart; each fixed sequence takes about 10 ms.
+"""
+import hypothesis  # noqa: F401  (a missing package fails the module: these tests never skip)
+import pytest
+
+import frame_ops as F
+
+pytestmark = pytest.mark.gpu
+
+W, H = 200, 140            # 4 x 5 tiles, partial right and bottom tiles
+IDENT = (1.0, 0.0, 0.0, 1.0, 0.0, 0.0)
+
+
+class Reached:
+    """What the frames of one property test reached on the GPU."""
+
+    def __init__(self):
+        self.paths = set()          # (triangle kind, raster path)
+        self.warm = 0
+        self.over_cap = 0           # frames under set_pair_capacity_override(50) with a batch of more pairs
+        self.frames = 0
+
+    def note(self, frame, got):
+        self.frames += 1
+        self.paths |= {(kind, path) for kind, path, _ in got["batches"]}
+        self.warm += got["warm"] > 0
+        self.over_cap += frame[3]["paircap"] == 50 and any(pairs > 50 for _, _, pairs in got["batches"])
+
+    def check(self):
+        want = {(k, p) for k in ("colour", "textured", "mesh") for p in ("order-free", "ordered")}
+        assert want <= self.paths, f"never reached: {sorted(want - self.paths)}"
+        assert self.warm > 0, "no frame with a warm batch"
+        assert self.over_cap > 0, "no frame overflowed the pair capacity of 50"
+
+
+def _compare(gpu, oracle, frame, reached=None):
+    got = F.run(gpu, frame)
+    want = F.run(oracle, frame)
+    bad = F.mismatches(got, want)
+    if bad:
+        print("mismatching frame:", repr(frame))
+    assert not bad, (bad, frame)
+    assert [b[0] for b in got["batches"]] == [b[0] for b in want["batches"]]
+    if reached is not None:
+        reached.note(frame, got)
+    return got
+
+
+def test_random_mixed_frames_match_oracle(gpu, oracle):
+    reached = Reached()
+    F.for_each_frame("small", lambda fr: _compare(gpu, oracle, fr, reached))
+    assert reached.frames >= 150
+    reached.check()
+
+
+def test_random_mixed_large_frames_match_oracle(gpu, oracle):
+    reached = Reached()
+    F.for_each_frame("large", lambda fr: _compare(gpu, oracle, fr, reached))
+    assert reached.frames >= 20
+    reached.check()
+
+
+# ---- fixed sequences -----------------------------------------------------------
+def _knobs(**kw):
+    return dict(F.KNOBS_OFF, **kw)
+
+
+RGB_TEX = (37, 23, 3, "f64", 5, None)
+RGBA_TEX = (16, 9, 4, "u8", 6, None)
+GOURAUD_MESH = ("c", "model", 8, 12, 3, True, False)
+TWO_TILES = (0.3, 0.0, 0.0, 0.2, 5.0, 3.0)     # the frame onto its top-left 60 x 28 pixels
+BG = ("clear", [0.3, 0.6, 0.9, 2.7])           # set_color(0.1, 0.2, 0.3, 0.9): non-uniform, alpha on RGB
+
+
+def _kinds_in_one_depth_buffer(test, write):
+    return (_knobs(), dict(texs=[RGB_TEX, RGBA_TEX], bufs=[], meshes=[GOURAUD_MESH]),
+            [("depthstate", test, write),
+             ("tri", "host", 150, 11, 40.0, False, False), ("ttri", "host", 150, 12, 40.0, "const", ("res", 0)),
+             ("tri", "host", 100, 13, 40.0, True, True), ("ttri", "host", 100, 14, 40.0, "const", ("res", 1)),
+             ("mesh", 0, 1, ("res", 0))])
+
+
+def _overflow_then_clears(first, fmt):
+    res = dict(texs=[RGB_TEX], bufs=[], meshes=[("c", "screen", 10, 10, 4, True, False)])
+    return (_knobs(paircap=50, fmt=fmt), res,
+            [first, ("cleardepth", 0xFFFFFFFF), BG, ("rect", [0.9, 0.2, 0.1, 0.5], [10.0, 10.0, 120.0, 90.0]),
+             ("tri", "host", 60, 22, 6.0, True, False)])
+
+
+def _fast_clear(batch1, batch2):
+    res = dict(texs=[RGB_TEX, (9, 13, 4, "u8", 8, None)], bufs=[], meshes=[("c", "screen", 6, 8, 5, True, False)])
+    return (_knobs(), res,
+            [BG, ("cleardepth", 0xFFFFFFF0), ("transform", TWO_TILES), batch1, ("transform", IDENT),
+             ("tex", ("res", 1), [-5.0, -4.0, 210.0, 150.0]), ("getcolor", 190.0, 130.0),
+             ("transform", TWO_TILES), batch2, ("readdepth",)])
+
+
+_TEXTURED = ("ttri", "host", 300, 21, 40.0, "const", ("res", 0))
+_TEXTURED_SMALL = ("ttri", "host", 80, 23, 6.0, "const", ("res", 0))
+_MESH = ("mesh", 0, 0, ("res", 0))
+
+FIXED = {
+    "kinds_in_one_depth_buffer_test_write": _kinds_in_one_depth_buffer(True, True),
+    "kinds_in_one_depth_buffer_test_only": _kinds_in_one_depth_buffer(True, False),
+    "kinds_in_one_depth_buffer_depth_off": _kinds_in_one_depth_buffer(False, False),
+    "six_buffer_batches_rotate_the_binning_sets": (
+        _knobs(paircap=50), dict(texs=[RGB_TEX], bufs=[("c", 120, 31, 40.0, True, False), ("t", 120, 32, 40.0, "const")],
+                                 meshes=[]),
+        [("buf", 0, ("res", 0)), ("translate", [0.7, 0.3, 0.0, 0.0]), ("buf", 1, ("res", 0)),
+         ("translate", [-0.7, -0.3, 0.0, 0.0]), ("buf", 0, ("res", 0)), ("translate", [0.7, 0.3, 0.0, 0.0]),
+         ("buf", 1, ("res", 0)), ("translate", [-0.7, -0.3, 0.0, 0.0]), ("buf", 0, ("res", 0)),
+         ("translate", [0.7, 0.3, 0.0, 0.0]), ("buf", 1, ("res", 0))]),
+    "overflowing_textured_batch_then_clears": _overflow_then_clears(_TEXTURED, None),
+    "overflowing_mesh_then_clears": _overflow_then_clears(_MESH, None),
+    "overflowing_textured_batch_then_clears_frame_output": _overflow_then_clears(_TEXTURED, "rgb"),
+    "overflowing_mesh_then_clears_frame_output": _overflow_then_clears(_MESH, "yuv420p"),
+    # the state a later re-run must not pick up: colour transform and depth state changed while the batch is pending
+    "rerun_keeps_the_colour_transform_and_depth_state_of_its_batch": (
+        _knobs(paircap=50), dict(texs=[RGB_TEX], bufs=[], meshes=[("c", "screen", 10, 10, 4, True, False)]),
+        [_TEXTURED, ("ct", [1.5, 2.4, 0.9, 3.0]), ("depthstate", False, False),
+         ("rect", [0.9, 0.2, 0.1, 0.5], [10.0, 10.0, 120.0, 90.0]), ("ct", [2.7, 1.2, 2.1, 3.0]), ("depthstate", True, True),
+         _MESH, ("ct", [0.6, 0.6, 2.4, 3.0]), ("depthstate", True, False), ("tri", "host", 200, 25, 40.0, True, False),
+         ("ct", [3.0, 3.0, 3.0, 1.5]), ("readdepth",)]),
+    "fast_clear_textured_batches_in_two_tiles": _fast_clear(_TEXTURED_SMALL, ("ttri", "host", 80, 24, 6.0, "const", ("res", 0))),
+    "fast_clear_meshes_in_two_tiles": _fast_clear(_MESH, ("mesh", 0, 1, ("res", 0))),
+    "recorded_primitives_between_batches": (
+        _knobs(), dict(texs=[RGB_TEX, RGBA_TEX], bufs=[], meshes=[GOURAUD_MESH]),
+        [("begin",), ("rect", [0.9, 0.2, 0.1, 0.5], [10.0, 10.0, 120.0, 90.0]), ("tex", ("res", 1), [30.0, 20.0, 100.0, 80.0]),
+         ("ttri", "host", 120, 41, 40.0, "const", ("res", 0)), ("circle", [0.1, 0.8, 0.3, 0.6], [120.0, 70.0, 45.0, 0.0]),
+         ("mesh", 0, 1, ("res", 0)), ("stex", ("res", 1), [60.0, 30.0, 90.0, 70.0], [0.2, 0.7, 0.1, 0.9]), ("flush",),
+         ("tri", "host", 120, 42, 40.0, True, False), ("end",)]),
+    # found by the fuzz: the colour entry points left the recorded list queued, so it ran after their batch
+    "recorded_fill_before_colour_batches": (
+        _knobs(record=True), dict(texs=[], bufs=[("c", 60, 44, 40.0, True, False)], meshes=[]),
+        [("fill", [0.66, 0.12, 0.95, 0.4]), ("tri", "host", 60, 43, 40.0, True, False),
+         ("rect", [0.9, 0.2, 0.1, 0.5], [10.0, 10.0, 120.0, 90.0]), ("tri", "dev", 60, 45, 40.0, False, False),
+         ("circle", [0.1, 0.8, 0.3, 0.6], [120.0, 70.0, 45.0, 0.0]), ("buf", 0, ("tiny", 1, 3)),
+         ("fill", [0.2, 0.9, 0.4, 0.3]), ("tri", "dev8", 60, 46, 40.0, True, True)]),
+    "shared_frame_texture_survives_the_rerun": (
+        _knobs(paircap=50), dict(texs=[RGB_TEX], bufs=[], meshes=[]),
+        [("grd", [0.9, 0.1, 0.4, 1.0], [0.0, 0.0, 200.0, 140.0]), ("tri", "host", 40, 51, 40.0, True, False),
+         ("ttri", "host", 300, 52, 40.0, "const", ("snap", "main", True)), ("begin",),
+         ("tex", ("snap", "main", True), [20.0, 10.0, 90.0, 60.0]), ("end",)]),
+    "texture_shared_from_a_recording_context": (
+        _knobs(record=True), dict(texs=[], bufs=[], meshes=[]),
+        [("aux", "rect", [0.9, 0.2, 0.1, 1.0], [3.0, 2.0, 10.0, 8.0]), ("snap", "aux", True),
+         ("aux", "clear", [0.2, 0.7, 0.4, 1.0], [0.0, 0.0, 0.0, 0.0]),
+         ("aux", "circle", [0.1, 0.3, 0.9, 0.8], [12.0, 9.0, 7.0, 0.0]), ("aux", "rect", [0.9, 0.9, 0.1, 0.5], [1.0, 1.0, 5.0, 20.0]),
+         ("ttri", "host", 150, 61, 40.0, "const", ("snap", "aux", True))]),
+    "moved_mesh_warm_buffer_resize": (
+        _knobs(), dict(texs=[RGB_TEX], bufs=[("c", 120, 71, 40.0, True, False)], meshes=[GOURAUD_MESH]),
+        [("mesh2", 0, 1, ("res", 0), 72), ("buf2", 0, ("res", 0), 0.0), ("resize", 150, 100),
+         ("mesh", 0, 1, ("res", 0)), ("buf", 0, ("res", 0))]),
+}
+
+
+def _expect(name, frame, got):
+    """The sequence took the road it is named after."""
+    paths = [p for _, p, _ in got["batches"]]
+    pairs = [n for _, _, n in got["batches"]]
+    if name.startswith("six_buffer"):
+        assert paths == ["order-free"] * 6 and min(pairs) > 50
+    if name.startswith("overflowing") or name.startswith("shared_frame") or name.startswith("rerun_keeps"):
+        assert max(pairs) > 50 and "order-free" in paths
+    if name.startswith("kinds_in_one"):
+        assert paths == ["order-free", "order-free", "ordered", "ordered", "order-free"]
+    if name.startswith("moved_mesh"):
+        assert got["warm"] > 0 and len(paths) == 6
+    if name.startswith("fast_clear"):
+        assert paths == ["order-free"] * 2      # and both batches stay inside the top-left tiles
+        assert (got["depth"][40:] == 0xFFFFFFF0).all() and (got["depth"][:, 140:] == 0xFFFFFFF0).all()
+        assert (got["depth"][:32, :64] != 0xFFFFFFF0).any()
+    if name.startswith("texture_shared"):
+        assert paths == ["order-free"] if not frame[2] else paths == ["ordered"]
+
+
+@pytest.mark.parametrize("alpha", [False, True], ids=["rgb", "rgba"])
+@pytest.mark.parametrize("name", list(FIXED))
+def test_fixed_sequence(gpu, oracle, name, alpha):
+    knobs, res, ops = FIXED[name]
+    frame = (W, H, alpha, knobs, res, ops)
+    _expect(name, frame, _compare(gpu, oracle, frame))
