@@ -382,29 +382,9 @@ void DestroyRenderContext(RenderContext* ctx) {
     NR_CHECK(hipStreamSynchronize(ctx->stream));
     NR_CHECK(hipStreamSynchronize(nr_bin_stream_for(ctx->device)));
     nr_dist_release(ctx);
-    TriScratch& t = ctx->tri;
-    void* ptrs[] = {ctx->buffer, ctx->depth, t.cnt,  t.off,        t.keys[0], t.keys[1], t.vals[0],
-                    t.vals[1],   t.tile_start, t.tile_end, t.temp, t.stage, t.d_frag, t.d_flag, ctx->u8buf,
-                    t.fdone,     t.kslot, t.orec, ctx->tileStamp, t.mstage};
-    for (void* p : ptrs)
+    for (void* p : {(void*)ctx->buffer, (void*)ctx->depth, (void*)ctx->u8buf, (void*)ctx->tileStamp})
         if (p) NR_CHECK(hipFree(p));
-    for (auto& F : t.fset) {
-        void* fp[] = {F.fcnt, F.foff, F.fcur, F.fitems, F.frect, F.frec, F.flist, F.dplan, F.gate, F.gplan};
-        for (void* p : fp)
-            if (p) NR_CHECK(hipFree(p));
-        if (F.h_plan) NR_CHECK(hipHostFree(F.h_plan));
-        if (F.evBin) NR_CHECK(hipEventDestroy(F.evBin));
-        if (F.evVis) NR_CHECK(hipEventDestroy(F.evVis));
-    }
-    if (t.h_total) NR_CHECK(hipHostFree(t.h_total));
-    if (t.hfail) NR_CHECK(hipHostFree(t.hfail));
-    {   // the warm-binning schedule
-        auto& S = t.sched;
-        void* sp[] = {S.off, S.items, S.dplan, S.blocks, S.off2};
-        for (void* p : sp)
-            if (p) NR_CHECK(hipFree(p));
-        if (S.ready) NR_CHECK(hipEventDestroy(S.ready));
-    }
+    ctx->tri.release();
     for (auto& p : ctx->evPending) {
         NR_CHECK(hipEventDestroy(p.second.first));
         NR_CHECK(hipEventDestroy(p.second.second));

@@ -44,12 +44,64 @@ struct BinKey {
     u64 mask;
 };
 
-// Scratch of the triangle pipeline, grown on demand (never shrunk).
+// A device array grown on demand (never shrunk): pointer and capacity in
+// elements.  Converts to the pointer (a template that deduces its argument
+// types -- hipExtLaunchKernelGGL, hipcub -- takes `.p`).  No destructor: the
+// owner's release() calls release(), with the device set.
+template <class T>
+struct DevArray {
+    T* p = nullptr;
+    size_t cap = 0;
+    operator T*() const { return p; }
+    // would ensure(n) reallocate (and so free memory the device may still read)?
+    bool needs(size_t n) const { return !p || cap < n; }
+    inline bool ensure(size_t n, bool* grew = nullptr);
+    void release() {
+        if (p) NR_CHECK(hipFree(p));
+        p = nullptr; cap = 0;
+    }
+};
+// Room for n elements in each of K arrays of one capacity (only ever grown
+// here, together): a regrow frees them all and allocates max(n, 3/2 capacity)
+// each, contents lost (*grew).  False: hipMalloc failed (latched, capacity 0).
+template <class T, size_t K>
+bool nr_ensure_together(DevArray<T>* const (&a)[K], size_t n, bool* grew = nullptr) {
+    if (grew) *grew = false;
+    if (!a[0]->needs(n)) return true;
+    const size_t cap = a[0]->cap, m = n > cap * 3 / 2 ? n : cap * 3 / 2;
+    for (DevArray<T>* x : a) x->release();
+    for (DevArray<T>* x : a)
+        if (hipMalloc((void**)&x->p, m * sizeof(T)) != hipSuccess) {
+            nr_set_error_msg("triangle scratch: hipMalloc failed");
+            for (DevArray<T>* y : a) y->cap = 0;
+            return false;
+        }
+    for (DevArray<T>* x : a) x->cap = m;
+    if (grew) *grew = true;
+    return true;
+}
+template <class T>
+inline bool DevArray<T>::ensure(size_t n, bool* grew) {
+    DevArray<T>* const one[1] = {this};
+    return nr_ensure_together(one, n, grew);
+}
+
+// Totals of one binned triangle batch (the plan kernel's, nr_tri_free.hip).
+struct BatchTotals {
+    u64 n = 0;       // triangles (0: no batch yet)
+    u32 pairs = 0;   // (tile, triangle) pairs
+    u32 items = 0;   // k_vis work items
+    u32 split = 0;   // slices of split tiles (key slots)
+    u32 heavy = 0;   // dense tiles (k_vis workgroup size)
+};
+
+// Scratch of the triangle pipeline, grown on demand (never shrunk).  Each
+// struct's release() frees all it declares (DestroyRenderContext, streams idle).
 struct TriScratch {
-    u64* cnt = nullptr; u64* off = nullptr; size_t tri_cap = 0;          // per triangle
-    f64* orec = nullptr; size_t orec_cap = 0;   // ordered raster: per-triangle setup records (ORec doubles each)
-    u32* keys[2] = {nullptr, nullptr}; u32* vals[2] = {nullptr, nullptr}; size_t pair_cap = 0;
-    u32* tile_start = nullptr; u32* tile_end = nullptr; size_t tile_cap = 0;
+    DevArray<u64> cnt, off;                                             // per triangle (grown together)
+    DevArray<f64> orec;   // ordered raster: per-triangle setup records (ORec doubles each)
+    DevArray<u32> keys[2], vals[2];                                     // pairs (grown together)
+    DevArray<u32> tile_start, tile_end;                                 // per tile (grown together)
     void* temp = nullptr; size_t temp_bytes = 0;                        // hipcub scratch
     u64* h_total = nullptr;                 // pinned readback: [0] pairs, [1] last count, [2] fragments
     u64* d_frag = nullptr;                  // device fragment counter
@@ -58,11 +110,11 @@ struct TriScratch {
     // double-buffered (FreeSet): a batch drawn from a TriangleBuffer is binned
     // on the device's binning stream while the previous batch's k_vis runs.
     struct FreeSet {
-        u32* fcnt = nullptr; u32* foff = nullptr; u32* fcur = nullptr; size_t ftile_cap = 0;
-        uint4* fitems = nullptr; size_t fitems_cap = 0;
-        u64* frect = nullptr; size_t frect_cap = 0;   // per-triangle tile rectangle (count -> emit)
-        f64* frec = nullptr; size_t frec_cap = 0;     // ordered batches: per-triangle setup records (ORec doubles each)
-        u32* flist = nullptr; size_t flist_cap = 0;
+        DevArray<u32> fcnt, foff, fcur;     // per tile (grown together)
+        DevArray<uint4> fitems;
+        DevArray<u64> frect;                // per-triangle tile rectangle (count -> emit)
+        DevArray<f64> frec;                 // ordered batches: per-triangle setup records (ORec doubles each)
+        DevArray<u32> flist;
         u32* dplan = nullptr;
         u64* h_plan = nullptr;              // pinned, device-mapped copy of the plan totals, (seq << 32) | value
         u64* d_hplan = nullptr;             // its device address
@@ -75,23 +127,28 @@ struct TriScratch {
         u32* gate = nullptr;                // [0] token of the set's last finished binning
         u32* gplan = nullptr;               // the raster's plan words (k_gate_wait copies the schedule's)
         u32 gateTok = 0;
+        void release() {
+            fcnt.release(); foff.release(); fcur.release(); fitems.release(); frect.release(); frec.release(); flist.release();
+            if (dplan) NR_CHECK(hipFree(dplan));
+            if (gate) NR_CHECK(hipFree(gate));
+            if (gplan) NR_CHECK(hipFree(gplan));
+            if (h_plan) NR_CHECK(hipHostFree(h_plan));
+            if (evBin) NR_CHECK(hipEventDestroy(evBin));
+            if (evVis) NR_CHECK(hipEventDestroy(evVis));
+        }
     } fset[3];
     int fnext = 0;                          // set of the next batch
-    u32* fdone = nullptr; size_t fdone_cap = 0;   // split-tile slice counters (k_vis only)
-    u64* kslot = nullptr; size_t kslot_cap = 0;   // split-tile key slots, TH*TW keys per slice (k_vis)
-    u32 lastSplit = 0;                      // split-tile slices of the last validated batch (slot estimate)
+    DevArray<u32> fdone;                    // split-tile slice counters (k_vis only)
+    DevArray<u64> kslot;                    // split-tile key slots, TH*TW keys per slice (k_vis)
     u32 planSeq = 0;                        // sequence number of the last async plan
-    u64 lastPairs = 0;                      // capacity estimate for the next batch
-    u32 lastItems = 0;                      // k_vis work items of the last validated batch (grid estimate)
-    u32 lastHeavy = 0;                      // dense tiles of the last batch (k_vis workgroup size)
-    u64 lastN = 0;                          // its triangle count (k_vis variant choice)
+    BatchTotals last;                       // the last validated batch's: the next one's estimates, the k_vis variant
     u64 capOverride = 0;                    // testing: force this pair capacity
     int coopMode = 0;                       // k_vis variant: 0 auto, 1 coop, 2 lane-only (SetCoopRaster)
     u32 splitAt = 0, dslice = 0;            // dense-tile split limits (SetSplitLimits; 0: NR_SPLIT_AT / NR_DSLICE)
-    f64* stage = nullptr; size_t stage_cap = 0;   // DrawTriangles() with host arrays
+    DevArray<f64> stage;                    // DrawTriangles() with host arrays
     // DrawMesh (nr_mesh.hip): the draw's transformed vertices and assembled soup -- (x, y) nv*2, z nv (padded
     // to an even count), xy n*6, z n*3; read by the batch until it is settled, like `stage`
-    f64* mstage = nullptr; size_t mstage_cap = 0;
+    DevArray<f64> mstage;
     // warm binning (nr_tri_free.hip): the tile offsets, k_vis work items and
     // plan totals of the last validated binning of one TriangleBuffer under
     // one binning key -- a later draw of the same buffer under the same key
@@ -101,11 +158,10 @@ struct TriScratch {
         bool valid = false;
         u64 tbUid = 0;
         BinKey key;
-        u32* off = nullptr; size_t off_cap = 0;          // ntiles + 1 list offsets
-        uint4* items = nullptr; size_t items_cap = 0;    // k_vis work items
+        DevArray<u32> off;                               // ntiles + 1 list offsets
+        DevArray<uint4> items;                           // k_vis work items
         u32* dplan = nullptr;                            // the plan's device totals {pairs, items, slices, fits}
-        u32 pairs = 0, nitems = 0, heavy = 0, split = 0;
-        u64 n = 0;
+        BatchTotals totals;
         u64 gen = 0;                                     // process-unique generation of this schedule
         hipEvent_t ready = nullptr;                      // the copies above are done (main stream)
         bool waitReady = false;                          // the next warm binning on the binning stream waits for it
@@ -120,9 +176,15 @@ struct TriScratch {
         // pairs, for a draw of the same buffer under a transform that moves no
         // vertex more than LOOSE_PX from the key's (a moving scene: k_bin_warm
         // into these ranges, k_vis slices each tile's actual count)
-        u32* off2 = nullptr; size_t off2_cap = 0;        // ntiles + 1 loose list offsets
+        DevArray<u32> off2;                              // ntiles + 1 loose list offsets
         u64 off2Gen = 0;                                 // gen they were formed for (0: none)
         u64 pairs2 = 0;                                  // a bound of off2[ntiles] (list capacity)
+        void release() {
+            off.release(); items.release(); off2.release();
+            if (dplan) NR_CHECK(hipFree(dplan));
+            if (blocks) NR_CHECK(hipFree(blocks));
+            if (ready) NR_CHECK(hipEventDestroy(ready));
+        }
     } sched;
     int warmMode = 0;                       // 0 automatic (NR_WARM), 1 on, 2 off (SetWarmBinning)
     u64 warmBatches = 0;                    // batches binned warm (GetWarmBatchCount)
@@ -141,6 +203,19 @@ struct TriScratch {
     // binning set or the schedule, it waits for the binning stream (evSide)
     bool sideGated = false;
     hipEvent_t evSide = nullptr;
+    void release() {
+        cnt.release(); off.release(); orec.release(); tile_start.release(); tile_end.release();
+        for (int k = 0; k < 2; ++k) { keys[k].release(); vals[k].release(); }
+        fdone.release(); kslot.release(); stage.release(); mstage.release();
+        if (temp) NR_CHECK(hipFree(temp));
+        if (d_frag) NR_CHECK(hipFree(d_frag));
+        if (d_flag) NR_CHECK(hipFree(d_flag));
+        if (h_total) NR_CHECK(hipHostFree(h_total));
+        if (hfail) NR_CHECK(hipHostFree(hfail));   // (dfail is its device address)
+        if (evSide) NR_CHECK(hipEventDestroy(evSide));
+        for (auto& F : fset) F.release();
+        sched.release();
+    }
 };
 
 enum NRKernelId { NRK_TRI_COUNT = 0, NRK_TRI_SCAN, NRK_TRI_EMIT, NRK_TRI_SORT, NRK_TILE_RANGES,
@@ -246,7 +321,7 @@ struct TriangleBuffer {
     // a draw under the same key is sized from them and needs no validation
     bool known = false;
     BinKey knownKey;
-    u32 knownPairs = 0, knownHeavy = 0, knownItems = 0, knownSplit = 0;
+    BatchTotals knownTotals;
     u64 uid = 0;          // process-unique id (a context's warm schedule names its buffer by it)
     // per cluster of CLUSTER consecutive triangles (one wave of the binning
     // kernels): its user-space bounding box {xmin, ymin, xmax, ymax} (NaN when

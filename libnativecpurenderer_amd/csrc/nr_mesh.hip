@@ -164,10 +164,7 @@ bool assemble(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out) {
     TriScratch& sc = ctx->tri;
     const size_t nv = (size_t)m->nv, n = (size_t)m->n;
     const size_t vzn = (nv + 1) & ~(size_t)1;   // keeps the soup's xy 16-byte aligned
-    f64* buf[1] = {sc.mstage};
-    const bool ok = nrtri::grow_set(buf, &sc.mstage_cap, nv * 2 + vzn + n * 9);
-    sc.mstage = buf[0];
-    if (!ok) return false;
+    if (!sc.mstage.ensure(nv * 2 + vzn + n * 9)) return false;
     f64* vxy = sc.mstage;
     f64* vz = vxy + nv * 2;
     f64* xy = vz + vzn;

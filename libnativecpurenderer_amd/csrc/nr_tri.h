@@ -92,7 +92,7 @@ inline void set_owned_rows(BinParams& bp, int tiles_y) {
 }
 
 // (unsharded: no integer division -- it costs ~30 VALU instructions)
-__device__ __forceinline__ bool owned_row(int ty, int period, u64 mask) {
+__host__ __device__ __forceinline__ bool owned_row(int ty, int period, u64 mask) {
     return period == 1 || ((mask >> (ty % period)) & 1ull);
 }
 
@@ -498,26 +498,33 @@ __device__ __forceinline__ void write_ordered_record(f64* rec, i64 t, const f64 
 
 enum Opacity { OPQ_UNKNOWN = 0, OPQ_OPAQUE, OPQ_BLENDED };
 
-template <typename T, size_t K>
-bool grow_set(T* (&ptrs)[K], size_t* cap, size_t need) {
-    if (*cap >= need && ptrs[0]) return true;
-    size_t n = need > *cap * 3 / 2 ? need : *cap * 3 / 2;
-    for (size_t k = 0; k < K; ++k) {
-        if (ptrs[k]) NR_CHECK(hipFree(ptrs[k]));
-        ptrs[k] = nullptr;
-    }
-    for (size_t k = 0; k < K; ++k)
-        if (hipMalloc((void**)&ptrs[k], n * sizeof(T)) != hipSuccess) {
-            nr_set_error_msg("triangle scratch: hipMalloc failed");
-            *cap = 0;
-            return false;
-        }
-    *cap = n;
-    return true;
-}
+// Words of a binned batch's plan (k_free_plan*): the device copy (a set's
+// dplan, the schedule's, a gate's gplan) holds the first PW_DEV, read by the
+// kernels after the plan; the host copy (FreeSet::h_plan) all PW_COUNT.
+enum PlanWord {
+    PW_PAIRS = 0,   // (tile, triangle) pairs
+    PW_ITEMS,       // k_vis work items
+    PW_SPLIT,       // slices of split tiles
+    PW_FITS,        // the list, items and key slots had room (ordered: and every list fits the LDS sort)
+    PW_DEV,
+    PW_SEQ = PW_DEV,   // the batch's sequence number
+    PW_HEAVY,          // dense tiles
+    PW_LONGEST,        // longest tile list (ordered batches; else 0)
+    PW_COUNT
+};
+
 bool grow_temp(TriScratch& sc, size_t need);
 
 FrameParams frame_params(RenderContext* ctx, const TriSrc& src, const TexView* tex = nullptr);
+inline BinParams bin_params(const FrameParams& fp) {   // the binning's view of the same snapshot
+    BinParams bp;
+    bp.src = fp.src;
+    for (int k = 0; k < 6; ++k) bp.m[k] = fp.m[k];
+    bp.W = fp.W; bp.H = fp.H; bp.tiles_x = fp.tiles_x;
+    bp.period = fp.period; bp.mask = fp.mask;
+    set_owned_rows(bp, fp.tiles_y);
+    return bp;
+}
 void finish_batch(RenderContext* ctx, const FrameParams& fp);
 u32* tile_stamps(RenderContext* ctx, i64 ntiles);   // the context's tile stamps, next epoch (nr_tri.hip)
 
@@ -536,7 +543,7 @@ constexpr u32 ORD_SORT_CAP = 8192;    // longest tile list the ordered raster so
 constexpr int ORD_BIN_TILES = 16384;  // tiles of the binned ordered path (the register plan kernel's limit)
 // binned ordered batches: k_tile_sort sorts each tile's list [off[t], off[t + 1])
 // in place (binning stream), then the raster runs one workgroup per tile; both
-// are no-ops unless plan[3] (fits)
+// are no-ops unless plan[PW_FITS]
 void launch_tile_sort(const u32* off, u32* list, const u32* plan, int ntiles, hipStream_t s, hipEvent_t stop);
 void launch_ordered_binned(const FrameParams& fp, const u32* list, const u32* off, const u32* plan, const f64* rec,
                            int ntiles, hipStream_t s, hipEvent_t start, hipEvent_t stop);

@@ -258,6 +258,21 @@ void nr_settle(RenderContext* ctx) {
     nr_flush_commands(ctx);   // recorded draws come after the last batch in program order
 }
 
+// The context's staging array (TriScratch::stage) laid out for a batch of n
+// triangles with ncol attribute doubles each: xy n*6 | z n*3, padded to an even
+// count (keeps the attributes 16-byte aligned) | attributes n*ncol.  The caller
+// has settled the context (a pending batch may still read the array).  False:
+// it could not be grown (error latched).
+struct Stage { f64* xy; f64* z; f64* attr; };
+static bool stage_batch(RenderContext* ctx, i64 n, size_t ncol, Stage* st) {
+    const size_t zn = ((size_t)n * 3 + 1) & ~(size_t)1;
+    if (!ctx->tri.stage.ensure((size_t)n * (6 + ncol) + zn)) return false;
+    st->xy = ctx->tri.stage;
+    st->z = st->xy + (size_t)n * 6;
+    st->attr = st->z + zn;
+    return true;
+}
+
 extern "C" {
 
 // New (no reference counterpart): depth-test LESS on/off, depth write on/off.
@@ -296,16 +311,12 @@ void DrawTrianglesDevice(RenderContext* ctx, const f64* xy, const f64* z, const 
     if ((((uintptr_t)xy | (uintptr_t)rgba) & 15) && n > 0) {
         NR_CHECK(hipSetDevice(ctx->device));
         settle(ctx);
-        const size_t ncol = gouraud ? 12 : 4, zn = ((size_t)n * 3 + 1) & ~(size_t)1;
-        f64* stage_buf[1] = {ctx->tri.stage};
-        if (!grow_set(stage_buf, &ctx->tri.stage_cap, (size_t)n * (6 + ncol) + zn)) return;
-        ctx->tri.stage = stage_buf[0];
-        f64* dxy = ctx->tri.stage;
-        f64* dz = dxy + (size_t)n * 6;
-        f64* dc = dz + zn;
-        NR_CHECK(hipMemcpyAsync(dxy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
-        NR_CHECK(hipMemcpyAsync(dc, rgba, (size_t)n * ncol * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
-        draw(ctx, dxy, z, dc, n, gouraud ? ATTR_GOURAUD : ATTR_FLAT, OPQ_UNKNOWN, nullptr, z != nullptr);   // z stays the caller's
+        const size_t ncol = gouraud ? 12 : 4;
+        Stage st;
+        if (!stage_batch(ctx, n, ncol, &st)) return;
+        NR_CHECK(hipMemcpyAsync(st.xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
+        NR_CHECK(hipMemcpyAsync(st.attr, rgba, (size_t)n * ncol * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
+        draw(ctx, st.xy, z, st.attr, n, gouraud ? ATTR_GOURAUD : ATTR_FLAT, OPQ_UNKNOWN, nullptr, z != nullptr);   // z stays the caller's
         return;
     }
     draw(ctx, xy, z, rgba, n, gouraud ? ATTR_GOURAUD : ATTR_FLAT, OPQ_UNKNOWN, nullptr, true);
@@ -317,19 +328,13 @@ void DrawTriangles(RenderContext* ctx, const f64* xy, const f64* z, const f64* r
     settle(ctx);   // a pending batch may still read the staging buffer
     if (n <= 0) return;
     const size_t ncol = gouraud ? 12 : 4;
-    const size_t zn = ((size_t)n * 3 + 1) & ~(size_t)1;   // keeps the colours 16-byte aligned
-    const size_t need = (size_t)n * (6 + ncol) + zn;
-    f64* stage_buf[1] = {ctx->tri.stage};
-    if (!grow_set(stage_buf, &ctx->tri.stage_cap, need)) return;
-    ctx->tri.stage = stage_buf[0];
-    f64* dxy = ctx->tri.stage;
-    f64* dz = dxy + (size_t)n * 6;
-    f64* dc = dz + zn;
-    NR_CHECK(hipMemcpyAsync(dxy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    if (z) NR_CHECK(hipMemcpyAsync(dz, z, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    NR_CHECK(hipMemcpyAsync(dc, rgba, (size_t)n * ncol * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    Stage st;
+    if (!stage_batch(ctx, n, ncol, &st)) return;
+    NR_CHECK(hipMemcpyAsync(st.xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    if (z) NR_CHECK(hipMemcpyAsync(st.z, z, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    NR_CHECK(hipMemcpyAsync(st.attr, rgba, (size_t)n * ncol * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
     NR_CHECK(hipStreamSynchronize(ctx->stream));   // caller may reuse its arrays on return
-    draw(ctx, dxy, z ? dz : nullptr, dc, n, gouraud ? ATTR_GOURAUD : ATTR_FLAT, host_opacity(rgba, n, gouraud), nullptr,
+    draw(ctx, st.xy, z ? st.z : nullptr, st.attr, n, gouraud ? ATTR_GOURAUD : ATTR_FLAT, host_opacity(rgba, n, gouraud), nullptr,
          false);
 }
 
@@ -338,18 +343,13 @@ void DrawTexturedTriangles(RenderContext* ctx, Texture* tex, const f64* xy, cons
     NR_CHECK(hipSetDevice(ctx->device));
     nr_settle(ctx);   // a pending batch may still read the staging buffer; recorded draws come first
     if (!check_texture(ctx, tex, "DrawTexturedTriangles") || n <= 0) return;
-    const size_t zn = ((size_t)n * 3 + 1) & ~(size_t)1;   // keeps the uv 16-byte aligned
-    f64* stage_buf[1] = {ctx->tri.stage};
-    if (!grow_set(stage_buf, &ctx->tri.stage_cap, (size_t)n * 12 + zn)) return;
-    ctx->tri.stage = stage_buf[0];
-    f64* dxy = ctx->tri.stage;
-    f64* dz = dxy + (size_t)n * 6;
-    f64* duv = dz + zn;
-    NR_CHECK(hipMemcpyAsync(dxy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    if (z) NR_CHECK(hipMemcpyAsync(dz, z, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    NR_CHECK(hipMemcpyAsync(duv, uv, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    Stage st;
+    if (!stage_batch(ctx, n, 6, &st)) return;
+    NR_CHECK(hipMemcpyAsync(st.xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    if (z) NR_CHECK(hipMemcpyAsync(st.z, z, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    NR_CHECK(hipMemcpyAsync(st.attr, uv, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
     NR_CHECK(hipStreamSynchronize(ctx->stream));   // caller may reuse its arrays on return
-    draw_textured(ctx, tex, dxy, z ? dz : nullptr, duv, n, nullptr, false);
+    draw_textured(ctx, tex, st.xy, z ? st.z : nullptr, st.attr, n, nullptr, false);
 }
 
 // New: textured triangles from device-resident arrays (as DrawTrianglesDevice).
@@ -359,15 +359,11 @@ void DrawTexturedTrianglesDevice(RenderContext* ctx, Texture* tex, const f64* xy
     nr_settle(ctx);
     if (!check_texture(ctx, tex, "DrawTexturedTrianglesDevice") || n <= 0) return;
     if (((uintptr_t)xy | (uintptr_t)uv) & 15) {   // (16-byte vector loads: re-stage, as DrawTrianglesDevice)
-        const size_t zn = ((size_t)n * 3 + 1) & ~(size_t)1;
-        f64* stage_buf[1] = {ctx->tri.stage};
-        if (!grow_set(stage_buf, &ctx->tri.stage_cap, (size_t)n * 12 + zn)) return;
-        ctx->tri.stage = stage_buf[0];
-        f64* dxy = ctx->tri.stage;
-        f64* duv = dxy + (size_t)n * 6 + zn;
-        NR_CHECK(hipMemcpyAsync(dxy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
-        NR_CHECK(hipMemcpyAsync(duv, uv, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
-        draw_textured(ctx, tex, dxy, z, duv, n, nullptr, z != nullptr);
+        Stage st;
+        if (!stage_batch(ctx, n, 6, &st)) return;
+        NR_CHECK(hipMemcpyAsync(st.xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
+        NR_CHECK(hipMemcpyAsync(st.attr, uv, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
+        draw_textured(ctx, tex, st.xy, z, st.attr, n, nullptr, z != nullptr);
         return;
     }
     draw_textured(ctx, tex, xy, z, uv, n, nullptr, true);

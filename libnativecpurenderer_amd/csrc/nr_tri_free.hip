@@ -314,8 +314,10 @@ __global__ __launch_bounds__(PLAN_T) void k_free_plan(u32* __restrict__ cnt, int
     }
     if (tid == 0) {
         off[ntiles] = ta;
-        const u32 t[7] = {ta, tb, tm, fits ? 1u : 0u, seq, th, 0u};
-        for (int k = 0; k < 4; ++k) totals[k] = t[k];
+        u32 t[PW_COUNT];
+        t[PW_PAIRS] = ta; t[PW_ITEMS] = tb; t[PW_SPLIT] = tm; t[PW_FITS] = fits ? 1u : 0u;
+        t[PW_SEQ] = seq; t[PW_HEAVY] = th; t[PW_LONGEST] = 0u;
+        for (int k = 0; k < PW_DEV; ++k) totals[k] = t[k];
         // the host copy (nr_settle polls it): every word carries the batch's
         // sequence number in its high half and is stored on its own (8-byte
         // stores are single-copy atomic), so the host needs no ordering between
@@ -323,7 +325,7 @@ __global__ __launch_bounds__(PLAN_T) void k_free_plan(u32* __restrict__ cnt, int
         // the whole L2 (buffer_wbl2), the dirty frame lines of the raster
         // running beside this kernel included (C3 -1.2 %, 8-way share -2 %,
         // profiles/r03_c3/ab_plan_release.txt)
-        for (int k = 0; k < 7; ++k)
+        for (int k = 0; k < PW_COUNT; ++k)
             __hip_atomic_store(&host_totals[k], ((u64)seq << 32) | t[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
@@ -468,9 +470,11 @@ __global__ __launch_bounds__(T) void k_free_plan_r(u32* __restrict__ cnt, int nt
     }
     if (tid == 0) {
         off[ntiles] = ta;   // (the same value as the padding stores write there)
-        const u32 t[7] = {ta, tb, tm, fits ? 1u : 0u, seq, th, smax};
-        for (int k = 0; k < 4; ++k) totals[k] = t[k];
-        for (int k = 0; k < 7; ++k)   // (host copy: see k_free_plan)
+        u32 t[PW_COUNT];
+        t[PW_PAIRS] = ta; t[PW_ITEMS] = tb; t[PW_SPLIT] = tm; t[PW_FITS] = fits ? 1u : 0u;
+        t[PW_SEQ] = seq; t[PW_HEAVY] = th; t[PW_LONGEST] = smax;
+        for (int k = 0; k < PW_DEV; ++k) totals[k] = t[k];
+        for (int k = 0; k < PW_COUNT; ++k)   // (host copy: see k_free_plan)
             __hip_atomic_store(&host_totals[k], ((u64)seq << 32) | t[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
@@ -480,7 +484,7 @@ __global__ __launch_bounds__(256) void k_free_emit(const BinParams bp, const u32
                                                    u32* __restrict__ cur, u32* __restrict__ list, int ntiles,
                                                    const u64* __restrict__ rects, const u32* __restrict__ plan) {
     extern __shared__ u32 hist[];
-    if (!plan[3]) return;
+    if (!plan[PW_FITS]) return;
     const int tid = threadIdx.x;
     const i64 base = (i64)blockIdx.x * 256 * TPT;
     u64 rk[TPT];   // every rectangle first: one round of load latency
@@ -568,19 +572,25 @@ __global__ __launch_bounds__(256) void k_free_emit(const BinParams bp, const u32
 // Columns follow tri_tiles: a triangle with a screen coordinate beyond 1e7
 // is binned into every column of its rows, so a box with a corner beyond
 // 1e7 (which may hold such a vertex) is never culled by x.
-__device__ __forceinline__ bool cluster_may_touch(const BinParams& bp, const f64* box) {
+// The margins are the caller's: px columns and rows rows each side, and a box
+// with a corner beyond hugeAt is not culled by x.  The device test takes
+// CLUSTER_DEV; the host's list of a schedule's active binning blocks
+// (warm_blocks) CLUSTER_HOST -- wider in every margin, so a superset.
+struct ClusterMargins { f64 px, rows, hugeAt; };
+constexpr ClusterMargins CLUSTER_DEV = {4.0, 1.0, 1e7}, CLUSTER_HOST = {12.0, 3.0, 5e6};
+__host__ __device__ __forceinline__ bool cluster_may_touch(const BinParams& bp, const f64* box, const ClusterMargins mg) {
     f64 y0 = INFINITY, y1 = -INFINITY, x0 = INFINITY, x1 = -INFINITY;
     bool huge = false;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         f64 sx, sy;
         nr_xform(bp.m, box[(c & 1) ? 2 : 0], box[(c & 2) ? 3 : 1], sx, sy);
-        if (!isfinite(sx) || !isfinite(sy)) return true;
-        huge = huge || fabs(sx) > 1e7 || fabs(sy) > 1e7;
+        if (!std::isfinite(sx) || !std::isfinite(sy)) return true;
+        huge = huge || fabs(sx) > mg.hugeAt || fabs(sy) > mg.hugeAt;
         y0 = fmin(y0, sy); y1 = fmax(y1, sy); x0 = fmin(x0, sx); x1 = fmax(x1, sx);
     }
-    if (!huge && (x1 < -4.0 || x0 > (f64)bp.W + 4.0)) return false;
-    const f64 r0 = fmax(ceil(y0) - 1.0, 0.0), r1 = fmin(ceil(y1) + 1.0, (f64)bp.H);
+    if (!huge && (x1 < -mg.px || x0 > (f64)bp.W + mg.px)) return false;
+    const f64 r0 = fmax(ceil(y0) - mg.rows, 0.0), r1 = fmin(ceil(y1) + mg.rows, (f64)bp.H);
     if (!(r0 < r1)) return false;
     if (bp.period == 1) return true;
     const int ty0 = (int)r0 / TH, ty1 = ((int)r1 - 1) / TH;
@@ -644,7 +654,7 @@ __global__ __launch_bounds__(256) void k_bin_warm(const BinParams bp, const u32*
 #pragma unroll
     for (int k = 0; k < TPT; ++k) {
         const i64 c = (base + k * 256) / NR_CLUSTER + __builtin_amdgcn_readfirstlane(tid >> 6);
-        cl[k] = !cbox || c * NR_CLUSTER >= bp.src.n || cluster_may_touch(bp, cbox + c * 4);
+        cl[k] = !cbox || c * NR_CLUSTER >= bp.src.n || cluster_may_touch(bp, cbox + c * 4, CLUSTER_DEV);
         anyc = anyc || cl[k];
     }
     // a workgroup none of whose clusters reaches an owned tile has nothing to do
@@ -1125,7 +1135,7 @@ constexpr int KS = TW + 1;        // padded row stride of the LDS tile keys
 // items are latency-bound: more waves per item).
 // The checks of a warm batch (k_bin_warm).  Batch-wide: the tag word
 // wstat[WS_TAG] != this batch's tag (no tile over its range) and the plan says
-// it fits (plan[3] == 0: the binning's token never came, k_gate_wait);
+// it fits (plan[PW_FITS] == 0: the binning's token never came, k_gate_wait);
 // otherwise the raster runs its work items over EVERY triangle of the batch
 // instead of the tile lists -- slow, but the same frame bit for bit (a
 // triangle that misses a tile adds nothing to it).  Per tile: the tile's
@@ -1135,7 +1145,7 @@ constexpr int KS = TW + 1;        // padded row stride of the LDS tile keys
 // exchanged for the batch's tag) reports it in host-mapped *hfail (reason 1 a
 // tile over its range, 2 token timeout, 3 a tile's count wrong, 4 a tile over
 // its loose range; nr_settle latches an error and drops the schedule, or for
-// 4 stops binning that buffer loose).  wstat null: a cold batch (plan[3] == 0
+// 4 stops binning that buffer loose).  wstat null: a cold batch (plan[PW_FITS] == 0
 // there: the batch does nothing, the host re-runs it).
 // Loose batches (a changed transform, loose ranges off = off2): the cursors
 // start at 0 and hold the tile's pair count n, which only has to fit the
@@ -1184,14 +1194,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
     bool fb = false;   // fallback: every triangle of the batch against every tile (WarmCheck)
     if (wc.wstat) {
         const u32 wt = __hip_atomic_load(&wc.wstat[WS_TAG], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fb = !plan[3] || wt == wc.tag;
-        if (fb && blockIdx.x == 0 && threadIdx.x == 0) warm_report(wc, plan[3] ? 1u : 2u, ~0u, wt, wc.tag);
-    } else if (!plan[3]) {
+        fb = !plan[PW_FITS] || wt == wc.tag;
+        if (fb && blockIdx.x == 0 && threadIdx.x == 0) warm_report(wc, plan[PW_FITS] ? 1u : 2u, ~0u, wt, wc.tag);
+    } else if (!plan[PW_FITS]) {
         return;
     }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: the chunk loop is a scalar loop)
-    const u32 nitems = plan[1];
+    const u32 nitems = plan[PW_ITEMS];
     unsigned long long myFrags = 0;
     if (COUNT && tid == 0) sFrag = 0;
     // grid-stride over the work items (the grid is sized from a capacity
@@ -1433,21 +1443,21 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
                     const u32 F = (u32)__builtin_amdgcn_readlane((int)fin, 63), fex = fin - len;
                     const int pk = (xs - (int)fex) * 64 + r;   // x - f, row
                     int fcar = -1;
-                    for (u32 fb = 0; fb < F; fb += 64) {
-                        const int q = window_owner(mk, lane, fex, len, fb, fcar);
+                    for (u32 f0 = 0; f0 < F; f0 += 64) {
+                        const int q = window_owner(mk, lane, fex, len, f0, fcar);
                         fcar = __builtin_amdgcn_readlane(q, 63);
                         const int pq = bperm(pk, q);
                         const u32 fid = bperm(rid, q);
                         const int rr = pq & 63;
-                        const int xx = (int)(fb + (u32)lane) + (pq >> 6);
+                        const int xx = (int)(f0 + (u32)lane) + (pq >> 6);
                         if (ZMODE == 0) {
-                            if (fb + (u32)lane < F) atomicMax(&key[rr * KS + xx], (u64)fid);
+                            if (f0 + (u32)lane < F) atomicMax(&key[rr * KS + xx], (u64)fid);
                             continue;
                         }
                         const f64 T1 = bperm(t1, q), T2 = bperm(t2, q);
                         const f64 qx0 = bperm(ox0, q), qe1y = bperm(oe1y, q), qe2y = bperm(oe2y, q);
                         const f64 qin = bperm(oin, q), qz0 = bperm(oz0, q), qd1 = bperm(od1, q), qd2 = bperm(od2, q);
-                        if (fb + (u32)lane < F) {
+                        if (f0 + (u32)lane < F) {
                             // frag_depth with the row's products: the same operations on the same values
                             const f64 X = (f64)(int)(x0 + xx);
                             const f64 dx = X - qx0;
@@ -1618,20 +1628,21 @@ struct VisArgs {
     WarmCheck wc;   // (a warm batch's checks; zero: a cold batch)
 };
 
+// t: the totals that pick the variant -- this batch's when they are known (a
+// warm, known-size or exact batch), else the last validated batch's
 template <int Z, bool C, int G>
-void launch_vis(const FrameParams& fp, const TriScratch& sc, const VisArgs& va, u32 grid, hipStream_t s,
-                hipEvent_t start, hipEvent_t stop) {
+void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& t, const VisArgs& va, u32 grid,
+                hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     const WarmCheck wc = va.wc;
-    // the flattened raster when the previous batch had more than COOP_PAIRS
-    // tiles per triangle (large triangles), or when there is no history
-    const bool coop = sc.coopMode ? sc.coopMode == 1
-                                  : (sc.lastN == 0 || sc.lastPairs > (u64)(COOP_PAIRS * (f64)sc.lastN));
-    // wide workgroups when the last batch had few pairs (a sharded frame):
-    // its dense items run at low occupancy and are latency-bound
-    const bool wide = !C && sc.lastN != 0 && sc.lastHeavy > 0 && sc.lastHeavy < WIDE_HEAVY;
+    // the flattened raster when the batch has more than COOP_PAIRS tiles per
+    // triangle (large triangles), or when there is no history
+    const bool coop = sc.coopMode ? sc.coopMode == 1 : (t.n == 0 || (u64)t.pairs > (u64)(COOP_PAIRS * (f64)t.n));
+    // wide workgroups when the batch has few pairs (a sharded frame): its
+    // dense items run at low occupancy and are latency-bound
+    const bool wide = !C && t.n != 0 && t.heavy > 0 && t.heavy < WIDE_HEAVY;
 #define NR_VIS(CO, NTT, ...)                                                                                       \
     hipExtLaunchKernelGGL((k_vis<Z, __VA_ARGS__>), dim3(grid), dim3(NTT), 0, s, start, stop, 0, fp, va.items,    \
-                          va.list, sc.kslot, sc.fdone, va.plan, wc)
+                          va.list, sc.kslot.p, sc.fdone.p, va.plan, wc)
     if (wide) {
         if (coop) NR_VIS(1, 2 * VWG, false, G, true, 2 * VWG);
         else NR_VIS(0, 2 * VWG, false, G, false, 2 * VWG);
@@ -1643,22 +1654,20 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const VisArgs& va, 
 #undef NR_VIS
 }
 
-template <int Z, int G>
-void launch_vis_z(const FrameParams& fp, const TriScratch& sc, const VisArgs& va, u32 grid, hipStream_t s,
-                  hipEvent_t start, hipEvent_t stop) {
-    if (fp.fragCounter) launch_vis<Z, true, G>(fp, sc, va, grid, s, start, stop);
-    else launch_vis<Z, false, G>(fp, sc, va, grid, s, start, stop);
-}
+// k_vis' ZMODE of a batch: 0 no test, 1 LESS + write, 2 LESS without write
+static int z_mode(const FrameParams& fp) { return fp.depthTest ? (fp.depthWrite ? 1 : 2) : 0; }
 
-static void launch_vis_any(const FrameParams& fp, const TriScratch& sc, const VisArgs& va, u32 grid, hipStream_t s,
-                           hipEvent_t start, hipEvent_t stop, int zmode, int mode) {
-#define NR_VZ(ZM) (mode == ATTR_TEX ? launch_vis_z<ZM, ATTR_TEX>(fp, sc, va, grid, s, start, stop) \
-                 : mode == ATTR_GOURAUD ? launch_vis_z<ZM, ATTR_GOURAUD>(fp, sc, va, grid, s, start, stop) \
-                 : launch_vis_z<ZM, ATTR_FLAT>(fp, sc, va, grid, s, start, stop))
+static void launch_vis_any(const FrameParams& fp, const TriScratch& sc, const BatchTotals& t, const VisArgs& va,
+                           u32 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+    const int zmode = z_mode(fp), mode = fp.src.mode;
+#define NR_VG(ZM, G) (fp.fragCounter ? launch_vis<ZM, true, G>(fp, sc, t, va, grid, s, start, stop) \
+                                     : launch_vis<ZM, false, G>(fp, sc, t, va, grid, s, start, stop))
+#define NR_VZ(ZM) (mode == ATTR_TEX ? NR_VG(ZM, ATTR_TEX) : mode == ATTR_GOURAUD ? NR_VG(ZM, ATTR_GOURAUD) : NR_VG(ZM, ATTR_FLAT))
     if (zmode == 1) NR_VZ(1);
     else if (zmode == 2) NR_VZ(2);
     else NR_VZ(0);
 #undef NR_VZ
+#undef NR_VG
 }
 
 // Events of a batch carried by the kernels' own completion signals
@@ -1685,14 +1694,11 @@ static BinKey bin_key(const BinParams& bp) {
     return k;
 }
 
-static void record_known(TriangleBuffer* tb, const BinKey& key, u32 pairs, u32 heavy, u32 items, u32 split) {
+static void record_known(TriangleBuffer* tb, const BinKey& key, const BatchTotals& t) {
     if (!tb) return;
     tb->known = true;
     tb->knownKey = key;
-    tb->knownPairs = pairs;
-    tb->knownHeavy = heavy;
-    tb->knownItems = items;
-    tb->knownSplit = split;
+    tb->knownTotals = t;
 }
 
 // Split limits of dense tiles (split_limits): a tile of more pairs than
@@ -1729,123 +1735,152 @@ static void main_after_side_binning(RenderContext* ctx) {
     sc.sideGated = false;
 }
 
+// ---- steps shared by the cold (free_enqueue) and warm (warm_enqueue) batches ----
+// Start of a batch in binning set F, binned on stream sb: the set's events on
+// first use, and a binning on the main stream ordered after any warm binning
+// still on the binning stream.
+static void set_begin(RenderContext* ctx, TriScratch::FreeSet& F, hipStream_t sb) {
+    if (!F.evBin) { F.evBin = sync_event(); F.evVis = sync_event(); }
+    if (sb == ctx->stream) main_after_side_binning(ctx);
+}
+
+// Scratch of the split tiles (k_vis only): a slice counter per tile, zeroed
+// when allocated (main stream; k_vis leaves them zero), and TH * TW key slots
+// per slice.  wait: the main stream, whose running raster may still read the
+// slots, drained before a regrow (null: the caller has drained it).
+static bool grow_fdone(RenderContext* ctx, int ntiles) {
+    TriScratch& sc = ctx->tri;
+    bool grew;
+    if (!sc.fdone.ensure((size_t)ntiles + 1, &grew)) return false;
+    if (grew) NR_CHECK(hipMemsetAsync(sc.fdone, 0, sc.fdone.cap * sizeof(u32), ctx->stream));
+    return true;
+}
+static bool grow_kslot(TriScratch& sc, size_t slices, hipStream_t wait) {
+    const size_t need = std::max<size_t>(slices, 1) * (TH * TW);
+    if (wait && sc.kslot.needs(need)) NR_CHECK(hipStreamSynchronize(wait));
+    return sc.kslot.ensure(need);
+}
+
+// Hand-off from a binning on the binning stream sb to the raster on the main
+// stream sa: the raster waits for F.evBin -- the stop event of the binning's
+// last kernel (carried), or a marker recorded here.  (A device-side hand-off
+// instead, a polling kernel on the main queue, measured +15 % on an 8-way share
+// and needs the two streams on separate hardware queues: removed in round 4;
+// warm batches have their own, k_gate_wait.)
+static void bin_handoff(TriScratch::FreeSet& F, hipStream_t sb, hipStream_t sa, bool carried) {
+    if (sb == sa) return;
+    if (!carried) NR_CHECK(hipEventRecord(F.evBin, sb));
+    NR_CHECK(hipStreamWaitEvent(sa, F.evBin, 0));
+}
+
+// The visibility raster of a batch binned into set F, on the main stream;
+// F.evVis (k_vis done reading the set) is the kernel's stop event, or a marker
+// when the batch has no work item.
+static void vis_tail(RenderContext* ctx, TriScratch::FreeSet& F, const FrameParams& fp, const VisArgs& va, u32 grid) {
+    if (grid > 0) {
+        FrameParams fpt = fp;   // (timed: the raster stamps itself on the device clock)
+        fpt.tstamp = nr_timing_stamp(ctx, NRK_TILE_RASTER);
+        launch_vis_any(fpt, ctx->tri, ctx->tri.last, va, grid, ctx->stream, nullptr, F.evVis);
+        NR_CHECK(hipGetLastError());
+    } else {
+        NR_CHECK(hipEventRecord(F.evVis, ctx->stream));
+    }
+    F.visRecorded = true;
+}
+
+// Host view of a plan kernel's totals (k_free_plan*): word k = (seq << 32) | value, each
+// stored by the device on its own; a batch's totals are complete once every word carries
+// its sequence number.
+static bool plan_ready(const TriScratch::FreeSet& F, u32 seq) {
+    for (int k = 0; k < PW_COUNT; ++k)
+        if ((u32)(__atomic_load_n(&F.h_plan[k], __ATOMIC_ACQUIRE) >> 32) != seq) return false;
+    return true;
+}
+static u32 plan_val(const TriScratch::FreeSet& F, PlanWord k) { return (u32)__atomic_load_n(&F.h_plan[k], __ATOMIC_ACQUIRE); }
+static BatchTotals plan_totals(const TriScratch::FreeSet& F, i64 n) {   // {n, pairs, items, split, heavy}
+    return BatchTotals{(u64)n, plan_val(F, PW_PAIRS), plan_val(F, PW_ITEMS), plan_val(F, PW_SPLIT), plan_val(F, PW_HEAVY)};
+}
+
 // Enqueues one batch with binning outputs in set `si`.  exact: read the
 // pair/item totals back (host sync) and allocate exactly; otherwise size the
 // list from the previous batch, let the plan kernel check it on the device
 // and validate later (nr_settle).  pipelined: bin on the device's binning
 // stream -- after the raster that last read set `si`, not after everything
 // queued before on the main stream -- so that it overlaps the previous
-// batch's k_vis (only for immutable inputs: a TriangleBuffer).
-// Host view of a plan kernel's totals (k_free_plan*): word k = (seq << 32) | value, each
-// stored by the device on its own; a batch's totals are complete once every word carries
-// its sequence number.
-static bool plan_ready(const TriScratch::FreeSet& F, u32 seq) {
-    for (int k = 0; k < 7; ++k)
-        if ((u32)(__atomic_load_n(&F.h_plan[k], __ATOMIC_ACQUIRE) >> 32) != seq) return false;
-    return true;
-}
-static u32 plan_val(const TriScratch::FreeSet& F, int k) { return (u32)__atomic_load_n(&F.h_plan[k], __ATOMIC_ACQUIRE); }
-
+// batch's k_vis (only for immutable inputs: a TriangleBuffer).  ordered: the
+// ordered raster's records and list sort, and its raster instead of k_vis.
+struct EnqueueMode {
+    bool exact = false, pipelined = false, ordered = false;
+};
+// known: the batch's totals from its buffer's last validated binning under the
+// same key (sizes the scratch; null: sized from the last validated batch).
 // Returns ENQ_FAIL, ENQ_OK, or (exact, ordered) ENQ_SORTED: a tile list is
 // longer than the ordered raster sorts in LDS -- nothing was rasterised; the
 // caller takes the global-sort path.
 enum { ENQ_FAIL = 0, ENQ_OK = 1, ENQ_SORTED = 2 };
-static int free_enqueue(RenderContext* ctx, const TriSrc& src, const FrameParams& fp, const BinParams& bp,
-                        bool exact, int si, bool pipelined, u32* seqOut, u64 knownPairs = 0,
-                        u32 knownItems = 0, bool idle = false, u32 knownSplit = 0, bool ordered = false) {
+static int free_enqueue(RenderContext* ctx, const FrameParams& fp, const BinParams& bp, int si, const EnqueueMode em,
+                        u32* seqOut, const BatchTotals* known = nullptr) {
+    const bool exact = em.exact, ordered = em.ordered;
+    const TriSrc& src = bp.src;
     hipStream_t sa = ctx->stream;
-    hipStream_t sb = pipelined ? nr_bin_stream_for(ctx->device) : sa;
+    hipStream_t sb = em.pipelined ? nr_bin_stream_for(ctx->device) : sa;
     TriScratch& sc = ctx->tri;
     TriScratch::FreeSet& F = sc.fset[si];
     const int ntiles = fp.tiles_x * fp.tiles_y;
-    const int zmode = fp.depthTest ? (fp.depthWrite ? 1 : 2) : 0;
-    const int mode = src.mode;
-    if (!F.evBin) { F.evBin = sync_event(); F.evVis = sync_event(); }
-    if (sb == sa) main_after_side_binning(ctx);
+    set_begin(ctx, F, sb);
     // the set's buffers are rewritten (binning stream) only after the raster
     // that last read them; a regrow frees them, so the host waits for it then
     if (F.visRecorded && sb != sa) NR_CHECK(hipStreamWaitEvent(sb, F.evVis, 0));
     auto quiesce = [&]() {
         if (F.visRecorded) NR_CHECK(hipEventSynchronize(F.evVis));
     };
+    // room for `need` elements of one of the set's arrays
+    auto grow = [&](auto& a, size_t need) {
+        need = std::max<size_t>(need, 1);
+        if (a.needs(need)) quiesce();
+        return a.ensure(need);
+    };
 
-    if (F.ftile_cap < std::max<size_t>((size_t)ntiles + 1, TILE_ARR) || !F.fcnt) quiesce();
-    u32* tb[3] = {F.fcnt, F.foff, F.fcur};
-    const size_t oldcap = F.ftile_cap;
     // (k_free_plan_r reads and writes the tile arrays as 16-byte vectors up to TILE_ARR)
-    if (!grow_set(tb, &F.ftile_cap, std::max<size_t>((size_t)ntiles + 1, TILE_ARR))) return ENQ_FAIL;
-    F.fcnt = tb[0]; F.foff = tb[1]; F.fcur = tb[2];
-    if (F.ftile_cap != oldcap) {   // counters start at zero; k_free_plan re-zeroes them after each use
-        NR_CHECK(hipMemsetAsync(F.fcnt, 0, F.ftile_cap * sizeof(u32), sb));
-        NR_CHECK(hipMemsetAsync(F.fcur, 0, F.ftile_cap * sizeof(u32), sb));
+    const size_t tneed = std::max<size_t>((size_t)ntiles + 1, TILE_ARR);
+    if (F.fcnt.needs(tneed)) quiesce();
+    bool grew;
+    if (!nr_ensure_together({&F.fcnt, &F.foff, &F.fcur}, tneed, &grew)) return ENQ_FAIL;
+    if (grew) {   // counters start at zero; k_free_plan re-zeroes them after each use
+        NR_CHECK(hipMemsetAsync(F.fcnt, 0, F.fcnt.cap * sizeof(u32), sb));
+        NR_CHECK(hipMemsetAsync(F.fcur, 0, F.fcur.cap * sizeof(u32), sb));
     }
-    u32* db[1] = {sc.fdone};
-    const size_t olddone = sc.fdone_cap;
-    if (!grow_set(db, &sc.fdone_cap, (size_t)ntiles + 1)) return ENQ_FAIL;
-    sc.fdone = db[0];
-    if (sc.fdone_cap != olddone) NR_CHECK(hipMemsetAsync(sc.fdone, 0, sc.fdone_cap * sizeof(u32), sa));
-    if (!F.dplan) NR_CHECK(hipMalloc(&F.dplan, 4 * sizeof(u32)));
-    if (!F.h_plan) {
+    if (!grow_fdone(ctx, ntiles)) return ENQ_FAIL;
+    if (!F.dplan) NR_CHECK(hipMalloc(&F.dplan, PW_DEV * sizeof(u32)));
+    if (!F.h_plan) {   // (8 words: PW_COUNT, to a whole 64-byte line)
         NR_CHECK(hipHostMalloc((void**)&F.h_plan, 8 * sizeof(u64), hipHostMallocMapped | hipHostMallocCoherent));
         for (int k = 0; k < 8; ++k) F.h_plan[k] = 0;
         NR_CHECK(hipHostGetDevicePointer((void**)&F.d_hplan, F.h_plan, 0));
     }
-    // key slots of split tiles' slices (TH * TW keys each): sized from the
-    // last validated batch; the plan kernel checks the capacity on the device
-    auto grow_kslot = [&](size_t slices) {
-        slices = std::max<size_t>(slices, 1);
-        if (sc.kslot_cap >= slices * (TH * TW) && sc.kslot) return true;
-        NR_CHECK(hipStreamSynchronize(sa));   // the running raster may still read them
-        u64* kb[1] = {sc.kslot};
-        const bool ok = grow_set(kb, &sc.kslot_cap, slices * (TH * TW));
-        sc.kslot = kb[0];
-        return ok;
-    };
-    auto grow_list = [&](size_t need) {
-        need = std::max<size_t>(need, 1);
-        if (F.flist_cap < need) quiesce();
-        u32* lb[1] = {F.flist};
-        const bool ok = grow_set(lb, &F.flist_cap, need);
-        F.flist = lb[0];
-        return ok;
-    };
-    auto grow_items = [&](size_t need) {
-        need = std::max<size_t>(need, 1);
-        if (F.fitems_cap < need) quiesce();
-        uint4* ib[1] = {F.fitems};
-        const bool ok = grow_set(ib, &F.fitems_cap, need);
-        F.fitems = ib[0];
-        return ok;
-    };
-    if (F.frect_cap < (size_t)src.n) quiesce();
-    u64* rb[1] = {F.frect};
-    if (!grow_set(rb, &F.frect_cap, (size_t)src.n)) return ENQ_FAIL;
-    F.frect = rb[0];
-    if (ordered) {   // the ordered raster's per-triangle setup records
-        const size_t need = (size_t)std::max<i64>(src.n, 1) * ORec;
-        if (F.frec_cap < need) quiesce();
-        f64* rr[1] = {F.frec};
-        if (!grow_set(rr, &F.frec_cap, need)) return ENQ_FAIL;
-        F.frec = rr[0];
-    }
+    if (!grow(F.frect, (size_t)src.n)) return ENQ_FAIL;
+    // the ordered raster's per-triangle setup records
+    if (ordered && !grow(F.frec, (size_t)std::max<i64>(src.n, 1) * ORec)) return ENQ_FAIL;
+    const BatchTotals last = sc.last;   // (the last validated batch's, or this batch's known totals)
     size_t cap;
     if (!exact) {
-        const u64 est = std::max<u64>(std::max<u64>(std::max<u64>(sc.lastPairs + sc.lastPairs / 4, (u64)src.n * 2), 1u << 20),
-                                      knownPairs);
+        const u64 est = std::max<u64>(std::max<u64>(std::max<u64>((u64)last.pairs + last.pairs / 4, (u64)src.n * 2), 1u << 20),
+                                      known ? known->pairs : 0);
         cap = (size_t)std::min<u64>(sc.capOverride ? sc.capOverride : est, 0xFFFFFFF0ull);
-        if (!grow_list(cap)) return ENQ_FAIL;
-        if (!sc.capOverride) cap = std::min<size_t>(F.flist_cap, 0xFFFFFFF0ull);
+        if (!grow(F.flist, cap)) return ENQ_FAIL;
+        if (!sc.capOverride) cap = std::min<size_t>(F.flist.cap, 0xFFFFFFF0ull);
         // work items: at most one per tile + one per full slice of the list,
         // twice that with dense tiles split into row halves (NR_ROW_SPLIT)
-        if (!grow_items((size_t)ntiles + cap / SLICE_MIN + 2)) return ENQ_FAIL;
-        // key slots of split tiles' slices (ordered batches use none): the last validated batch's + 25 %, at
-        // least one per tile (a slot per slice is needed only for tiles over the slice length)
-        if (!ordered && !grow_kslot(std::max<size_t>(std::max<size_t>((size_t)sc.lastSplit + sc.lastSplit / 4, knownSplit),
-                                                     std::min<size_t>((size_t)ntiles, 1024))))
+        if (!grow(F.fitems, (size_t)ntiles + cap / SLICE_MIN + 2)) return ENQ_FAIL;
+        // key slots of split tiles' slices (TH * TW keys each; ordered batches use none): the last validated
+        // batch's + 25 %, at least one per tile (a slot per slice is needed only for tiles over the slice
+        // length); the plan kernel checks the capacity on the device
+        if (!ordered &&
+            !grow_kslot(sc, std::max<size_t>(std::max<size_t>((size_t)last.split + last.split / 4, known ? known->split : 0),
+                                             std::min<size_t>((size_t)ntiles, 1024)), sa))
             return ENQ_FAIL;
     } else {
-        if (!grow_list(1) || !grow_items(1) || (!ordered && !grow_kslot(std::max<u32>(sc.lastSplit, 1)))) return ENQ_FAIL;
-        cap = std::min<size_t>(F.flist_cap, 0xFFFFFFF0ull);
+        if (!grow(F.flist, 1) || !grow(F.fitems, 1) || (!ordered && !grow_kslot(sc, last.split, sa))) return ENQ_FAIL;
+        cap = std::min<size_t>(F.flist.cap, 0xFFFFFFF0ull);
     }
 
     const int hbins = bp.hrows * fp.tiles_x;   // LDS histograms: the owned tile rows
@@ -1856,23 +1891,18 @@ static int free_enqueue(RenderContext* ctx, const TriSrc& src, const FrameParams
     u32 grid;
     for (int attempt = 0;; ++attempt) {
         nr_timing_begin_on(ctx, NRK_TRI_COUNT, &e0, &e1, sb);
-        if (ordered) {
-            if (ldsh) hipLaunchKernelGGL((k_free_count<true, true>), dim3(gb), dim3(256), hbytes, sb, bp, F.fcnt, ntiles, F.frect, F.frec);
-            else hipLaunchKernelGGL((k_free_count<false, true>), dim3(gb), dim3(256), 0, sb, bp, F.fcnt, ntiles, F.frect, F.frec);
-        } else if (ldsh) {
-            hipLaunchKernelGGL((k_free_count<true>), dim3(gb), dim3(256), hbytes, sb, bp, F.fcnt, ntiles, F.frect, nullptr);
-        } else {
-            hipLaunchKernelGGL((k_free_count<false>), dim3(gb), dim3(256), 0, sb, bp, F.fcnt, ntiles, F.frect, nullptr);
-        }
+        const auto count = ordered ? (ldsh ? k_free_count<true, true> : k_free_count<false, true>)
+                                   : (ldsh ? k_free_count<true> : k_free_count<false>);
+        hipLaunchKernelGGL(count, dim3(gb), dim3(256), hbytes, sb, bp, F.fcnt, ntiles, F.frect, ordered ? F.frec.p : nullptr);
         NR_CHECK(hipGetLastError());
         nr_timing_end_on(ctx, NRK_TRI_COUNT, e0, e1, sb);
 
         const u32 seq = ++sc.planSeq;
         *seqOut = seq;
         nr_timing_begin_on(ctx, NRK_TRI_SCAN, &e0, &e1, sb);
-        const u32 icap32 = (u32)std::min<size_t>(F.fitems_cap, 0xFFFFFFF0ull);
+        const u32 icap32 = (u32)std::min<size_t>(F.fitems.cap, 0xFFFFFFF0ull);
         // (an ordered batch uses no key slots, and its lists must fit the raster's LDS sort)
-        const u32 kcap32 = ordered ? 0xFFFFFFFFu : (u32)std::min<size_t>(sc.kslot_cap / (TH * TW), 0xFFFFFFF0ull);
+        const u32 kcap32 = ordered ? 0xFFFFFFFFu : (u32)std::min<size_t>(sc.kslot.cap / (TH * TW), 0xFFFFFFF0ull);
         const u32 maxc = ordered ? ORD_SORT_CAP : 0u;
         const u32 sat = sc.splitAt ? sc.splitAt : SPLIT_AT, dsl = sc.dslice ? sc.dslice : DSLICE;
         if (ntiles <= PLAN_T * PR_MAX || ordered) {   // (ordered: ntiles <= ORD_BIN_TILES)
@@ -1897,8 +1927,8 @@ static int free_enqueue(RenderContext* ctx, const TriSrc& src, const FrameParams
         }
         else
             hipLaunchKernelGGL(k_free_plan, dim3(1), dim3(1024), 0, sb, F.fcnt, ntiles, fp.tiles_x, fp.period,
-                               fp.mask, F.foff, F.fitems, F.fcur, F.dplan, F.d_hplan, (u32)cap,
-                               (u32)std::min<size_t>(F.fitems_cap, 0xFFFFFFF0ull), seq, SLICE_TARGET, kcap32, sat, dsl);
+                               fp.mask, F.foff, F.fitems, F.fcur, F.dplan, F.d_hplan, (u32)cap, icap32, seq,
+                               SLICE_TARGET, kcap32, sat, dsl);
         NR_CHECK(hipGetLastError());
         nr_timing_end_on(ctx, NRK_TRI_SCAN, e0, e1, sb);
 
@@ -1911,37 +1941,34 @@ static int free_enqueue(RenderContext* ctx, const TriSrc& src, const FrameParams
             // were dispatched only to exit
             // (two or three items per workgroup in turn: C3 k_vis 138 -> 150 / 157 us,
             // profiles/r03_c3/ab_grid_div.txt)
-            u64 g = F.fitems_cap;
-            if (knownItems) g = knownItems;
-            else if (sc.lastItems) g = std::max<u64>((u64)sc.lastItems + sc.lastItems / 4, 1024);
-            grid = (u32)std::min<u64>(std::min<u64>(g, F.fitems_cap), 8192);
+            u64 g = F.fitems.cap;
+            if (known && known->items) g = known->items;
+            else if (last.items) g = std::max<u64>((u64)last.items + last.items / 4, 1024);
+            grid = (u32)std::min<u64>(std::min<u64>(g, F.fitems.cap), 8192);
             break;
         }
         // exact: read the totals back; if the list or the items did not fit,
         // grow both and bin again (the plan kernel re-zeroed the counters)
         NR_CHECK(hipStreamSynchronize(sb));
-        sc.lastPairs = plan_val(F, 0);
-        sc.lastHeavy = plan_val(F, 5);
-        sc.lastItems = plan_val(F, 1);
-        sc.lastSplit = plan_val(F, 2);
-        sc.lastN = (u64)src.n;
-        grid = plan_val(F, 1);
-        if (plan_val(F, 3)) break;
-        if (ordered && plan_val(F, 6) > ORD_SORT_CAP) return ENQ_SORTED;
-        if (attempt > 0 || !grow_list(plan_val(F, 0)) || !grow_items(plan_val(F, 1)) ||
-            (!ordered && !grow_kslot(plan_val(F, 2)))) {
+        const BatchTotals t = sc.last = plan_totals(F, src.n);
+        grid = t.items;
+        if (plan_val(F, PW_FITS)) break;
+        if (ordered && plan_val(F, PW_LONGEST) > ORD_SORT_CAP) return ENQ_SORTED;
+        if (attempt > 0 || !grow(F.flist, t.pairs) || !grow(F.fitems, t.items) ||
+            (!ordered && !grow_kslot(sc, t.split, sa))) {
             nr_set_error_msg("triangle binning: pair list allocation failed");
             return ENQ_FAIL;
         }
-        cap = std::min<size_t>(F.flist_cap, 0xFFFFFFF0ull);
+        cap = std::min<size_t>(F.flist.cap, 0xFFFFFFF0ull);
     }
 
     nr_timing_begin_on(ctx, NRK_TRI_EMIT, &e0, &e1, sb);
     const bool xs = sb != sa && !e1;   // no timing events around the kernel
     hipEvent_t binStop = xs ? F.evBin : nullptr;
     hipEvent_t emitStop = ordered ? nullptr : binStop;   // (ordered: the list sort ends the binning)
-    if (ldsh) hipExtLaunchKernelGGL(k_free_emit<true>, dim3(gb), dim3(256), (u32)hbytes, sb, nullptr, emitStop, 0, bp, F.foff, F.fcur, F.flist, ntiles, F.frect, (const u32*)F.dplan);
-    else hipExtLaunchKernelGGL(k_free_emit<false>, dim3(gb), dim3(256), 0, sb, nullptr, emitStop, 0, bp, F.foff, F.fcur, F.flist, ntiles, F.frect, (const u32*)F.dplan);
+    hipExtLaunchKernelGGL(ldsh ? k_free_emit<true> : k_free_emit<false>, dim3(gb), dim3(256), (u32)hbytes, sb, nullptr,
+                          emitStop, 0, bp, (const u32*)F.foff, F.fcur.p, F.flist.p, ntiles, (const u64*)F.frect,
+                          (const u32*)F.dplan);
     NR_CHECK(hipGetLastError());
     nr_timing_end_on(ctx, NRK_TRI_EMIT, e0, e1, sb);
     if (ordered) {   // each tile's list into submission order
@@ -1950,27 +1977,17 @@ static int free_enqueue(RenderContext* ctx, const TriSrc& src, const FrameParams
         NR_CHECK(hipGetLastError());
         nr_timing_end_on(ctx, NRK_TRI_SORT, e0, e1, sb);
     }
-    if (sb != sa) {   // (a device-side hand-off instead, a polling kernel on the main queue, measured +15 % on
-                      // an 8-way share and needs the two streams on separate hardware queues: removed in round 4)
-        if (!xs) NR_CHECK(hipEventRecord(F.evBin, sb));
-        NR_CHECK(hipStreamWaitEvent(sa, F.evBin, 0));
-    }
+    bin_handoff(F, sb, sa, xs);
 
-    bool visDone = false;
-    FrameParams fpt = fp;   // (timed: the raster stamps itself on the device clock)
-    fpt.tstamp = nr_timing_stamp(ctx, NRK_TILE_RASTER);
     if (ordered) {   // one workgroup per tile, its list sorted in LDS
+        FrameParams fpt = fp;   // (timed: the raster stamps itself on the device clock)
+        fpt.tstamp = nr_timing_stamp(ctx, NRK_TILE_RASTER);
         launch_ordered_binned(fpt, F.flist, F.foff, F.dplan, F.frec, ntiles, sa, nullptr, F.evVis);
         NR_CHECK(hipGetLastError());
-        visDone = true;
-    } else if (grid > 0) {
-        launch_vis_any(fpt, sc, VisArgs{F.fitems, F.flist, F.dplan, WarmCheck{nullptr, nullptr, nullptr, 0u, 0u, nullptr, 0u}},
-                       grid, sa, nullptr, F.evVis, zmode, mode);
-        NR_CHECK(hipGetLastError());
-        visDone = true;
+        F.visRecorded = true;
+    } else {
+        vis_tail(ctx, F, fp, VisArgs{F.fitems, F.flist, F.dplan, WarmCheck{nullptr, nullptr, nullptr, 0u, 0u, nullptr, 0u}}, grid);
     }
-    if (!visDone) NR_CHECK(hipEventRecord(F.evVis, sa));
-    F.visRecorded = true;
     return ENQ_OK;
 }
 
@@ -2009,38 +2026,43 @@ static bool warm_inline(i64 n, int period, u64 mask, i64 W, i64 H) {
 // context's warm schedule: device copies on the main stream, after the
 // batch's raster; the set's next binning waits for them (F.evVis).
 static void sched_capture(RenderContext* ctx, TriScratch::FreeSet& F, const BinKey& key, const TriangleBuffer* tb,
-                          int ntiles, u32 pairs, u32 items, u32 heavy, u32 split, u64 n) {
+                          int ntiles, const BatchTotals& t) {
     TriScratch& sc = ctx->tri;
     if (!warm_on(sc) || !tb) return;
     auto& S = sc.sched;
     hipStream_t sa = ctx->stream;
     main_after_side_binning(ctx);   // (a late warm binning may still read S.off)
     S.valid = false;
-    if (S.off_cap < (size_t)ntiles + 1 || S.items_cap < std::max<size_t>(items, 1) || !S.dplan) {
+    const size_t ineed = std::max<size_t>(t.items, 1);
+    if (S.off.needs((size_t)ntiles + 1) || S.items.needs(ineed) || !S.dplan) {
         NR_CHECK(hipStreamSynchronize(sa));   // a queued warm batch may still read the old arrays
         NR_CHECK(hipStreamSynchronize(nr_bin_stream_for(ctx->device)));
-        u32* ob[1] = {S.off};
-        if (!grow_set(ob, &S.off_cap, (size_t)ntiles + 1)) return;
-        S.off = ob[0];
-        uint4* ib[1] = {S.items};
-        if (!grow_set(ib, &S.items_cap, std::max<size_t>(items, 1))) return;
-        S.items = ib[0];
-        if (!S.dplan) NR_CHECK(hipMalloc(&S.dplan, 4 * sizeof(u32)));
+        if (!S.off.ensure((size_t)ntiles + 1) || !S.items.ensure(ineed)) return;
+        if (!S.dplan) NR_CHECK(hipMalloc(&S.dplan, PW_DEV * sizeof(u32)));
     }
     if (!S.ready) S.ready = sync_event();
     NR_CHECK(hipMemcpyAsync(S.off, F.foff, ((size_t)ntiles + 1) * sizeof(u32), hipMemcpyDeviceToDevice, sa));
-    if (items) NR_CHECK(hipMemcpyAsync(S.items, F.fitems, (size_t)items * sizeof(uint4), hipMemcpyDeviceToDevice, sa));
-    NR_CHECK(hipMemcpyAsync(S.dplan, F.dplan, 4 * sizeof(u32), hipMemcpyDeviceToDevice, sa));
+    if (t.items) NR_CHECK(hipMemcpyAsync(S.items, F.fitems, (size_t)t.items * sizeof(uint4), hipMemcpyDeviceToDevice, sa));
+    NR_CHECK(hipMemcpyAsync(S.dplan, F.dplan, PW_DEV * sizeof(u32), hipMemcpyDeviceToDevice, sa));
     NR_CHECK(hipEventRecord(S.ready, sa));
     NR_CHECK(hipEventRecord(F.evVis, sa));   // the set is rewritten only after the copies
     F.visRecorded = true;
     S.valid = true;
     S.tbUid = tb->uid;
     S.key = key;
-    S.pairs = pairs; S.nitems = items; S.heavy = heavy; S.split = split; S.n = n;
+    S.totals = t;
     static u64 g_gen = 0;
     S.gen = ++g_gen;
     S.waitReady = true;
+}
+
+// A validated binning of `tb` under `key` in set F: its totals are the
+// buffer's known sizes, and -- when it fitted, so that the set holds its
+// offsets and items -- it becomes the warm schedule.
+static void keep_binning(RenderContext* ctx, TriScratch::FreeSet& F, const BinKey& key, TriangleBuffer* tb, int ntiles,
+                         const BatchTotals& t, bool fitted = true) {
+    record_known(tb, key, t);
+    if (fitted) sched_capture(ctx, F, key, tb, ntiles, t);
 }
 
 static bool sched_matches(const TriScratch& sc, const TriangleBuffer* tb, const BinKey& key) {
@@ -2050,9 +2072,10 @@ static bool sched_matches(const TriScratch& sc, const TriangleBuffer* tb, const 
 }
 
 // Loose binning (round 6): the buffer of the schedule drawn under another
-// transform (same frame, shard pattern and depth mode), where no vertex moves
-// more than LOOSE_PX on screen from where the schedule's transform put it --
-// a moving or jittering scene.  Every tile's pair count then changes by the
+// transform (same frame and shard pattern; any depth mode -- the schedule
+// holds binning results only), where no vertex moves more than LOOSE_PX on
+// screen from where the schedule's transform put it -- a moving or jittering
+// scene.  Every tile's pair count then changes by the
 // triangles that cross its edges; the loose ranges (loose_cap) hold them, so
 // the batch bins in one pass (k_bin_warm) instead of count -> plan -> emit.
 // The displacement bound: the two affine maps differ by an affine map, whose
@@ -2156,35 +2179,14 @@ __global__ void k_gate_wait(const u32* __restrict__ gate, u32 tok, const u32* __
             break;
         }
     }
-    for (int k = 0; k < 4; ++k) gplan[k] = (k == 3 && !ok) ? 0u : splan[k];   // {pairs, items, slices, fits}
+    for (int k = 0; k < PW_DEV; ++k) gplan[k] = (k == PW_FITS && !ok) ? 0u : splan[k];
 }
 
 // The binning blocks (256 * TPT triangles) of a schedule with a cluster that
 // may reach an owned tile: cluster_may_touch on the host over the buffer's
-// cluster boxes, widened by two rows and eight columns each side (a superset
-// of the device test, which still runs per wave).  Built once per schedule:
-// the warm binning of a rank then launches only these workgroups (an 8-way
-// share: about 1 in 7).
-static bool host_cluster_may_touch(const BinParams& bp, const f64* box) {
-    f64 y0 = INFINITY, y1 = -INFINITY, x0 = INFINITY, x1 = -INFINITY;
-    bool huge = false;   // (tri_tiles' full-width rule, as the device test)
-    for (int c = 0; c < 4; ++c) {
-        f64 sx, sy;
-        nr_xform(bp.m, box[(c & 1) ? 2 : 0], box[(c & 2) ? 3 : 1], sx, sy);
-        if (!std::isfinite(sx) || !std::isfinite(sy)) return true;
-        huge = huge || std::fabs(sx) > 5e6 || std::fabs(sy) > 5e6;
-        y0 = std::min(y0, sy); y1 = std::max(y1, sy); x0 = std::min(x0, sx); x1 = std::max(x1, sx);
-    }
-    if (!huge && (x1 < -12.0 || x0 > (f64)bp.W + 12.0)) return false;
-    const f64 r0 = std::max(std::ceil(y0) - 3.0, 0.0), r1 = std::min(std::ceil(y1) + 3.0, (f64)bp.H);
-    if (!(r0 < r1)) return false;
-    if (bp.period == 1) return true;
-    const int ty0 = (int)r0 / TH, ty1 = ((int)r1 - 1) / TH;
-    if (ty1 >= ty0 + 64) return true;
-    for (int ty = ty0; ty <= ty1; ++ty)
-        if ((bp.mask >> (ty % bp.period)) & 1ull) return true;
-    return false;
-}
+// cluster boxes with the wider margins CLUSTER_HOST (the device test still
+// runs per wave).  Built once per schedule: the warm binning of a rank then
+// launches only these workgroups (an 8-way share: about 1 in 7).
 static void warm_blocks(RenderContext* ctx, const BinParams& bp, const TriangleBuffer* tb) {
     auto& S = ctx->tri.sched;
     if (S.blocksGen == S.gen) return;
@@ -2201,7 +2203,7 @@ static void warm_blocks(RenderContext* ctx, const BinParams& bp, const TriangleB
     for (i64 b = 0; b < nb; ++b) {
         bool any = false;
         for (i64 c = b * (per / NR_CLUSTER); c < std::min<i64>((b + 1) * (per / NR_CLUSTER), nc); ++c) {
-            const bool t = host_cluster_may_touch(bp, tb->hcbox.data() + c * 4);
+            const bool t = cluster_may_touch(bp, tb->hcbox.data() + c * 4, CLUSTER_HOST);
             any = any || t;
             anyCull = anyCull || !t;
         }
@@ -2229,18 +2231,18 @@ static void warm_blocks(RenderContext* ctx, const BinParams& bp, const TriangleB
 // bin into the schedule's loose ranges, cursors from 0 (k_bin_warm), and let
 // k_vis slice each tile's actual count.
 static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinParams& bp, const TriangleBuffer* tb,
-                         bool loose = false) {
+                         bool loose) {
     const f64* tbCbox = tb->cbox;
     TriScratch& sc = ctx->tri;
     auto& S = sc.sched;
+    const BatchTotals& T = S.totals;
     hipStream_t sa = ctx->stream;
     hipStream_t sb = warm_inline(bp.src.n, fp.period, fp.mask, fp.W, fp.H) ? sa : nr_bin_stream_for(ctx->device);
     const int ntiles = fp.tiles_x * fp.tiles_y;
     const int si = sc.fnext;
     sc.fnext = (sc.fnext + 1) % BIN_SETS;
     TriScratch::FreeSet& F = sc.fset[si];
-    if (!F.evBin) { F.evBin = sync_event(); F.evVis = sync_event(); }
-    if (sb == sa) main_after_side_binning(ctx);
+    set_begin(ctx, F, sb);
     if (!sc.hfail) {
         NR_CHECK(hipHostMalloc((void**)&sc.hfail, 4 * sizeof(u32), hipHostMallocMapped | hipHostMallocCoherent));
         for (int k = 0; k < 4; ++k) sc.hfail[k] = 0;
@@ -2249,43 +2251,28 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
     // cursors [0, ntiles), then the batch checks {report tag, error tag} (WarmCheck)
     const size_t tneed = std::max<size_t>((size_t)ntiles + 2, TILE_ARR);
     if (loose && S.off2Gen != S.gen)   // (a bound of the loose list: every tile's loose_cap)
-        S.pairs2 = (u64)S.pairs + S.pairs / 4 + 64ull * (u64)(ntiles + 1);
-    const size_t lneed = std::max<size_t>(loose ? (size_t)S.pairs2 : (size_t)S.pairs, 1);
+        S.pairs2 = (u64)T.pairs + T.pairs / 4 + 64ull * (u64)(ntiles + 1);
+    const size_t lneed = std::max<size_t>(loose ? (size_t)S.pairs2 : (size_t)T.pairs, 1);
     if (loose && lneed >= 0xF0000000ull) return false;
-    const bool grow = F.ftile_cap < tneed || !F.fcnt || F.flist_cap < lneed ||
-                      sc.kslot_cap < std::max<size_t>(S.split, 1) * (TH * TW) || sc.fdone_cap < (size_t)ntiles + 1;
-    if (grow) {   // (first use of a set, or a larger schedule: rare)
+    if (F.fcnt.needs(tneed) || F.flist.needs(lneed) || sc.kslot.needs(std::max<size_t>(T.split, 1) * (TH * TW)) ||
+        sc.fdone.needs((size_t)ntiles + 1)) {   // (first use of a set, or a larger schedule: rare)
         NR_CHECK(hipStreamSynchronize(sa));
         NR_CHECK(hipStreamSynchronize(nr_bin_stream_for(ctx->device)));
-        u32* tb3[3] = {F.fcnt, F.foff, F.fcur};
-        const size_t oldcap = F.ftile_cap;
-        if (!grow_set(tb3, &F.ftile_cap, tneed)) return false;
-        F.fcnt = tb3[0]; F.foff = tb3[1]; F.fcur = tb3[2];
-        if (F.ftile_cap != oldcap) {
-            NR_CHECK(hipMemsetAsync(F.fcnt, 0, F.ftile_cap * sizeof(u32), sa));
+        bool grew;
+        if (!nr_ensure_together({&F.fcnt, &F.foff, &F.fcur}, tneed, &grew)) return false;
+        if (grew) {
+            NR_CHECK(hipMemsetAsync(F.fcnt, 0, F.fcnt.cap * sizeof(u32), sa));
             F.curGen = 0;
         }
-        u32* lb[1] = {F.flist};
-        if (!grow_set(lb, &F.flist_cap, lneed)) return false;
-        F.flist = lb[0];
-        u64* kb[1] = {sc.kslot};
-        if (!grow_set(kb, &sc.kslot_cap, std::max<size_t>(S.split, 1) * (TH * TW))) return false;
-        sc.kslot = kb[0];
-        u32* db[1] = {sc.fdone};
-        const size_t olddone = sc.fdone_cap;
-        if (!grow_set(db, &sc.fdone_cap, (size_t)ntiles + 1)) return false;
-        sc.fdone = db[0];
-        if (sc.fdone_cap != olddone) NR_CHECK(hipMemsetAsync(sc.fdone, 0, sc.fdone_cap * sizeof(u32), sa));
+        if (!F.flist.ensure(lneed) || !grow_kslot(sc, T.split, nullptr) || !grow_fdone(ctx, ntiles)) return false;
     }
     // (the active blocks are found under the schedule's own transform: a loose batch launches them all)
     if (tbCbox && !loose) warm_blocks(ctx, bp, tb);
     if (loose && S.off2Gen != S.gen) {   // the schedule's loose ranges, once (main stream, before S.ready)
-        if (S.off2_cap < (size_t)ntiles + 1) {
+        if (S.off2.needs((size_t)ntiles + 1)) {
             NR_CHECK(hipStreamSynchronize(sa));
             NR_CHECK(hipStreamSynchronize(nr_bin_stream_for(ctx->device)));
-            u32* ob[1] = {S.off2};
-            if (!grow_set(ob, &S.off2_cap, (size_t)ntiles + 1)) return false;
-            S.off2 = ob[0];
+            if (!S.off2.ensure((size_t)ntiles + 1)) return false;
         }
         hipLaunchKernelGGL(k_loose_off, dim3(1), dim3(1024), 0, sa, (const u32*)S.off, S.off2, ntiles);
         NR_CHECK(hipGetLastError());
@@ -2299,7 +2286,7 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
     // cursors: epoch e of this schedule on this set (k_bin_warm); zeroed for a
     // new schedule, after a cold batch on the set, or before they could wrap
     // (loose: from zero every batch -- they count the tile's pairs)
-    if (loose || F.curGen != S.gen || (u64)(F.curEpoch + 1) * std::max<u32>(S.pairs, 1) >= 0xF0000000ull) {
+    if (loose || F.curGen != S.gen || (u64)(F.curEpoch + 1) * std::max<u32>(T.pairs, 1) >= 0xF0000000ull) {
         NR_CHECK(hipMemsetAsync(F.fcur, 0, ((size_t)ntiles + 2) * sizeof(u32), sb));   // (and the check words)
         F.curGen = loose ? 0 : S.gen;
         F.curEpoch = 0;
@@ -2312,7 +2299,7 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
     const bool gated = sb != sa && !e1;   // same-queue hand-off (k_gate_wait) instead of an event wait
     if (gated && !F.gate) {
         NR_CHECK(hipMalloc(&F.gate, 4 * sizeof(u32)));
-        NR_CHECK(hipMalloc(&F.gplan, 4 * sizeof(u32)));
+        NR_CHECK(hipMalloc(&F.gplan, PW_DEV * sizeof(u32)));
         // zeroed in order on the signalling stream: a plain hipMemset (null
         // stream) may still be pending when the first signal lands and zero
         // it -- that raster's wait then times out (seen with a cold-batch gate
@@ -2340,13 +2327,9 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
     const int grid = useBlocks ? (int)S.nblocks : gb;
     if (inject == 4 && gated) hipLaunchKernelGGL(k_delay_binning, dim3(1), dim3(64), 0, sb);
     if (grid > 0) {
-        if (ldsh)
-            hipExtLaunchKernelGGL(k_bin_warm<true>, dim3(grid), dim3(256), (u32)(2 * hbins * sizeof(u32)), sb, nullptr,
-                                  binStop, 0, bp, binOff, F.fcur, F.flist, wstat, tag, epoch, cbox, blocks, (u32)inject,
-                                  (u32)loose);
-        else
-            hipExtLaunchKernelGGL(k_bin_warm<false>, dim3(grid), dim3(256), 0, sb, nullptr, binStop, 0, bp, binOff,
-                                  F.fcur, F.flist, wstat, tag, epoch, cbox, blocks, (u32)inject, (u32)loose);
+        hipExtLaunchKernelGGL(ldsh ? k_bin_warm<true> : k_bin_warm<false>, dim3(grid), dim3(256),
+                              ldsh ? (u32)(2 * hbins * sizeof(u32)) : 0u, sb, nullptr, binStop, 0, bp, binOff, F.fcur.p,
+                              F.flist.p, wstat, tag, epoch, cbox, blocks, (u32)inject, (u32)loose);
     } else if (binStop) {
         NR_CHECK(hipEventRecord(F.evBin, sb));
     }
@@ -2362,25 +2345,12 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
         NR_CHECK(hipGetLastError());
         visPlan = F.gplan;
         sc.sideGated = true;
-    } else if (sb != sa) {
-        if (!xs) NR_CHECK(hipEventRecord(F.evBin, sb));
-        NR_CHECK(hipStreamWaitEvent(sa, F.evBin, 0));
+    } else {
+        bin_handoff(F, sb, sa, xs);
     }
-    // this batch's totals pick the k_vis variant (launch_vis)
-    sc.lastN = S.n; sc.lastPairs = S.pairs; sc.lastHeavy = S.heavy; sc.lastItems = S.nitems; sc.lastSplit = S.split;
-    const int zmode = fp.depthTest ? (fp.depthWrite ? 1 : 2) : 0;
-    bool visDone = false;
-    if (S.nitems > 0) {
-        FrameParams fpt = fp;   // (timed: the raster stamps itself on the device clock)
-        fpt.tstamp = nr_timing_stamp(ctx, NRK_TILE_RASTER);
-        const WarmCheck wc{wstat, F.fcur, binOff, tag, epoch + 1, sc.dfail, (u32)loose};
-        launch_vis_any(fpt, sc, VisArgs{S.items, F.flist, visPlan, wc}, std::min<u32>(S.nitems, 8192), sa, nullptr,
-                       F.evVis, zmode, fp.src.mode);
-        NR_CHECK(hipGetLastError());
-        visDone = true;
-    }
-    if (!visDone) NR_CHECK(hipEventRecord(F.evVis, sa));
-    F.visRecorded = true;
+    sc.last = T;   // this batch's totals pick the k_vis variant (launch_vis)
+    const WarmCheck wc{wstat, F.fcur, binOff, tag, epoch + 1, sc.dfail, (u32)loose};
+    vis_tail(ctx, F, fp, VisArgs{S.items, F.flist, visPlan, wc}, std::min<u32>(T.items, 8192));
     return true;
 }
 
@@ -2397,12 +2367,7 @@ void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool c
     }
     if (!ordered && (fp.pendColor || fp.pendDepth))   // fast clear: the empty tiles' clears stay pending (k_vis)
         fp.tileStamp = tile_stamps(ctx, (i64)fp.tiles_x * fp.tiles_y), fp.tileEpoch = ctx->tileEpoch;
-    BinParams bp;
-    bp.src = src;
-    for (int k = 0; k < 6; ++k) bp.m[k] = ctx->m[k];
-    bp.W = ctx->width; bp.H = ctx->height; bp.tiles_x = fp.tiles_x;
-    bp.period = fp.period; bp.mask = fp.mask;
-    set_owned_rows(bp, fp.tiles_y);
+    const BinParams bp = bin_params(fp);
     // fragment counting reads a counter back anyway: run exact (synchronous);
     // so does a batch from the caller's device arrays: a deferred overflow
     // re-run (settle, at the next call) could read them after the caller has
@@ -2423,28 +2388,23 @@ void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool c
     const bool known = !ordered && fp.period == 1 && tb && tb->known &&
                        !sc.capOverride && memcmp(&tb->knownKey, &key, sizeof key) == 0;
     if (known && !exact) {   // this batch's totals pick the k_vis variant (launch_vis)
-        sc.lastN = (u64)src.n;
-        sc.lastPairs = tb->knownPairs;
-        sc.lastHeavy = tb->knownHeavy;
-        sc.lastItems = tb->knownItems;
-        sc.lastSplit = tb->knownSplit;
+        sc.last = tb->knownTotals;
+        sc.last.n = (u64)src.n;
     }
-    // warm: the schedule kept from this buffer's last validated binning under this key
+    // warm: the schedule kept from this buffer's last validated binning under
+    // this key, or (loose) under a key whose transform is within LOOSE_PX
     warm_poll(ctx);
-    if (!ordered && !exact && sched_matches(sc, tb, key)) {
-        if (warm_enqueue(ctx, fp, bp, tb)) {
+    if (!ordered && !exact) {
+        const bool same = sched_matches(sc, tb, key);
+        const bool loose = !same && loose_matches(sc, tb, key);
+        if ((same || loose) && warm_enqueue(ctx, fp, bp, tb, loose)) {
             ctx->lastPath = 1;
             ++sc.warmBatches;
+            if (loose) ++sc.looseBatches;
             finish_batch(ctx, fp);
+            return;
         }
-        return;
-    }
-    if (!ordered && !exact && loose_matches(sc, tb, key) && warm_enqueue(ctx, fp, bp, tb, true)) {
-        ctx->lastPath = 1;
-        ++sc.warmBatches;
-        ++sc.looseBatches;
-        finish_batch(ctx, fp);
-        return;
+        if (same) return;   // (error latched; a loose batch that could not be enqueued bins cold)
     }
     const int si = sc.fnext;
     sc.fnext = (sc.fnext + 1) % BIN_SETS;
@@ -2465,10 +2425,13 @@ void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool c
         if (q == hipErrorNotReady) (void)hipGetLastError();   // an answer, not a failure
         else if (q != hipSuccess) NR_CHECK(q);                 // a real asynchronous error: latch it
     }
-    sc.fset[si].curGen = 0;   // (its cursors will hold this batch's counts)
-    const int r = free_enqueue(ctx, src, fp, bp, exact, si, pipeOn && tb != nullptr && !exact && !idle, &seq,
-                               known ? tb->knownPairs : 0, known ? tb->knownItems : 0, idle, known ? tb->knownSplit : 0,
-                               ordered);
+    TriScratch::FreeSet& F = sc.fset[si];
+    F.curGen = 0;   // (its cursors will hold this batch's counts)
+    EnqueueMode em;
+    em.exact = exact;
+    em.pipelined = pipeOn && tb != nullptr && !exact && !idle;
+    em.ordered = ordered;
+    const int r = free_enqueue(ctx, fp, bp, si, em, &seq, known ? &tb->knownTotals : nullptr);
     if (r == ENQ_FAIL) return;
     if (r == ENQ_SORTED) {   // (exact) a tile list too long for the LDS sort
         fp.tileStamp = nullptr;   // (the ordered raster writes every tile)
@@ -2477,14 +2440,9 @@ void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool c
     }
     const int ntiles = fp.tiles_x * fp.tiles_y;
     if (exact) {
-        if (!ordered) {
-            record_known(tb, key, (u32)sc.lastPairs, sc.lastHeavy, sc.lastItems, sc.lastSplit);
-            sched_capture(ctx, sc.fset[si], key, tb, ntiles, (u32)sc.lastPairs, sc.lastItems, sc.lastHeavy,
-                          sc.lastSplit, (u64)src.n);
-        }
+        if (!ordered) keep_binning(ctx, F, key, tb, ntiles, sc.last);
     } else if (known) {
-        sched_capture(ctx, sc.fset[si], key, tb, ntiles, tb->knownPairs, tb->knownItems, tb->knownHeavy,
-                      tb->knownSplit, (u64)src.n);
+        sched_capture(ctx, F, key, tb, ntiles, sc.last);
     } else {
         PendingBatch* pb = new PendingBatch{src, fp, bp, si, seq, tb, key, ordered};
         ctx->pendingBatch = pb;
@@ -2522,33 +2480,26 @@ void settle(RenderContext* ctx) {
             std::this_thread::yield();
         }
     }
-    sc.lastN = (u64)pb->src.n;
-    sc.lastPairs = plan_val(F, 0);
-    sc.lastHeavy = plan_val(F, 5);
-    sc.lastItems = plan_val(F, 1);
-    sc.lastSplit = plan_val(F, 2);
-    if (!pb->ordered) {   // exact totals, fitted or not
-        record_known(pb->tb, pb->key, plan_val(F, 0), plan_val(F, 5), plan_val(F, 1), plan_val(F, 2));
-        if (plan_val(F, 3))   // it fitted: its offsets and items are the buffer's schedule under this key
-            sched_capture(ctx, F, pb->key, pb->tb, pb->fp.tiles_x * pb->fp.tiles_y, plan_val(F, 0), plan_val(F, 1),
-                          plan_val(F, 5), plan_val(F, 2), (u64)pb->src.n);
-    }
-    if (!plan_val(F, 3)) {
+    const int ntiles = pb->fp.tiles_x * pb->fp.tiles_y;
+    const bool fits = plan_val(F, PW_FITS) != 0;
+    sc.last = plan_totals(F, pb->src.n);
+    // exact totals, fitted or not; fitted: its offsets and items are the buffer's schedule under this key
+    if (!pb->ordered) keep_binning(ctx, F, pb->key, pb->tb, ntiles, sc.last, fits);
+    if (!fits) {
         // overflow (or, ordered, a tile list too long for the LDS sort): the
         // batch's later kernels did nothing; re-run it exactly on the main
         // stream, after everything queued so far
         NR_CHECK(hipEventSynchronize(F.evVis));
         u32 seq = 0;
-        const bool sorted = pb->ordered && plan_val(F, 6) > ORD_SORT_CAP;
+        const bool sorted = pb->ordered && plan_val(F, PW_LONGEST) > ORD_SORT_CAP;
+        EnqueueMode em;
+        em.exact = true;
+        em.ordered = pb->ordered;
         int rr = ENQ_SORTED;
-        if (sorted || (rr = free_enqueue(ctx, pb->src, pb->fp, pb->bp, true, pb->set, false, &seq, 0, 0, false, 0,
-                                         pb->ordered)) == ENQ_SORTED)
+        if (sorted || (rr = free_enqueue(ctx, pb->fp, pb->bp, pb->set, em, &seq)) == ENQ_SORTED)
             rerun_ordered_sorted(ctx, pb->src, pb->fp, pb->bp);   // (the context's flags are left as they are now)
-        else if (rr == ENQ_OK && !pb->ordered) {   // the exact re-run's binning is the buffer's schedule under this key
-            record_known(pb->tb, pb->key, (u32)sc.lastPairs, sc.lastHeavy, sc.lastItems, sc.lastSplit);
-            sched_capture(ctx, F, pb->key, pb->tb, pb->fp.tiles_x * pb->fp.tiles_y, (u32)sc.lastPairs, sc.lastItems,
-                          sc.lastHeavy, sc.lastSplit, (u64)pb->src.n);
-        }
+        else if (rr == ENQ_OK && !pb->ordered)   // the exact re-run's binning is the buffer's schedule under this key
+            keep_binning(ctx, F, pb->key, pb->tb, ntiles, sc.last);
     }
     delete pb;
 }

@@ -124,7 +124,7 @@ __device__ __forceinline__ u64 window_bits(int xs, int xe) {
 // stores alpha, so the per-fragment alpha moves are dropped.
 // BINNED: the tile's list comes from the order-free binning, sorted per tile
 // by k_tile_sort (tstart = the plan's list offsets: [off[tile], off[tile + 1]));
-// the batch is a no-op unless plan[3] (fits); otherwise [tstart, tend) of the
+// the batch is a no-op unless plan[PW_FITS] (fits); otherwise [tstart, tend) of the
 // globally sorted pairs.
 // MODE (AttrMode): a textured batch interpolates (u, v) where a Gouraud batch
 // interpolates its colour, fetches the texel (tex_index; rgb, and alpha from
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
     // (wave: uniform, so the per-wave masks and addresses below stay scalar)
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     raster_stamp_begin(fp);
-    if (BINNED && !plan[3]) return;
+    if (BINNED && !plan[PW_FITS]) return;
     if (!owned_row(ty, fp.period, fp.mask)) return;
     const u32 ls = tstart[tile], le = BINNED ? tstart[tile + 1] : tend[tile];
     if (ls == le && !fp.pendColor && !(DEPTH && fp.pendDepth)) return;
@@ -530,7 +530,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 constexpr int SORT_T = 512;
 __global__ __launch_bounds__(SORT_T) void k_tile_sort(const u32* __restrict__ off, u32* __restrict__ list,
                                                       const u32* __restrict__ plan) {
-    if (!plan[3]) return;
+    if (!plan[PW_FITS]) return;
     const u32 ls = off[blockIdx.x], n = off[blockIdx.x + 1] - ls;
     if (n < 2) return;
     __shared__ u32 SL[ORD_SORT_CAP];
@@ -594,13 +594,7 @@ void draw_ordered(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, boo
         return;
     }
     FrameParams fp = frame_params(ctx, src, tex);
-    BinParams bp;
-    bp.src = src;
-    for (int k = 0; k < 6; ++k) bp.m[k] = ctx->m[k];
-    bp.W = ctx->width; bp.H = ctx->height; bp.tiles_x = fp.tiles_x;
-    bp.period = fp.period; bp.mask = fp.mask;
-    set_owned_rows(bp, fp.tiles_y);
-    draw_ordered_sorted(ctx, src, fp, bp);
+    draw_ordered_sorted(ctx, src, fp, bin_params(fp));
 }
 
 namespace {
@@ -616,15 +610,9 @@ void ordered_sorted_kernels(RenderContext* ctx, const TriSrc& src, const FramePa
     TriScratch& sc = ctx->tri;
     const int ntiles = fp.tiles_x * fp.tiles_y;
 
-    u64* tri_bufs[2] = {sc.cnt, sc.off};
-    if (!grow_set(tri_bufs, &sc.tri_cap, (size_t)src.n)) return;
-    sc.cnt = tri_bufs[0]; sc.off = tri_bufs[1];
-    f64* rec_bufs[1] = {sc.orec};
-    if (!grow_set(rec_bufs, &sc.orec_cap, (size_t)std::max<i64>(src.n, 1) * ORec)) return;
-    sc.orec = rec_bufs[0];
-    u32* tile_bufs[2] = {sc.tile_start, sc.tile_end};
-    if (!grow_set(tile_bufs, &sc.tile_cap, (size_t)ntiles)) return;
-    sc.tile_start = tile_bufs[0]; sc.tile_end = tile_bufs[1];
+    if (!nr_ensure_together({&sc.cnt, &sc.off}, (size_t)src.n)) return;
+    if (!sc.orec.ensure((size_t)std::max<i64>(src.n, 1) * ORec)) return;
+    if (!nr_ensure_together({&sc.tile_start, &sc.tile_end}, (size_t)ntiles)) return;
 
     const int g1 = (int)((src.n + 255) / 256);
     hipEvent_t e0, e1;
@@ -634,10 +622,10 @@ void ordered_sorted_kernels(RenderContext* ctx, const TriSrc& src, const FramePa
     nr_timing_end(ctx, NRK_TRI_COUNT, e0, e1);
 
     size_t need = 0;
-    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, sc.cnt, sc.off, (int)src.n, s));
+    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, sc.cnt.p, sc.off.p, (int)src.n, s));
     if (!grow_temp(sc, need)) return;
     nr_timing_begin(ctx, NRK_TRI_SCAN, &e0, &e1);
-    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(sc.temp, need, sc.cnt, sc.off, (int)src.n, s));
+    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(sc.temp, need, sc.cnt.p, sc.off.p, (int)src.n, s));
     nr_timing_end(ctx, NRK_TRI_SCAN, e0, e1);
 
     // total pair count: sizes the sort (host sync)
@@ -677,9 +665,7 @@ void ordered_sorted_kernels(RenderContext* ctx, const TriSrc& src, const FramePa
 
     const u32* list = sc.tile_start;   // never dereferenced when every list is empty
     if (P > 0) {
-        u32* pair_bufs[4] = {sc.keys[0], sc.keys[1], sc.vals[0], sc.vals[1]};
-        if (!grow_set(pair_bufs, &sc.pair_cap, (size_t)P)) return;
-        sc.keys[0] = pair_bufs[0]; sc.keys[1] = pair_bufs[1]; sc.vals[0] = pair_bufs[2]; sc.vals[1] = pair_bufs[3];
+        if (!nr_ensure_together({&sc.keys[0], &sc.keys[1], &sc.vals[0], &sc.vals[1]}, (size_t)P)) return;
 
         nr_timing_begin(ctx, NRK_TRI_EMIT, &e0, &e1);
         hipLaunchKernelGGL(k_tri_emit, dim3(g1), dim3(256), 0, s, bp, sc.off, sc.keys[0], sc.vals[0]);
@@ -689,11 +675,11 @@ void ordered_sorted_kernels(RenderContext* ctx, const TriSrc& src, const FramePa
         int bits = 1;
         while ((1 << bits) < ntiles) ++bits;
         size_t sneed = 0;
-        NR_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sneed, sc.keys[0], sc.keys[1], sc.vals[0], sc.vals[1],
+        NR_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sneed, sc.keys[0].p, sc.keys[1].p, sc.vals[0].p, sc.vals[1].p,
                                                     (int)P, 0, bits, s));
         if (!grow_temp(sc, sneed)) return;
         nr_timing_begin(ctx, NRK_TRI_SORT, &e0, &e1);
-        NR_CHECK(hipcub::DeviceRadixSort::SortPairs(sc.temp, sneed, sc.keys[0], sc.keys[1], sc.vals[0], sc.vals[1],
+        NR_CHECK(hipcub::DeviceRadixSort::SortPairs(sc.temp, sneed, sc.keys[0].p, sc.keys[1].p, sc.vals[0].p, sc.vals[1].p,
                                                     (int)P, 0, bits, s));
         nr_timing_end(ctx, NRK_TRI_SORT, e0, e1);
 
