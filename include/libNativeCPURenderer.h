@@ -186,6 +186,10 @@ void SetWarmBinning(RenderContext* ctx, i64 mode);                       /* NEW:
 i64 GetWarmBatchCount(RenderContext* ctx);                               /* NEW (testing): batches binned warm */
 i64 GetLooseBatchCount(RenderContext* ctx);                              /* NEW (testing): of those, binned into the loose
                                                                             ranges of a changed transform */
+i64 GetReusedBatchCount(RenderContext* ctx);                             /* NEW (testing): of the warm batches, rasterised
+                                                                            from a kept pair list (no binning) */
+void SetListReuse(RenderContext* ctx, i64 mode);                         /* NEW: pair-list reuse of an unchanged repeat draw
+                                                                            0 auto (on), 2 off (every warm batch bins) */
 void SetWarmFaultInjection(RenderContext* ctx, i64 mode);                /* NEW (testing): fault in the next warm batch
                                  1 range overflow, 2 withheld token, 3 dropped pairs, 4 binning delayed past the
                                  raster's token wait (the frame must stay exact) */

@@ -98,6 +98,8 @@ DEVICE_ABI = {
     "SetWarmBinning": (None, (P, L)),
     "GetWarmBatchCount": (L, (P,)),
     "GetLooseBatchCount": (L, (P,)),
+    "GetReusedBatchCount": (L, (P,)),
+    "SetListReuse": (None, (P, L)),
     "ExecuteCommands": (L, (P, P, L, P, L)),
     "SetWarmFaultInjection": (None, (P, L)),
     "GetWarmFailureCount": (L, (P,)),

@@ -415,6 +415,7 @@ void ResizeRenderContext(RenderContext* ctx, i64 width, i64 height) {
     }
     ctx->pendColor = ctx->pendDepth = false;
     ctx->tileColor = ctx->tileDepth = false;
+    ctx->tri.sched.listSet = -1;   // (list reuse: a resized context bins again)
     i64 n = GetBufferSize(ctx);
     NR_CHECK(hipMalloc(&ctx->buffer, (size_t)(n > 0 ? n : 1) * sizeof(f64)));
     NR_CHECK(hipMemsetAsync(ctx->buffer, 0, (size_t)(n > 0 ? n : 1) * sizeof(f64), ctx->stream));

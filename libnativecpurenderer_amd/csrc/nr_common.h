@@ -179,6 +179,13 @@ struct TriScratch {
         DevArray<u32> off2;                              // ntiles + 1 loose list offsets
         u64 off2Gen = 0;                                 // gen they were formed for (0: none)
         u64 pairs2 = 0;                                  // a bound of off2[ntiles] (list capacity)
+        // list reuse: the binning set that holds the pair list (and cursors) of this
+        // generation's last warm binning, untouched since (-1: none), and that
+        // batch's checks -- a later batch under the same key rasterises from it
+        // without binning (warm_enqueue)
+        int listSet = -1;
+        u32 listTag = 0, listMult = 0;                   // its WarmCheck tag and cursor multiple (epoch + 1)
+        bool listGated = false;                          // binned beside the raster: its plan words are the set's gplan
         void release() {
             off.release(); items.release(); off2.release();
             if (dplan) NR_CHECK(hipFree(dplan));
@@ -189,6 +196,8 @@ struct TriScratch {
     int warmMode = 0;                       // 0 automatic (NR_WARM), 1 on, 2 off (SetWarmBinning)
     u64 warmBatches = 0;                    // batches binned warm (GetWarmBatchCount)
     u64 looseBatches = 0;                   // of those, into the loose ranges (GetLooseBatchCount)
+    u64 reusedBatches = 0;                  // of the warm ones, rasterised from a kept pair list (GetReusedBatchCount)
+    int reuseMode = 0;                      // list reuse: 0 automatic (on), 2 off (SetListReuse)
     std::vector<u64> looseBanned;           // buffers whose loose binning overflowed a tile: not binned loose again
     // warm-batch checks (k_vis WarmCheck): host-mapped word a raster sets when
     // a warm batch failed them (1 binning check, 2 token timeout), read by

@@ -482,11 +482,20 @@ i64 GetFragmentCount(RenderContext* ctx) { return (i64)ctx->fragTotal; }
 // New (testing / A-B measurement): warm binning of a TriangleBuffer drawn
 // again under the key of its last validated binning (one binning pass into
 // the kept tile ranges), 0 automatic (NR_WARM), 1 on, 2 off.
-void SetWarmBinning(RenderContext* ctx, i64 mode) { ctx->tri.warmMode = (int)(mode >= 0 && mode <= 2 ? mode : 0); }
+void SetWarmBinning(RenderContext* ctx, i64 mode) {
+    ctx->tri.warmMode = (int)(mode >= 0 && mode <= 2 ? mode : 0);
+    if (ctx->tri.warmMode == 2) ctx->tri.sched.listSet = -1;   // (no kept pair list outlives the switch)
+}
 // New (testing): number of batches of this context binned warm so far.
 i64 GetWarmBatchCount(RenderContext* ctx) { return (i64)ctx->tri.warmBatches; }
 // New (testing): of those, batches binned into the loose ranges (a changed transform).
 i64 GetLooseBatchCount(RenderContext* ctx) { return (i64)ctx->tri.looseBatches; }
+// New (testing): of the warm batches, those rasterised from the pair list an
+// earlier warm batch under the same key left in place (no binning at all).
+i64 GetReusedBatchCount(RenderContext* ctx) { return (i64)ctx->tri.reusedBatches; }
+// New (testing / A-B measurement): list reuse, 0 automatic (on), 2 off (every
+// warm batch bins, the cursors running on from epoch to epoch).
+void SetListReuse(RenderContext* ctx, i64 mode) { ctx->tri.reuseMode = mode == 2 ? 2 : 0; }
 // New (testing): a fault in the next warm batch -- 1 its binning finds its
 // tiles over their ranges, 2 (a batch binned beside the raster) its token is
 // withheld (the raster's wait times out after 1 s), 3 it drops a workgroup's
@@ -506,7 +515,10 @@ i64 GetLastRasterPath(RenderContext* ctx) { return ctx->lastPath; }
 
 // New (testing): cap the visibility path's pair list (0 = automatic), to
 // exercise the overflow re-run of nr_settle.
-void SetPairCapacityOverride(RenderContext* ctx, i64 pairs) { ctx->tri.capOverride = (u64)(pairs > 0 ? pairs : 0); }
+void SetPairCapacityOverride(RenderContext* ctx, i64 pairs) {
+    ctx->tri.capOverride = (u64)(pairs > 0 ? pairs : 0);
+    if (ctx->tri.capOverride) ctx->tri.sched.listSet = -1;
+}
 
 // New (testing / A-B measurement): force the ordered raster for every batch.
 void SetForceOrderedRaster(RenderContext* ctx, bool on) { ctx->forceOrdered = on ? 1 : 0; }

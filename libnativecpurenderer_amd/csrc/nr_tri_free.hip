@@ -2033,6 +2033,7 @@ static void sched_capture(RenderContext* ctx, TriScratch::FreeSet& F, const BinK
     hipStream_t sa = ctx->stream;
     main_after_side_binning(ctx);   // (a late warm binning may still read S.off)
     S.valid = false;
+    S.listSet = -1;   // (a new generation: no list of its own yet)
     const size_t ineed = std::max<size_t>(t.items, 1);
     if (S.off.needs((size_t)ntiles + 1) || S.items.needs(ineed) || !S.dplan) {
         NR_CHECK(hipStreamSynchronize(sa));   // a queued warm batch may still read the old arrays
@@ -2239,9 +2240,31 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
     hipStream_t sa = ctx->stream;
     hipStream_t sb = warm_inline(bp.src.n, fp.period, fp.mask, fp.W, fp.H) ? sa : nr_bin_stream_for(ctx->device);
     const int ntiles = fp.tiles_x * fp.tiles_y;
+    // List reuse: the schedule's last warm binning left its pair list in set
+    // S.listSet and nothing has written that set since.  The buffer is
+    // immutable and the key is the same, so a binning now would write the same
+    // pairs: rasterise from the kept list -- no binning, no gate, nothing on the
+    // binning stream, and the set rotation stays where it is.  The raster
+    // repeats that binning's checks (its tag, cursor multiple and plan words:
+    // the gate's copy carries a token timeout), so a list whose binning failed
+    // falls back on every reuse as it did on the binning frame, and reports
+    // once (warm_report, per tag); once the host has seen the failure the
+    // schedule is gone (warm_poll).  Stream order puts this raster after the one
+    // that first waited for the list; vis_tail re-records F.evVis, so the set's
+    // next binning waits for the last reader.  An injected fault bins.
+    if (!loose && S.listSet >= 0 && sc.reuseMode != 2 && !sc.warmInject) {
+        TriScratch::FreeSet& F = sc.fset[S.listSet];
+        sc.last = T;
+        const u32* plan = S.listGated ? F.gplan : S.dplan;
+        const WarmCheck wc{F.fcur + ntiles, F.fcur, S.off, S.listTag, S.listMult, sc.dfail, 0u};
+        vis_tail(ctx, F, fp, VisArgs{S.items, F.flist, plan, wc}, std::min<u32>(T.items, 8192));
+        ++sc.reusedBatches;
+        return true;
+    }
     const int si = sc.fnext;
     sc.fnext = (sc.fnext + 1) % BIN_SETS;
     TriScratch::FreeSet& F = sc.fset[si];
+    if (S.listSet == si) S.listSet = -1;   // (rewritten below, or left half grown)
     set_begin(ctx, F, sb);
     if (!sc.hfail) {
         NR_CHECK(hipHostMalloc((void**)&sc.hfail, 4 * sizeof(u32), hipHostMallocMapped | hipHostMallocCoherent));
@@ -2351,6 +2374,12 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
     sc.last = T;   // this batch's totals pick the k_vis variant (launch_vis)
     const WarmCheck wc{wstat, F.fcur, binOff, tag, epoch + 1, sc.dfail, (u32)loose};
     vis_tail(ctx, F, fp, VisArgs{S.items, F.flist, visPlan, wc}, std::min<u32>(T.items, 8192));
+    if (!loose) {   // the list later batches under this key reuse
+        S.listSet = si;
+        S.listTag = tag;
+        S.listMult = epoch + 1;
+        S.listGated = gated;
+    }
     return true;
 }
 
@@ -2427,6 +2456,7 @@ void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool c
     }
     TriScratch::FreeSet& F = sc.fset[si];
     F.curGen = 0;   // (its cursors will hold this batch's counts)
+    if (sc.sched.listSet == si) sc.sched.listSet = -1;   // (and its list this batch's pairs)
     EnqueueMode em;
     em.exact = exact;
     em.pipelined = pipeOn && tb != nullptr && !exact && !idle;

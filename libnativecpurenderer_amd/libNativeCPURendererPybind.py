@@ -525,6 +525,16 @@ class RenderContext:
         schedule (the same buffer under a transform moved by <= 2 px)."""
         return lib.GetLooseBatchCount(self._ptr)
 
+    def reused_batch_count(self) -> int:
+        """Of the warm batches, those rasterised from the pair list an earlier
+        warm batch under the same key left in place (no binning at all)."""
+        return lib.GetReusedBatchCount(self._ptr)
+
+    def set_list_reuse(self, mode: int):
+        """Pair-list reuse of an unchanged repeat draw: 0 automatic (on), 2
+        off (every warm batch bins again)."""
+        lib.SetListReuse(self._ptr, int(mode))
+
     def packed(self) -> "PackedCommands":
         """A packing front end of this context: its draw and state calls go
         to the library as one array per submit() (ExecuteCommands)."""
