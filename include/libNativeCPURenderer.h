@@ -176,6 +176,26 @@ void DrawMesh(RenderContext* ctx, Mesh* m, const f64* matrix16);         /* NEW:
 void DrawTexturedMesh(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrix16);   /* NEW: texture chosen per draw */
 bool AssembleMesh(RenderContext* ctx, Mesh* m, const f64* matrix16, f64* xy_out, f64* z_out);   /* NEW: DrawMesh's
                                  vertex stage and assembly alone, the soup (xy n*6, z n*3) copied to the host; a sync point */
+/* NEW: near-plane clipping and back-face culling of mesh draws (DESIGN §3 "Clip stage").  Per context, not part
+   of the save / restore stack, not recorded in command lists.  With both off (the default) mesh draws are
+   unchanged.  With either on, a mesh draw clips every triangle against cw = wNear on the device (0, 1 or 2 output
+   triangles, attributes interpolated in clip space, submission order kept), culls each output triangle by the
+   sign of area2 = (x1-x0)*(y2-y0) - (x2-x0)*(y1-y0) before the context's 2D transform (zero and NaN areas are
+   never culled), reads the output count back -- one wait for the device, of such draws only -- and rasterises
+   exactly that many triangles.  AssembleMesh ignores the state. */
+bool SetMeshNearPlane(RenderContext* ctx, f64 wNear);                    /* NEW: 0 off, > 0 the plane; negative or
+                                 non-finite: false, error latched, state unchanged */
+f64 GetMeshNearPlane(RenderContext* ctx);                                /* NEW */
+bool SetMeshCull(RenderContext* ctx, i64 mode);                          /* NEW: 0 none, 1 drops area2 > 0, 2 drops
+                                 area2 < 0; another value: false, error latched, state unchanged */
+i64 GetMeshCull(RenderContext* ctx);                                     /* NEW */
+i64 GetMeshLastTriangleCount(RenderContext* ctx);                        /* NEW: triangles the last mesh draw of ctx
+                                 rasterised: n_out of the clip stage, the mesh's n when the stage was off */
+bool AssembleMeshClipped(RenderContext* ctx, Mesh* m, const f64* matrix16, i64 cap, f64* xy_out, f64* z_out,
+                         f64* attr_out, i64* n_out);                     /* NEW: the soup a draw of m rasterises under
+                                 ctx's near plane and cull mode (the draw's own kernels): the full count in *n_out, the
+                                 first min(cap, *n_out) triangles copied to the host (xy x6, z x3, attr x12 Gouraud / x4
+                                 flat / x6 textured); a sync point; either mesh kind */
 void SetFragmentCounting(RenderContext* ctx, bool on);                   /* NEW: covered-fragment counter */
 i64 GetFragmentCount(RenderContext* ctx);                                /* NEW */
 i64 GetLastRasterPath(RenderContext* ctx);                               /* NEW: 1 order-free tiled, 2 ordered, 3 order-free frame */

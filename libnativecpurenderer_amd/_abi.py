@@ -89,6 +89,12 @@ DEVICE_ABI = {
     "DrawMesh": (None, (P, P, P)),
     "DrawTexturedMesh": (None, (P, P, P, P)),
     "AssembleMesh": (B, (P, P, P, P, P)),
+    "SetMeshNearPlane": (B, (P, D)),
+    "GetMeshNearPlane": (D, (P,)),
+    "SetMeshCull": (B, (P, L)),
+    "GetMeshCull": (L, (P,)),
+    "GetMeshLastTriangleCount": (L, (P,)),
+    "AssembleMeshClipped": (B, (P, P, P, L, P, P, P, P)),
     "SetFragmentCounting": (None, (P, B)),
     "GetFragmentCount": (L, (P,)),
     "GetLastRasterPath": (L, (P,)),

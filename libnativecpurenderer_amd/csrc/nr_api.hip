@@ -328,7 +328,9 @@ u64* nr_timing_stamp(RenderContext* ctx, int kid) {
 static const char* kKernelNames[NRK_COUNT_] = {"tri_count", "tri_scan",    "tri_emit", "tri_sort",
                                                "tile_ranges", "tile_raster", "prim",     "fill",
                                                "resolve",   "vis_init",    "output",   "gather",
-                                               "mesh_vertex", "mesh_assemble"};
+                                               "mesh_vertex", "mesh_assemble",
+                                               "mesh_clip_vertex", "mesh_clip_count", "mesh_clip_scan",
+                                               "mesh_clip_emit"};
 
 extern "C" {
 
@@ -789,7 +791,7 @@ void EnableKernelTiming(RenderContext* ctx, bool on) {
 
 // Sum and count of the named kernel's durations since the last reset
 // (names: tri_count tri_scan tri_emit tri_sort tile_ranges tile_raster prim fill resolve vis_init output gather
-// mesh_vertex mesh_assemble).
+// mesh_vertex mesh_assemble mesh_clip_vertex mesh_clip_count mesh_clip_scan mesh_clip_emit).
 bool GetKernelTiming(RenderContext* ctx, const char* name, f64* total_ms, i64* count) {
     NR_CHECK(hipSetDevice(ctx->device));
     timing_collect(ctx);

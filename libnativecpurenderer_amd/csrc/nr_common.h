@@ -149,6 +149,12 @@ struct TriScratch {
     // DrawMesh (nr_mesh.hip): the draw's transformed vertices and assembled soup -- (x, y) nv*2, z nv (padded
     // to an even count), xy n*6, z n*3; read by the batch until it is settled, like `stage`
     DevArray<f64> mstage;
+    // clipped / culled mesh draws (nr_mesh.hip, SetMeshNearPlane / SetMeshCull): the draw's clip coordinates
+    // (cx, cy, cz, cw) nv*4, and per source triangle its keep mask | output count | scanned offset, n each
+    // (+ the total); the emitted soup -- xy n_out*6, z n_out*3 (padded to an even count), attributes
+    // n_out*attr_stride -- is then what mstage holds
+    DevArray<f64> mclip;
+    DevArray<u32> mscan;
     // warm binning (nr_tri_free.hip): the tile offsets, k_vis work items and
     // plan totals of the last validated binning of one TriangleBuffer under
     // one binning key -- a later draw of the same buffer under the same key
@@ -215,7 +221,7 @@ struct TriScratch {
     void release() {
         cnt.release(); off.release(); orec.release(); tile_start.release(); tile_end.release();
         for (int k = 0; k < 2; ++k) { keys[k].release(); vals[k].release(); }
-        fdone.release(); kslot.release(); stage.release(); mstage.release();
+        fdone.release(); kslot.release(); stage.release(); mstage.release(); mclip.release(); mscan.release();
         if (temp) NR_CHECK(hipFree(temp));
         if (d_frag) NR_CHECK(hipFree(d_frag));
         if (d_flag) NR_CHECK(hipFree(d_flag));
@@ -229,7 +235,8 @@ struct TriScratch {
 
 enum NRKernelId { NRK_TRI_COUNT = 0, NRK_TRI_SCAN, NRK_TRI_EMIT, NRK_TRI_SORT, NRK_TILE_RANGES,
                   NRK_TILE_RASTER, NRK_PRIM, NRK_FILL, NRK_RESOLVE, NRK_VIS_INIT, NRK_OUTPUT, NRK_GATHER,
-                  NRK_MESH_VERTEX, NRK_MESH_ASSEMBLE, NRK_COUNT_ };
+                  NRK_MESH_VERTEX, NRK_MESH_ASSEMBLE, NRK_MESH_CLIP_VERTEX, NRK_MESH_CLIP_COUNT, NRK_MESH_CLIP_SCAN,
+                  NRK_MESH_CLIP_EMIT, NRK_COUNT_ };
 
 struct RenderContext {
     i64 width = 0, height = 0;
@@ -273,6 +280,12 @@ struct RenderContext {
     u64 fragTotal = 0;
     int lastPath = 0;                 // raster of the last triangle batch (1 order-free, 2 ordered)
     int forceOrdered = 0;             // testing: always take the ordered raster
+    // mesh front end (nr_mesh.hip): near plane cw = meshNear (0: off) and cull mode (0 none, 1 drops area2 > 0,
+    // 2 drops area2 < 0) of this context's mesh draws -- not part of the state stack, not recorded; and the
+    // triangle count the last mesh draw handed to the rasters
+    f64 meshNear = 0;
+    int meshCull = 0;
+    i64 meshLastCount = 0;
     iu8* u8buf = nullptr; size_t u8cap = 0;   // GetBufferAsUInt8 staging
     // multi-GPU: owned tile rows ty % nshards == shard (nr_dist.hip)
     int nshards = 1, shard = 0;

@@ -21,8 +21,21 @@
 // after nrtri::settle, the rule DrawTriangles follows for its staging buffer.
 // The attributes do not depend on the matrix: they are expanded through the
 // indices once, at creation.
+//
+// Near-plane clipping and back-face culling (SetMeshNearPlane / SetMeshCull,
+// DESIGN.md §3 "Clip stage"): with either on, a draw runs another four passes
+// instead of the two above -- clip coordinates per vertex, a per-triangle count
+// of its 0, 1 or 2 output triangles, an exclusive scan, and an emit pass that
+// writes the clipped soup and its interpolated attributes at the scanned
+// offsets (a stable compaction: submission order is kept).  The draw reads the
+// total back before it bins, so such a draw -- and only such a draw -- waits
+// for the device once.  With both off nothing here runs.
 #include "nr_tri.h"
 
+#include <hipcub/hipcub.hpp>
+
+#include <climits>
+#include <cmath>
 #include <string>
 
 struct Mesh {
@@ -82,6 +95,215 @@ __global__ __launch_bounds__(256) void k_mesh_attr(const u32* __restrict__ idx, 
     if (t >= nout) return;
     const u32 i = idx[perTri == 3 ? t : t * 3];
     for (int k = 0; k < w2; ++k) out[t * w2 + k] = vattr[(i64)i * w2 + k];
+}
+
+// ---- near-plane clipping and back-face culling --------------------------------
+// Pass C1: one thread per vertex, the clip coordinates (cx, cy | cz, cw) as two
+// 16-byte stores; the expressions of k_mesh_vertex.
+__global__ __launch_bounds__(256) void k_mesh_clip_vertex(const f64* __restrict__ pos, i64 nv, Mat4 M,
+                                                          double2* __restrict__ clip) {
+    const i64 v = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (v >= nv) return;
+    const f64 px = pos[v * 3], py = pos[v * 3 + 1], pz = pos[v * 3 + 2];
+    const f64 cx = ((M.m[0] * px + M.m[1] * py) + M.m[2] * pz) + M.m[3];
+    const f64 cy = ((M.m[4] * px + M.m[5] * py) + M.m[6] * pz) + M.m[7];
+    const f64 cz = ((M.m[8] * px + M.m[9] * py) + M.m[10] * pz) + M.m[11];
+    const f64 cw = ((M.m[12] * px + M.m[13] * py) + M.m[14] * pz) + M.m[15];
+    clip[v * 2] = make_double2(cx, cy);
+    clip[v * 2 + 1] = make_double2(cz, cw);
+}
+
+// A source triangle's clip coordinates.  The arrays are only ever indexed by
+// constants (unrolled loops) or through sel3: they stay in registers.
+struct ClipTri { f64 cx[3], cy[3], cz[3], cw[3]; };
+struct ClipPos { f64 x, y, z, t; };   // a polygon vertex on the screen; t: its cut parameter (a cut only)
+
+__device__ __forceinline__ f64 sel3(int k, const f64 (&v)[3]) { return k == 0 ? v[0] : (k == 1 ? v[1] : v[2]); }
+
+__device__ __forceinline__ void load_clip_tri(const u32* __restrict__ idx, const double2* __restrict__ clip, i64 t,
+                                              ClipTri& c) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const i64 i = (i64)idx[t * 3 + k];
+        const double2 a = clip[i * 2], b = clip[i * 2 + 1];
+        c.cx[k] = a.x; c.cy[k] = a.y; c.cz[k] = b.x; c.cw[k] = b.y;
+    }
+}
+
+// in0 | in1 << 1 | in2 << 2 with in_k = (cw_k >= wNear), false for a NaN;
+// without a near plane every corner counts as inside.
+__device__ __forceinline__ int inside_code(const ClipTri& c, f64 wNear) {
+    if (!(wNear > 0)) return 7;
+    return (c.cw[0] >= wNear ? 1 : 0) | (c.cw[1] >= wNear ? 2 : 0) | (c.cw[2] >= wNear ? 4 : 0);
+}
+
+// The Sutherland-Hodgman walk from corner 0 (emit corner k if inside, then the
+// cut of edge (k, k + 1) if its ends differ), tabulated: vertex s of the polygon
+// under inside-code c is (a, b) -- the inside corner a itself when b == a, else
+// the cut of the edge from a (inside) towards b (outside).
+//   c = 1: 0 0>1 0>2        c = 2: 1>0 1 1>2        c = 4: 2>1 2 2>0
+//   c = 3: 0 1 1>2 0>2      c = 5: 0 0>1 2>1 2      c = 6: 1>0 1 2 2>0      c = 7: 0 1 2
+// Two bits per code; the lookups are shifts of a constant (no indexed array).
+__host__ __device__ constexpr u32 pack7(u32 c1, u32 c2, u32 c3, u32 c4, u32 c5, u32 c6, u32 c7) {
+    return c1 << 2 | c2 << 4 | c3 << 6 | c4 << 8 | c5 << 10 | c6 << 12 | c7 << 14;
+}
+__host__ __device__ constexpr u32 slot_a_tab(int s) {
+    return s == 0 ? pack7(0, 1, 0, 2, 0, 1, 0) : s == 1 ? pack7(0, 1, 1, 2, 0, 1, 1)
+         : s == 2 ? pack7(0, 1, 1, 2, 2, 2, 2) : pack7(0, 0, 0, 0, 2, 2, 0);
+}
+__host__ __device__ constexpr u32 slot_b_tab(int s) {
+    return s == 0 ? pack7(0, 0, 0, 1, 0, 0, 0) : s == 1 ? pack7(1, 1, 1, 2, 1, 1, 1)
+         : s == 2 ? pack7(2, 2, 2, 0, 1, 2, 2) : pack7(0, 0, 2, 0, 2, 0, 0);
+}
+__device__ __forceinline__ int slot_a(int s, int code) { return (int)((slot_a_tab(s) >> (2 * code)) & 3u); }
+__device__ __forceinline__ int slot_b(int s, int code) { return (int)((slot_b_tab(s) >> (2 * code)) & 3u); }
+// output triangles before the cull, as a mask: bit 0 (q0, q1, q2), bit 1 (q0, q2, q3)
+__device__ __forceinline__ u32 clip_outputs(int code) {
+    return code == 0 ? 0u : ((code == 3 || code == 5 || code == 6) ? 3u : 1u);
+}
+
+// Polygon vertex (a, b).  A corner: c / cw, NaN where !(cw > 0) -- k_mesh_vertex's
+// bits (behind a near plane an inside corner has cw >= wNear > 0).  A cut, always
+// from the inside end a towards the outside end b, every operation rounded:
+//   t = (cw_a - wNear) / (cw_a - cw_b);  q = c_a + (c_b - c_a) * t;  q / wNear
+__device__ __forceinline__ ClipPos clip_slot_pos(const ClipTri& c, int a, int b, f64 wNear) {
+    const f64 ax = sel3(a, c.cx), ay = sel3(a, c.cy), az = sel3(a, c.cz), aw = sel3(a, c.cw);
+    ClipPos q;
+    q.t = 0;
+    if (a == b) {
+        q.x = q.y = q.z = NAN;
+        if (aw > 0) {
+            q.x = ax / aw;
+            q.y = ay / aw;
+            q.z = az / aw;
+        }
+    } else {
+        const f64 bx = sel3(b, c.cx), by = sel3(b, c.cy), bz = sel3(b, c.cz), bw = sel3(b, c.cw);
+        q.t = (aw - wNear) / (aw - bw);
+        const f64 qx = ax + (bx - ax) * q.t;
+        const f64 qy = ay + (by - ay) * q.t;
+        const f64 qz = az + (bz - az) * q.t;
+        q.x = qx / wNear;
+        q.y = qy / wNear;
+        q.z = qz / wNear;
+    }
+    return q;
+}
+
+// cull 1 drops area2 > 0, cull 2 drops area2 < 0; a zero or NaN area is never culled
+__device__ __forceinline__ bool clip_culled(const ClipPos& p0, const ClipPos& p1, const ClipPos& p2, int cull) {
+    const f64 area2 = (p1.x - p0.x) * (p2.y - p0.y) - (p2.x - p0.x) * (p1.y - p0.y);
+    return cull == 1 ? area2 > 0 : (cull == 2 ? area2 < 0 : false);
+}
+
+// Pass C2: one thread per source triangle: which of its output triangles survive
+// the clip and the cull (keep: bit 0 the first, bit 1 the second half of a
+// quad) and how many (cnt, the scan's input).  Without a cull no vertex is formed.
+__global__ __launch_bounds__(256) void k_mesh_clip_count(const u32* __restrict__ idx, i64 n,
+                                                         const double2* __restrict__ clip, f64 wNear, int cull,
+                                                         u32* __restrict__ keep, u32* __restrict__ cnt) {
+    const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    ClipTri c;
+    load_clip_tri(idx, clip, t, c);
+    const int code = inside_code(c, wNear);
+    u32 k = clip_outputs(code);
+    if (cull != 0 && k != 0) {
+        const ClipPos q0 = clip_slot_pos(c, slot_a(0, code), slot_b(0, code), wNear);
+        const ClipPos q1 = clip_slot_pos(c, slot_a(1, code), slot_b(1, code), wNear);
+        const ClipPos q2 = clip_slot_pos(c, slot_a(2, code), slot_b(2, code), wNear);
+        if (clip_culled(q0, q1, q2, cull)) k &= ~1u;
+        if (k & 2u) {
+            const ClipPos q3 = clip_slot_pos(c, slot_a(3, code), slot_b(3, code), wNear);
+            if (clip_culled(q0, q2, q3, cull)) k &= ~2u;
+        }
+    }
+    keep[t] = k;
+    cnt[t] = (k & 1u) + (k >> 1);
+}
+
+// One attribute component of polygon vertex (a, b) from the corners' v0, v1, v2:
+// the corner's own, or at a cut A_a + (A_b - A_a) * t (linear in clip space;
+// 1 + 0 * t stays 1).
+__device__ __forceinline__ f64 clip_attr(int a, int b, f64 t, f64 v0, f64 v1, f64 v2) {
+    const f64 va = a == 0 ? v0 : (a == 1 ? v1 : v2);
+    const f64 vb = b == 0 ? v0 : (b == 1 ? v1 : v2);
+    return a == b ? va : va + (vb - va) * t;
+}
+
+__device__ __forceinline__ void clip_store_pos(i64 o, const ClipPos& p0, const ClipPos& p1, const ClipPos& p2,
+                                               double2* __restrict__ xy, f64* __restrict__ z) {
+    xy[o * 3] = make_double2(p0.x, p0.y);
+    xy[o * 3 + 1] = make_double2(p1.x, p1.y);
+    xy[o * 3 + 2] = make_double2(p2.x, p2.y);
+    z[o * 3] = p0.z;
+    z[o * 3 + 1] = p1.z;
+    z[o * 3 + 2] = p2.z;
+}
+
+// Pass C3: one thread per source triangle with an output: forms the polygon
+// again (the count pass's expressions) and writes its kept triangles at the
+// scanned offset.  H 16-byte attribute words per corner: 2 (Gouraud RGBA), 1
+// (UV), or 0 for a flat mesh, whose one colour (two words per triangle) is
+// copied to each output.  The attributes go word by word -- the three corners'
+// word j in, the polygon's word j out -- so nothing is held in an array.
+template <int H>
+__global__ __launch_bounds__(256) void k_mesh_clip_emit(const u32* __restrict__ idx, i64 n,
+                                                        const double2* __restrict__ clip,
+                                                        const double2* __restrict__ attr, f64 wNear,
+                                                        const u32* __restrict__ keep, const u32* __restrict__ off,
+                                                        double2* __restrict__ xy, f64* __restrict__ z,
+                                                        double2* __restrict__ oattr) {
+    const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const u32 k = keep[t];
+    if (k == 0) return;
+    const i64 o0 = (i64)off[t];         // the first kept triangle
+    const i64 o1 = o0 + (i64)(k & 1u);  // the second half of a quad, when kept
+    ClipTri c;
+    load_clip_tri(idx, clip, t, c);
+    const int code = inside_code(c, wNear);
+    const int a0 = slot_a(0, code), b0 = slot_b(0, code), a1 = slot_a(1, code), b1 = slot_b(1, code);
+    const int a2 = slot_a(2, code), b2 = slot_b(2, code), a3 = slot_a(3, code), b3 = slot_b(3, code);
+    const ClipPos q0 = clip_slot_pos(c, a0, b0, wNear);
+    const ClipPos q2 = clip_slot_pos(c, a2, b2, wNear);
+    f64 t1 = 0, t3 = 0;
+    if (k & 1u) {
+        const ClipPos q1 = clip_slot_pos(c, a1, b1, wNear);
+        t1 = q1.t;
+        clip_store_pos(o0, q0, q1, q2, xy, z);
+    }
+    if (k & 2u) {
+        const ClipPos q3 = clip_slot_pos(c, a3, b3, wNear);
+        t3 = q3.t;
+        clip_store_pos(o1, q0, q2, q3, xy, z);
+    }
+    if constexpr (H == 0) {
+        const double2 c0 = attr[t * 2], c1 = attr[t * 2 + 1];
+        if (k & 1u) { oattr[o0 * 2] = c0; oattr[o0 * 2 + 1] = c1; }
+        if (k & 2u) { oattr[o1 * 2] = c0; oattr[o1 * 2 + 1] = c1; }
+    } else {
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            const double2 w0 = attr[t * (3 * H) + j], w1 = attr[t * (3 * H) + H + j], w2 = attr[t * (3 * H) + 2 * H + j];
+            const double2 e0 = make_double2(clip_attr(a0, b0, q0.t, w0.x, w1.x, w2.x),
+                                            clip_attr(a0, b0, q0.t, w0.y, w1.y, w2.y));
+            const double2 e2 = make_double2(clip_attr(a2, b2, q2.t, w0.x, w1.x, w2.x),
+                                            clip_attr(a2, b2, q2.t, w0.y, w1.y, w2.y));
+            if (k & 1u) {
+                double2* q = oattr + o0 * (3 * H);
+                q[j] = e0;
+                q[H + j] = make_double2(clip_attr(a1, b1, t1, w0.x, w1.x, w2.x), clip_attr(a1, b1, t1, w0.y, w1.y, w2.y));
+                q[2 * H + j] = e2;
+            }
+            if (k & 2u) {
+                double2* q = oattr + o1 * (3 * H);
+                q[j] = e0;
+                q[H + j] = e2;
+                q[2 * H + j] = make_double2(clip_attr(a3, b3, t3, w0.x, w1.x, w2.x), clip_attr(a3, b3, t3, w0.y, w1.y, w2.y));
+            }
+        }
+    }
 }
 
 unsigned blocks_for(i64 threads) { return (unsigned)((threads + 255) / 256); }
@@ -188,6 +410,100 @@ bool assemble(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out) {
     return true;
 }
 
+// What a mesh draw hands to the rasters: n triangles and their attributes.
+struct DrawSoup { const f64* xy; const f64* z; const f64* attr; i64 n; };
+
+inline bool clip_stage_on(const RenderContext* ctx) { return ctx->meshNear > 0 || ctx->meshCull != 0; }
+
+// The clip stage of `m` under `matrix` and the context's near plane and cull
+// mode (one of them on; m->n > 0): clip coordinates, count, scan, then -- after
+// the total n_out has been read back, the one wait of such a draw -- the emit
+// pass into ctx's mesh staging, sized to n_out.  out->n == 0: nothing is left
+// to draw (no staging is touched).  False: scratch could not be grown (latched).
+bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, DrawSoup* out) {
+    if (m->n > (i64)INT_MAX) return fail("mesh clip stage", "more than 2^31 - 1 triangles");
+    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
+    TriScratch& sc = ctx->tri;
+    const size_t nv = (size_t)m->nv, n = (size_t)m->n;
+    if (!sc.mclip.ensure(nv * 4) || !sc.mscan.ensure(n * 3)) return false;
+    u32* keep = sc.mscan;
+    u32* cnt = keep + n;
+    u32* off = cnt + n;
+    size_t need = 0;
+    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, cnt, off, (int)m->n, ctx->stream));
+    if (!grow_temp(sc, need > 0 ? need : 1)) return false;
+    if (!sc.h_total) NR_CHECK(hipHostMalloc((void**)&sc.h_total, 4 * sizeof(u64)));
+    if (!sc.h_total) return fail("mesh clip stage", "hipHostMalloc failed");
+    Mat4 M = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
+    if (matrix)
+        for (int k = 0; k < 16; ++k) M.m[k] = matrix[k];
+    const f64 wNear = ctx->meshNear;
+    const double2* clip = reinterpret_cast<const double2*>(sc.mclip.p);
+    hipEvent_t a, b;
+    nr_timing_begin(ctx, NRK_MESH_CLIP_VERTEX, &a, &b);
+    hipLaunchKernelGGL(k_mesh_clip_vertex, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv, M,
+                       reinterpret_cast<double2*>(sc.mclip.p));
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_CLIP_VERTEX, a, b);
+    nr_timing_begin(ctx, NRK_MESH_CLIP_COUNT, &a, &b);
+    hipLaunchKernelGGL(k_mesh_clip_count, dim3(blocks_for(m->n)), dim3(256), 0, ctx->stream, m->idx, m->n, clip, wNear,
+                       ctx->meshCull, keep, cnt);
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_CLIP_COUNT, a, b);
+    nr_timing_begin(ctx, NRK_MESH_CLIP_SCAN, &a, &b);
+    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(sc.temp, need, cnt, off, (int)m->n, ctx->stream));
+    nr_timing_end(ctx, NRK_MESH_CLIP_SCAN, a, b);
+    // n_out = the last offset + the last count (at most 2n < 2^32): the sync point of a clipped or culled draw
+    u32* h = reinterpret_cast<u32*>(&sc.h_total[0]);
+    NR_CHECK(hipMemcpyAsync(&h[0], off + (n - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    NR_CHECK(hipMemcpyAsync(&h[1], cnt + (n - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("mesh clip stage", "the count could not be read back");
+    const size_t nout = (size_t)h[0] + (size_t)h[1];
+    out->xy = out->z = out->attr = nullptr;
+    out->n = (i64)nout;
+    if (nout == 0) return true;
+    if (nout > 2 * n) return fail("mesh clip stage", "inconsistent triangle count");   // (never: the counts are 0, 1 or 2)
+    const size_t stride = (size_t)nrtri::attr_stride(m->mode);
+    const size_t zn = (nout * 3 + 1) & ~(size_t)1;   // keeps the attributes 16-byte aligned
+    if (!sc.mstage.ensure(nout * 6 + zn + nout * stride)) return false;
+    f64* xy = sc.mstage;
+    f64* z = xy + nout * 6;
+    f64* attr = z + zn;
+    nr_timing_begin(ctx, NRK_MESH_CLIP_EMIT, &a, &b);
+    const dim3 grid(blocks_for(m->n)), block(256);
+    const double2* mattr = reinterpret_cast<const double2*>(m->attr);
+    double2* xy2 = reinterpret_cast<double2*>(xy);
+    double2* attr2 = reinterpret_cast<double2*>(attr);
+    if (m->mode == nrtri::ATTR_GOURAUD)
+        hipLaunchKernelGGL(k_mesh_clip_emit<2>, grid, block, 0, ctx->stream, m->idx, m->n, clip, mattr, wNear, keep, off,
+                           xy2, z, attr2);
+    else if (m->mode == nrtri::ATTR_TEX)
+        hipLaunchKernelGGL(k_mesh_clip_emit<1>, grid, block, 0, ctx->stream, m->idx, m->n, clip, mattr, wNear, keep, off,
+                           xy2, z, attr2);
+    else
+        hipLaunchKernelGGL(k_mesh_clip_emit<0>, grid, block, 0, ctx->stream, m->idx, m->n, clip, mattr, wNear, keep, off,
+                           xy2, z, attr2);
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_CLIP_EMIT, a, b);
+    out->xy = xy;
+    out->z = z;
+    out->attr = attr;
+    return true;
+}
+
+// The soup a draw of `m` rasterises under the context's clip state: the unclipped
+// path's (vertex stage + assembly, the mesh's own attributes) when it is off.
+bool draw_soup(RenderContext* ctx, const Mesh* m, const f64* matrix, DrawSoup* out) {
+    if (clip_stage_on(ctx)) return assemble_clipped(ctx, m, matrix, out);
+    Soup s;
+    if (!assemble(ctx, m, matrix, &s)) return false;
+    out->xy = s.xy;
+    out->z = s.z;
+    out->attr = m->attr;
+    out->n = m->n;
+    return true;
+}
+
 // The checks every mesh draw shares (in the style of check_texture).
 bool check_mesh(RenderContext* ctx, const Mesh* m, bool textured, const char* what) {
     if (!m) return fail(what, "NULL mesh");
@@ -268,10 +584,13 @@ void DrawMesh(RenderContext* ctx, Mesh* m, const f64* matrix16) {
     NR_CHECK(hipSetDevice(ctx->device));
     if (!check_mesh(ctx, m, false, "DrawMesh")) return;
     if (ctx->recording) nr_settle(ctx);   // recorded draws come first
+    ctx->meshLastCount = 0;
     if (m->n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
-    Soup s;
-    if (!assemble(ctx, m, matrix16, &s)) return;
-    nrtri::draw(ctx, s.xy, s.z, m->attr, m->n, m->mode, m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED, nullptr,
+    DrawSoup s;
+    if (!draw_soup(ctx, m, matrix16, &s)) return;
+    ctx->meshLastCount = s.n;
+    if (s.n <= 0) return;   // (clipped or culled away)
+    nrtri::draw(ctx, s.xy, s.z, s.attr, s.n, m->mode, m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED, nullptr,
                 false);
 }
 
@@ -281,10 +600,13 @@ void DrawTexturedMesh(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matr
     if (!check_mesh(ctx, m, true, "DrawTexturedMesh")) return;
     if (ctx->recording) nr_settle(ctx);   // recorded draws come first
     if (!nrtri::check_texture(ctx, tex, "DrawTexturedMesh")) return;
+    ctx->meshLastCount = 0;
     if (m->n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
-    Soup s;
-    if (!assemble(ctx, m, matrix16, &s)) return;
-    nrtri::draw_textured(ctx, tex, s.xy, s.z, m->attr, m->n, nullptr, false);
+    DrawSoup s;
+    if (!draw_soup(ctx, m, matrix16, &s)) return;
+    ctx->meshLastCount = s.n;
+    if (s.n <= 0) return;
+    nrtri::draw_textured(ctx, tex, s.xy, s.z, s.attr, s.n, nullptr, false);
 }
 
 // New: the vertex stage and the assembly alone -- exactly the kernels DrawMesh
@@ -300,6 +622,60 @@ bool AssembleMesh(RenderContext* ctx, Mesh* m, const f64* matrix16, f64* xy_out,
     if (!assemble(ctx, m, matrix16, &s)) return false;
     NR_CHECK(hipMemcpyAsync(xy_out, s.xy, (size_t)m->n * 6 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
     NR_CHECK(hipMemcpyAsync(z_out, s.z, (size_t)m->n * 3 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
+    NR_CHECK(hipStreamSynchronize(ctx->stream));
+    return true;
+}
+
+// New: the near plane of this context's mesh draws: 0 (the default) is off, w > 0
+// clips every mesh triangle against cw = w (DESIGN.md §3 "Clip stage").  Per
+// context; not part of the save / restore stack, not recorded.  A negative or
+// non-finite w latches an error and leaves the state unchanged.
+bool SetMeshNearPlane(RenderContext* ctx, f64 wNear) {
+    if (!(wNear >= 0) || !std::isfinite(wNear)) return fail("SetMeshNearPlane", "the plane must be finite and >= 0");
+    ctx->meshNear = wNear;
+    return true;
+}
+f64 GetMeshNearPlane(RenderContext* ctx) { return ctx->meshNear; }
+
+// New: back-face culling of this context's mesh draws by the sign of
+// area2 = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0) of each output triangle,
+// before the context's 2D transform: 0 none (the default), 1 drops area2 > 0,
+// 2 drops area2 < 0.  Another mode latches an error, the state unchanged.
+bool SetMeshCull(RenderContext* ctx, i64 mode) {
+    if (mode < 0 || mode > 2) return fail("SetMeshCull", "mode must be 0 (none), 1 (drop area2 > 0) or 2 (drop area2 < 0)");
+    ctx->meshCull = (int)mode;
+    return true;
+}
+i64 GetMeshCull(RenderContext* ctx) { return ctx->meshCull; }
+
+// New: the triangles the context's last mesh draw handed to the rasters: n_out of
+// the clip stage, or the mesh's n when the stage was off.
+i64 GetMeshLastTriangleCount(RenderContext* ctx) { return ctx->meshLastCount; }
+
+// New: the soup a mesh draw rasterises under the context's near plane and cull
+// mode -- the draw's own kernels -- copied to the host: *n_out = the full count,
+// the first min(cap, *n_out) triangles in xy_out (x6), z_out (x3) and attr_out
+// (x12 Gouraud, x4 flat, x6 textured).  A sync point; either mesh kind.
+bool AssembleMeshClipped(RenderContext* ctx, Mesh* m, const f64* matrix16, i64 cap, f64* xy_out, f64* z_out,
+                         f64* attr_out, i64* n_out) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    if (!m) return fail("AssembleMeshClipped", "NULL mesh");
+    if (m->device != ctx->device) return fail("AssembleMeshClipped", "mesh on another device");
+    if (!n_out) return fail("AssembleMeshClipped", "NULL output");
+    *n_out = 0;
+    if (cap < 0) return fail("AssembleMeshClipped", "negative capacity");
+    if (cap > 0 && (!xy_out || !z_out || !attr_out)) return fail("AssembleMeshClipped", "NULL output");
+    if (m->n <= 0) return true;
+    DrawSoup s;
+    if (!draw_soup(ctx, m, matrix16, &s)) return false;
+    *n_out = s.n;
+    const size_t k = (size_t)(s.n < cap ? s.n : cap);
+    if (k > 0) {
+        const size_t stride = (size_t)nrtri::attr_stride(m->mode);
+        NR_CHECK(hipMemcpyAsync(xy_out, s.xy, k * 6 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
+        NR_CHECK(hipMemcpyAsync(z_out, s.z, k * 3 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
+        NR_CHECK(hipMemcpyAsync(attr_out, s.attr, k * stride * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
+    }
     NR_CHECK(hipStreamSynchronize(ctx->stream));
     return true;
 }

@@ -354,6 +354,52 @@ class RenderContext:
             raise RuntimeError("AssembleMesh failed: " + _lib.last_error())
         return xy, z
 
+    # mesh near plane and back-face cull: per context, not saved / restored,
+    # not recorded; with both off draw_mesh is unchanged
+    def set_mesh_near_plane(self, w: float):
+        """Clips this context's mesh draws against the plane cw = w (0: off).
+        A negative or non-finite w raises (the error stays latched) and
+        leaves the state unchanged."""
+        if not lib.SetMeshNearPlane(self._ptr, float(w)):
+            raise RuntimeError("SetMeshNearPlane failed: " + _lib.last_error())
+
+    def get_mesh_near_plane(self) -> float:
+        return lib.GetMeshNearPlane(self._ptr)
+
+    def set_mesh_cull(self, mode: int):
+        """Back-face culling of this context's mesh draws by the sign of
+        area2 = (x1-x0)*(y2-y0) - (x2-x0)*(y1-y0) before the 2D transform:
+        0 none, 1 drops area2 > 0, 2 drops area2 < 0."""
+        if not lib.SetMeshCull(self._ptr, int(mode)):
+            raise RuntimeError("SetMeshCull failed: " + _lib.last_error())
+
+    def get_mesh_cull(self) -> int:
+        return lib.GetMeshCull(self._ptr)
+
+    @property
+    def mesh_last_triangle_count(self) -> int:
+        """Triangles the last draw_mesh on this context rasterised (after the
+        clip and the cull; the mesh's own count when both are off)."""
+        return lib.GetMeshLastTriangleCount(self._ptr)
+
+    def assemble_mesh_clipped(self, mesh: "Mesh", matrix=None):
+        """(xy (n_out, 6), z (n_out, 3), attr (n_out, 12 Gouraud / 4 flat / 6
+        textured)): the soup draw_mesh would rasterise under `matrix` and this
+        context's near plane and cull mode -- the draw's own kernels (a sync
+        point)."""
+        m, mp = self._matrix16(matrix)
+        cap = 2 * mesh.triangle_count
+        stride = 6 if mesh.textured else (12 if mesh.gouraud else 4)
+        xy = np.empty((cap, 6), dtype=np.float64)
+        z = np.empty((cap, 3), dtype=np.float64)
+        attr = np.empty((cap, stride), dtype=np.float64)
+        nout = ctypes.c_long(0)
+        if not lib.AssembleMeshClipped(self._ptr, mesh._ptr, mp, cap, _f64_ptr(xy), _f64_ptr(z), _f64_ptr(attr),
+                                       ctypes.byref(nout)):
+            raise RuntimeError("AssembleMeshClipped failed: " + _lib.last_error())
+        k = nout.value
+        return xy[:k].copy(), z[:k].copy(), attr[:k].copy()
+
     # ---- additions: sync, device interop, measurement ------------------
     def flush(self):
         lib.Flush(self._ptr)
