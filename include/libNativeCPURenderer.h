@@ -210,6 +210,14 @@ i64 GetReusedBatchCount(RenderContext* ctx);                             /* NEW 
                                                                             from a kept pair list (no binning) */
 void SetListReuse(RenderContext* ctx, i64 mode);                         /* NEW: pair-list reuse of an unchanged repeat draw
                                                                             0 auto (on), 2 off (every warm batch bins) */
+i64 GetPrunedBatchCount(RenderContext* ctx);                             /* NEW (testing): of the reused batches, rasterised
+                                                                            from the visible list (no hidden triangles) */
+i64 GetVisiblePairCount(RenderContext* ctx);                             /* NEW (testing): pairs kept in the current visible
+                                                                            list, 0 when there is none */
+void SetVisiblePruning(RenderContext* ctx, i64 mode);                    /* NEW: visible list of an unchanged repeat draw
+                                                                            0 auto (on), 2 off (reuse the full list) */
+bool GetScheduleTotals(RenderContext* ctx, i64* out4);                   /* NEW (testing): the warm schedule's pairs, work
+                                                                            items, split-tile slices, dense tiles; false: none */
 void SetWarmFaultInjection(RenderContext* ctx, i64 mode);                /* NEW (testing): fault in the next warm batch
                                  1 range overflow, 2 withheld token, 3 dropped pairs, 4 binning delayed past the
                                  raster's token wait (the frame must stay exact) */

@@ -106,6 +106,10 @@ DEVICE_ABI = {
     "GetLooseBatchCount": (L, (P,)),
     "GetReusedBatchCount": (L, (P,)),
     "SetListReuse": (None, (P, L)),
+    "GetPrunedBatchCount": (L, (P,)),
+    "GetVisiblePairCount": (L, (P,)),
+    "SetVisiblePruning": (None, (P, L)),
+    "GetScheduleTotals": (B, (P, P)),
     "ExecuteCommands": (L, (P, P, L, P, L)),
     "SetWarmFaultInjection": (None, (P, L)),
     "GetWarmFailureCount": (L, (P,)),

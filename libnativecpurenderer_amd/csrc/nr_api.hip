@@ -417,7 +417,8 @@ void ResizeRenderContext(RenderContext* ctx, i64 width, i64 height) {
     }
     ctx->pendColor = ctx->pendDepth = false;
     ctx->tileColor = ctx->tileDepth = false;
-    ctx->tri.sched.listSet = -1;   // (list reuse: a resized context bins again)
+    ctx->tri.sched.listSet = -1;   // (list reuse: a resized context bins again, and marks its winners again)
+    ctx->tri.sched.drop_visible();
     i64 n = GetBufferSize(ctx);
     NR_CHECK(hipMalloc(&ctx->buffer, (size_t)(n > 0 ? n : 1) * sizeof(f64)));
     NR_CHECK(hipMemsetAsync(ctx->buffer, 0, (size_t)(n > 0 ? n : 1) * sizeof(f64), ctx->stream));

@@ -192,8 +192,23 @@ struct TriScratch {
         int listSet = -1;
         u32 listTag = 0, listMult = 0;                   // its WarmCheck tag and cursor multiple (epoch + 1)
         bool listGated = false;                          // binned beside the raster: its plan words are the set's gplan
+        // visible list: the kept pair list without the triangles that won no
+        // pixel on the marking frame (a reused batch whose k_vis also set the
+        // winners' bits in vmask), pruned once per generation (k_prune_list) --
+        // a copy at the same offsets, so it outlives the binning set's reuse;
+        // reused batches of the capturing depth mode rasterise from it
+        DevArray<u32> vlist;                             // pruned pairs, tile t's vcnt[t] of them from off[t]
+        DevArray<u32> vcnt;                              // ntiles kept counts | 2 check words (always 0) | the kept total
+        DevArray<u32> vmask;                             // one bit per triangle: it won a pixel
+        int visState = 0;                                // 0 none, 1 marking frame enqueued, 2 pruned
+        int visZ = 0;                                    // depth mode (k_vis ZMODE) of the marking frame
+        int markSet = -1; u32 markTag = 0;               // the list the marking frame read (pruned from the same one)
+        hipEvent_t evMark = nullptr;                     // the marking frame is done (main stream)
+        void drop_visible() { visState = 0; }
         void release() {
             off.release(); items.release(); off2.release();
+            vlist.release(); vcnt.release(); vmask.release();
+            if (evMark) NR_CHECK(hipEventDestroy(evMark));
             if (dplan) NR_CHECK(hipFree(dplan));
             if (blocks) NR_CHECK(hipFree(blocks));
             if (ready) NR_CHECK(hipEventDestroy(ready));
@@ -204,6 +219,8 @@ struct TriScratch {
     u64 looseBatches = 0;                   // of those, into the loose ranges (GetLooseBatchCount)
     u64 reusedBatches = 0;                  // of the warm ones, rasterised from a kept pair list (GetReusedBatchCount)
     int reuseMode = 0;                      // list reuse: 0 automatic (on), 2 off (SetListReuse)
+    u64 prunedBatches = 0;                  // of the reused ones, rasterised from the visible list (GetPrunedBatchCount)
+    int pruneMode = 0;                      // visible list: 0 automatic (on), 2 off (SetVisiblePruning)
     std::vector<u64> looseBanned;           // buffers whose loose binning overflowed a tile: not binned loose again
     // warm-batch checks (k_vis WarmCheck): host-mapped word a raster sets when
     // a warm batch failed them (1 binning check, 2 token timeout), read by

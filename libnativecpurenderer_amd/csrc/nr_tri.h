@@ -382,6 +382,7 @@ struct FrameParams {
     u64* tstamp;      // non-null (kernel timing): {~first start, last end} of the raster on the device's
                       // 100 MHz clock (raster_stamp_begin / _end, nr_timing_stamp)
     TexView tex;      // ATTR_TEX batches: the texture (a snapshot when it aliases fb)
+    u32* winMask;     // a marking frame (k_vis MARK instances only): bit t is set when triangle t wins a pixel
 };
 
 // Texel of a fragment's interpolated (u, v), as an offset in doubles: the
@@ -555,6 +556,7 @@ void launch_ordered_binned(const FrameParams& fp, const u32* list, const u32* of
 void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, bool ordered = false,
                const TexView* tex = nullptr);
 void settle(RenderContext* ctx);
+i64 visible_pairs(RenderContext* ctx);   // pairs kept in the schedule's visible list (0: none)
 
 // the batch entry points behind every triangle draw call (nr_tri.hip), shared with the mesh front end
 // (nr_mesh.hip): draw picks the raster; draw_textured resolves the texture first (check_texture: its

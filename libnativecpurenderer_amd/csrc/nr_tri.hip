@@ -60,6 +60,7 @@ FrameParams frame_params(RenderContext* ctx, const TriSrc& src, const TexView* t
     fp.tileEpoch = 0;
     fp.tstamp = nullptr;
     fp.tex = tex ? *tex : tex_view(nullptr, 2, 2, false);
+    fp.winMask = nullptr;
     if (ctx->countFragments) {
         if (!sc.d_frag) NR_CHECK(hipMalloc(&sc.d_frag, sizeof(u64)));
         NR_CHECK(hipMemsetAsync(sc.d_frag, 0, sizeof(u64), ctx->stream));
@@ -484,7 +485,10 @@ i64 GetFragmentCount(RenderContext* ctx) { return (i64)ctx->fragTotal; }
 // the kept tile ranges), 0 automatic (NR_WARM), 1 on, 2 off.
 void SetWarmBinning(RenderContext* ctx, i64 mode) {
     ctx->tri.warmMode = (int)(mode >= 0 && mode <= 2 ? mode : 0);
-    if (ctx->tri.warmMode == 2) ctx->tri.sched.listSet = -1;   // (no kept pair list outlives the switch)
+    if (ctx->tri.warmMode == 2) {   // (no kept pair list, and no visible list, outlives the switch)
+        ctx->tri.sched.listSet = -1;
+        ctx->tri.sched.drop_visible();
+    }
 }
 // New (testing): number of batches of this context binned warm so far.
 i64 GetWarmBatchCount(RenderContext* ctx) { return (i64)ctx->tri.warmBatches; }
@@ -496,6 +500,29 @@ i64 GetReusedBatchCount(RenderContext* ctx) { return (i64)ctx->tri.reusedBatches
 // New (testing / A-B measurement): list reuse, 0 automatic (on), 2 off (every
 // warm batch bins, the cursors running on from epoch to epoch).
 void SetListReuse(RenderContext* ctx, i64 mode) { ctx->tri.reuseMode = mode == 2 ? 2 : 0; }
+// New (testing): of the reused batches, those rasterised from the schedule's
+// visible list (the kept pair list without the triangles that win no pixel).
+i64 GetPrunedBatchCount(RenderContext* ctx) { return (i64)ctx->tri.prunedBatches; }
+// New (testing): pairs kept in the current visible list, 0 when there is none.
+i64 GetVisiblePairCount(RenderContext* ctx) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    return nrtri::visible_pairs(ctx);
+}
+// New (testing / A-B measurement): the visible list, 0 automatic (on), 2 off
+// (reused batches rasterise from the full list; a list already pruned is kept
+// and used again after a switch back to 0).
+void SetVisiblePruning(RenderContext* ctx, i64 mode) { ctx->tri.pruneMode = mode == 2 ? 2 : 0; }
+// New (testing): totals of the context's warm schedule -- out[0..3] = (tile,
+// triangle) pairs, k_vis work items, slices of split tiles, dense tiles;
+// false (and zeros) when it has none.
+bool GetScheduleTotals(RenderContext* ctx, i64* out) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    nrtri::settle(ctx);
+    const auto& S = ctx->tri.sched;
+    const BatchTotals t = S.valid ? S.totals : BatchTotals{};
+    out[0] = t.pairs; out[1] = t.items; out[2] = t.split; out[3] = t.heavy;
+    return S.valid;
+}
 // New (testing): a fault in the next warm batch -- 1 its binning finds its
 // tiles over their ranges, 2 (a batch binned beside the raster) its token is
 // withheld (the raster's wait times out after 1 s), 3 it drops a workgroup's
@@ -517,7 +544,10 @@ i64 GetLastRasterPath(RenderContext* ctx) { return ctx->lastPath; }
 // exercise the overflow re-run of nr_settle.
 void SetPairCapacityOverride(RenderContext* ctx, i64 pairs) {
     ctx->tri.capOverride = (u64)(pairs > 0 ? pairs : 0);
-    if (ctx->tri.capOverride) ctx->tri.sched.listSet = -1;
+    if (ctx->tri.capOverride) {
+        ctx->tri.sched.listSet = -1;
+        ctx->tri.sched.drop_visible();
+    }
 }
 
 // New (testing / A-B measurement): force the ordered raster for every batch.

@@ -809,7 +809,14 @@ __device__ __forceinline__ int staged_record(const u32* ht, const unsigned short
 // global loads: one latency round), written over the keys.  Pass 3: colour,
 // ApplyPixel, framebuffer (+ u8 frame) written once.  A winner past the RT
 // staged records (or not placed within MAXPROBE probes) loads its own record.
-template <int ZMODE, int MODE, int NT, int HS>
+// MARK (a marking frame): every pixel's winner also gets its bit in
+// fp.winMask set -- here, where a winner id is read from the tile's final keys,
+// so staged, overflowed and directly loaded winners are all covered (the flat
+// loop per pixel; pass 1 once per distinct winner and per unstaged pixel).
+__device__ __forceinline__ void mark_winner(const FrameParams& fp, u32 id) {
+    __hip_atomic_fetch_or(&fp.winMask[(id - 1) >> 5], 1u << ((id - 1) & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <int ZMODE, int MODE, int NT, int HS, bool MARK = false>
 __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0, int wlim, int hlim,
                                            const u64* key, unsigned char* lds, u32& nU) {
     using St = ShadeStage<MODE, HS>;
@@ -836,6 +843,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                 id[j] = (u32)kv;
                 store_depth<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, kv);
                 if (id[j]) {
+                    if constexpr (MARK) mark_winner(fp, id[j]);
                     const f64* q = fp.src.rgba() + ((i64)id[j] - 1) * 4;
                     const double2 rg = *reinterpret_cast<const double2*>(q);
                     c[j][0] = rg.x; c[j][1] = rg.y; c[j][2] = q[2];
@@ -887,7 +895,10 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
             if (q == k) ids[q] = id;   // static register index
         store_depth<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, kv);
         if (!id) continue;
+        // (MARK: once per distinct winner -- by the thread that enters it in the
+        // hash table -- and per pixel whose winner is not in the table)
         if (OVF_Q && __hip_atomic_load(&nU, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= (u32)St::RT) {
+            if constexpr (MARK) mark_winner(fp, id);
             ovf |= 1u << k;
             continue;
         }
@@ -899,6 +910,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
             if (cur == 0) {
                 const u32 old = atomicCAS(&ht[h], 0u, id);
                 if (old == 0) {
+                    if constexpr (MARK) mark_winner(fp, id);
                     const u32 d = atomicAdd(&nU, 1u);
                     hidx[h] = (unsigned short)(d < (u32)St::RT ? d : St::RT);
                     if (d < (u32)St::RT) didx[d] = id;
@@ -907,6 +919,9 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                 }
                 if (old == id) { placed = true; break; }
             }
+        }
+        if constexpr (MARK) {
+            if (!placed) mark_winner(fp, id);
         }
         if (OVF_Q && !placed) ovf |= 1u << k;
     }
@@ -1170,7 +1185,8 @@ __device__ __forceinline__ void warm_report(const WarmCheck& wc, u32 why, u32 a,
     __hip_atomic_store(&wc.hfail[0], why, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-template <int ZMODE, bool COUNT, int MODE, bool FLAT, int NT>   // ZMODE 0: no test, 1: LESS+write, 2: LESS no write
+// MARK: a marking frame's instance (shade_tile MARK; the visible list, warm_enqueue).
+template <int ZMODE, bool COUNT, int MODE, bool FLAT, int NT, bool MARK = false>   // ZMODE 0: no test, 1: LESS+write, 2: LESS no write
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) void k_vis(const FrameParams fp, const uint4* __restrict__ items,
                                              const u32* __restrict__ list,
                                              u64* __restrict__ kslot, u32* __restrict__ done,
@@ -1518,7 +1534,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         NR_PROBE_STAMP(2);
         if (!multi) {   // the whole list was in this slice: shade now
             if (rlo < rcap)
-                shade_tile<ZMODE, MODE, NT, HS>(fp, x0, y0 + rlo, wlim, rcap - rlo, key + rlo * KS, lds, nU);
+                shade_tile<ZMODE, MODE, NT, HS, MARK>(fp, x0, y0 + rlo, wlim, rcap - rlo, key + rlo * KS, lds, nU);
             continue;
         }
         // split tile (a dense tile's slice): the slice's keys go to its own
@@ -1587,7 +1603,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         }
         __syncthreads();
         NR_PROBE_STAMP(3);
-        shade_tile<ZMODE, MODE, NT, HS>(fp, x0, y0, wlim, hlim, key, lds, nU);
+        shade_tile<ZMODE, MODE, NT, HS, MARK>(fp, x0, y0, wlim, hlim, key, lds, nU);
     }   // work items
 #if NR_PROBE
     if (tid == 0 && pr_item != ~0u) probe_item(pr_item, pr_d, pr_t0, __builtin_amdgcn_s_memrealtime(), NT);
@@ -1643,6 +1659,20 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& 
 #define NR_VIS(CO, NTT, ...)                                                                                       \
     hipExtLaunchKernelGGL((k_vis<Z, __VA_ARGS__>), dim3(grid), dim3(NTT), 0, s, start, stop, 0, fp, va.items,    \
                           va.list, sc.kslot.p, sc.fdone.p, va.plan, wc)
+    // a marking frame (fp.winMask; never a counting batch, never LESS without write)
+    if constexpr (!C && Z != 2) {
+        if (fp.winMask) {
+            if (wide) {
+                if (coop) NR_VIS(1, 2 * VWG, false, G, true, 2 * VWG, true);
+                else NR_VIS(0, 2 * VWG, false, G, false, 2 * VWG, true);
+            } else if (coop) {
+                NR_VIS(1, VWG, false, G, true, VWG, true);
+            } else {
+                NR_VIS(0, VWG, false, G, false, VWG, true);
+            }
+            return;
+        }
+    }
     if (wide) {
         if (coop) NR_VIS(1, 2 * VWG, false, G, true, 2 * VWG);
         else NR_VIS(0, 2 * VWG, false, G, false, 2 * VWG);
@@ -2034,6 +2064,7 @@ static void sched_capture(RenderContext* ctx, TriScratch::FreeSet& F, const BinK
     main_after_side_binning(ctx);   // (a late warm binning may still read S.off)
     S.valid = false;
     S.listSet = -1;   // (a new generation: no list of its own yet)
+    S.drop_visible();
     const size_t ineed = std::max<size_t>(t.items, 1);
     if (S.off.needs((size_t)ntiles + 1) || S.items.needs(ineed) || !S.dplan) {
         NR_CHECK(hipStreamSynchronize(sa));   // a queued warm batch may still read the old arrays
@@ -2125,6 +2156,7 @@ static void warm_poll(RenderContext* ctx) {
     }
     if (f != 2 && sc.sched.valid) sc.warmBanned.push_back(sc.sched.tbUid);
     sc.sched.valid = false;
+    sc.sched.drop_visible();
     if (f == 2)
         snprintf(msg, sizeof msg, "triangle batch: a raster's wait for its warm binning timed out; the batch was "
                                   "rasterised from all its triangles (under serialised kernel dispatch -- a "
@@ -2228,6 +2260,145 @@ static void warm_blocks(RenderContext* ctx, const BinParams& bp, const TriangleB
     S.blocksGen = S.gen;
 }
 
+// ---- visible list -----------------------------------------------------------
+// Under list reuse the buffer, the key and the pair list are those of the frame
+// before, so the triangles that can win a pixel are too.  One reused batch of a
+// schedule generation is the marking frame: its k_vis (a MARK instance) sets
+// bit t of S.vmask for every triangle t that wins a pixel.  k_prune_list then
+// copies the kept list without the unmarked triangles -- same offsets, each
+// tile's order kept -- into S.vlist, with the tiles' kept counts in S.vcnt, and
+// later reused batches of that depth mode rasterise from the copy with k_vis
+// unchanged: the counts are the cursors of a WarmCheck in the loose format, so
+// each item slices its tile's actual count afresh.
+// Exact, because the raster is a per-pixel min / max over keys (zq << 32) | id
+// and a triangle that wins no pixel changes none ("Visible list"):
+//   LESS + write: marked only on a frame whose depth is a pending clear to
+//     0xFFFFFFFF; an unmarked triangle's key is above a kept one's at every
+//     pixel it covers, whatever the depth buffer holds -- valid for every later
+//     LESS + write draw;
+//   no test: the highest covering id wins, whatever the depth -- valid for
+//     that mode;
+//   LESS without write: never pruned (the passing set depends on the depth
+//     buffer's contents); such draws, and any draw in a mode other than the
+//     capturing one, use the full list, which stays where it is.
+// The list is dropped with the schedule generation (sched_capture, a failed
+// check, a resize, SetWarmBinning(2), a capacity override).
+static bool visible_capture_ok(const FrameParams& fp, int zm) {
+    if (fp.fragCounter || fp.src.n <= 0) return false;
+    if (zm == 1) return fp.pendDepth && fp.pendDepthValue == 0xFFFFFFFFu;
+    return zm == 0;
+}
+
+// One workgroup per work item; the first item of each tile (slice 0) prunes
+// the tile's pairs [off[t], off[t + 1]): those whose triangle is marked go, in
+// their order, to vlist from off[t], and their number to vcnt[t].  A split tile
+// (nsl slices) keeps at least nsl pairs -- k_vis cuts the count into nsl
+// slices and none may be empty (its chunk length divides) -- padded with the
+// tile's first unmarked pairs: a triangle more never changes the frame.  A
+// split tile holds more pairs than slices, so the padding is always there.
+__global__ __launch_bounds__(256) void k_prune_list(const uint4* __restrict__ items, const u32* __restrict__ off,
+                                                    const u32* __restrict__ list, const u32* __restrict__ mask, u32 n,
+                                                    u32* __restrict__ vlist, u32* __restrict__ vcnt,
+                                                    u32* __restrict__ total) {
+    __shared__ u32 wsum[4];
+    const uint4 d = items[blockIdx.x];
+    if (d.w >> 16) return;
+    const u32 tile = d.x, nsl = d.w & 0xFFFFu;
+    const u32 beg = off[tile], end = off[tile + 1];
+    if (beg == end) return;   // (vcnt is zeroed before the launch)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    auto marked = [&](u32 t) -> u32 { return t < n ? (mask[t >> 5] >> (t & 31u)) & 1u : 0u; };
+    u32 pad = 0;   // unmarked pairs a split tile keeps
+    if (nsl > 1) {
+        u32 m = 0;
+        for (u32 i = beg + tid; i < end; i += 256) m += marked(list[i]);
+        m = wave_scan(m, lane);
+        if (lane == 63) wsum[w] = m;
+        __syncthreads();
+        const u32 tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+        pad = tot < nsl ? nsl - tot : 0u;
+    }
+    // a pair's place among the kept ones: the marked pairs before it + the
+    // padding pairs before it (the first `pad` unmarked ones); marked and
+    // unmarked counts of a 256-pair round are scanned together, 16 bits each
+    u32 km = 0, ku = 0;   // marked / unmarked pairs of the rounds so far
+    for (u32 b = beg; b < end; b += 256) {
+        const u32 i = b + tid;
+        const bool in = i < end;
+        const u32 t = in ? list[i] : 0u;
+        const u32 mk = in ? marked(t) : 0u;
+        const u32 v = mk | ((in && !mk ? 1u : 0u) << 16);
+        const u32 inc = wave_scan(v, lane);
+        if (lane == 63) wsum[w] = inc;
+        __syncthreads();
+        u32 ex = inc - v, tot = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < w) ex += wsum[k];
+            tot += wsum[k];
+        }
+        __syncthreads();
+        const u32 ub = ku + (ex >> 16);
+        if (in && (mk || ub < pad)) vlist[beg + km + (ex & 0xFFFFu) + min(ub, pad)] = t;
+        km += tot & 0xFFFFu;
+        ku += tot >> 16;
+    }
+    if (tid == 0) {
+        const u32 c = km + min(ku, pad);
+        vcnt[tile] = c;
+        atomicAdd(total, c);
+    }
+}
+
+// The marking frame's set-up: room for the mask, the pruned list and the
+// counts (a regrow waits for the main stream: a queued batch of an earlier
+// generation may still read them; first use or a larger schedule), the mask
+// zeroed on the main stream, and the batch's snapshot pointed at it.
+static void visible_mark_begin(RenderContext* ctx, FrameParams& fp, int ntiles) {
+    auto& S = ctx->tri.sched;
+    const size_t words = ((size_t)fp.src.n + 31) / 32, pairs = std::max<size_t>(S.totals.pairs, 1);
+    if (S.vmask.needs(words) || S.vlist.needs(pairs) || S.vcnt.needs((size_t)ntiles + 3)) {
+        NR_CHECK(hipStreamSynchronize(ctx->stream));
+        if (!S.vmask.ensure(words) || !S.vlist.ensure(pairs) || !S.vcnt.ensure((size_t)ntiles + 3)) return;
+    }
+    NR_CHECK(hipMemsetAsync(S.vmask, 0, words * sizeof(u32), ctx->stream));
+    fp.winMask = S.vmask;
+}
+
+// After a marking frame: prune once the host has seen, without waiting, that
+// the marking frame -- and with it, in stream order, the list's binning frame,
+// whose raster checked the binning -- is done, and that no check failed
+// (hfail: a failure is latched by the next warm_poll, which drops the
+// schedule; a failed list is never pruned).  Main stream, before the batch
+// that first reads the pruned list.
+static void visible_prune(RenderContext* ctx, int ntiles) {
+    TriScratch& sc = ctx->tri;
+    auto& S = sc.sched;
+    if (S.markSet != S.listSet || S.markTag != S.listTag) {   // binned again since: mark afresh
+        S.visState = 0;
+        return;
+    }
+    const hipError_t q = hipEventQuery(S.evMark);
+    if (q == hipErrorNotReady) {
+        (void)hipGetLastError();   // an answer, not a failure
+        return;
+    }
+    if (q != hipSuccess) {
+        NR_CHECK(q);
+        S.visState = 0;
+        return;
+    }
+    if (sc.hfail && __atomic_load_n(sc.hfail, __ATOMIC_ACQUIRE)) return;
+    if (!S.totals.items) return;
+    NR_CHECK(hipMemsetAsync(S.vcnt, 0, ((size_t)ntiles + 3) * sizeof(u32), ctx->stream));
+    hipLaunchKernelGGL(k_prune_list, dim3(S.totals.items), dim3(256), 0, ctx->stream, (const uint4*)S.items,
+                       (const u32*)S.off, (const u32*)sc.fset[S.listSet].flist, (const u32*)S.vmask,
+                       (u32)std::min<u64>(S.totals.n, 0xFFFFFFFFull), S.vlist.p, S.vcnt.p, S.vcnt.p + ntiles + 2);
+    NR_CHECK(hipGetLastError());
+    S.visState = 2;
+}
+
 // loose: the batch's transform differs from the schedule's (loose_matches):
 // bin into the schedule's loose ranges, cursors from 0 (k_bin_warm), and let
 // k_vis slice each tile's actual count.
@@ -2255,9 +2426,35 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
     if (!loose && S.listSet >= 0 && sc.reuseMode != 2 && !sc.warmInject) {
         TriScratch::FreeSet& F = sc.fset[S.listSet];
         sc.last = T;
+        // The visible list (above): prune after a marking frame the host has
+        // seen complete; rasterise from the pruned copy in its depth mode --
+        // the schedule's items and plan, the kept counts as the cursors of a
+        // loose-format check whose tag (1) never matches its words (always 0);
+        // else the full list, on one eligible frame per generation with the
+        // winners marked.
+        const int zm = z_mode(fp);
+        const bool pruning = sc.pruneMode != 2 && !fp.fragCounter;
+        if (pruning && S.visState == 1) visible_prune(ctx, ntiles);
+        if (pruning && S.visState == 2 && S.visZ == zm) {
+            const WarmCheck wv{S.vcnt + ntiles, S.vcnt, S.off, 1u, 1u, sc.dfail, 1u};
+            vis_tail(ctx, F, fp, VisArgs{S.items, S.vlist, S.dplan, wv}, std::min<u32>(T.items, 8192));
+            ++sc.reusedBatches;
+            ++sc.prunedBatches;
+            return true;
+        }
+        FrameParams fpm = fp;
+        if (pruning && S.visState == 0 && visible_capture_ok(fp, zm)) visible_mark_begin(ctx, fpm, ntiles);
         const u32* plan = S.listGated ? F.gplan : S.dplan;
         const WarmCheck wc{F.fcur + ntiles, F.fcur, S.off, S.listTag, S.listMult, sc.dfail, 0u};
-        vis_tail(ctx, F, fp, VisArgs{S.items, F.flist, plan, wc}, std::min<u32>(T.items, 8192));
+        vis_tail(ctx, F, fpm, VisArgs{S.items, F.flist, plan, wc}, std::min<u32>(T.items, 8192));
+        if (fpm.winMask) {   // a marking frame: its end, for visible_prune
+            if (!S.evMark) S.evMark = sync_event();
+            NR_CHECK(hipEventRecord(S.evMark, sa));
+            S.visState = 1;
+            S.visZ = zm;
+            S.markSet = S.listSet;
+            S.markTag = S.listTag;
+        }
         ++sc.reusedBatches;
         return true;
     }
@@ -2532,6 +2729,18 @@ void settle(RenderContext* ctx) {
             keep_binning(ctx, F, pb->key, pb->tb, ntiles, sc.last);
     }
     delete pb;
+}
+
+// Pairs kept in the context's visible list, 0 when it has none (waits for the
+// main stream: a query, not a draw).
+i64 visible_pairs(RenderContext* ctx) {
+    auto& S = ctx->tri.sched;
+    if (!S.valid || S.visState != 2) return 0;
+    const i64 ntiles = ((S.key.W + TW - 1) / TW) * ((S.key.H + TH - 1) / TH);
+    u32 v = 0;
+    NR_CHECK(hipStreamSynchronize(ctx->stream));
+    NR_CHECK(hipMemcpy(&v, S.vcnt.p + ntiles + 2, sizeof v, hipMemcpyDeviceToHost));
+    return (i64)v;
 }
 
 }  // namespace nrtri

@@ -581,6 +581,30 @@ class RenderContext:
         off (every warm batch bins again)."""
         lib.SetListReuse(self._ptr, int(mode))
 
+    def pruned_batch_count(self) -> int:
+        """Of the reused batches, those rasterised from the visible list: the
+        kept pair list without the triangles that won no pixel on the
+        schedule's marking frame."""
+        return lib.GetPrunedBatchCount(self._ptr)
+
+    def visible_pair_count(self) -> int:
+        """Pairs kept in the current visible list, 0 when there is none."""
+        return lib.GetVisiblePairCount(self._ptr)
+
+    def set_visible_pruning(self, mode: int):
+        """The visible list of an unchanged repeat draw: 0 automatic (on), 2
+        off (reused batches rasterise from the full pair list)."""
+        lib.SetVisiblePruning(self._ptr, int(mode))
+
+    def schedule_totals(self) -> typing.Optional[dict]:
+        """Testing: totals of the context's warm schedule -- (tile, triangle)
+        pairs, k_vis work items, slices of split tiles, dense tiles -- or None
+        when it has none."""
+        out = (ctypes.c_long * 4)()
+        if not lib.GetScheduleTotals(self._ptr, out):
+            return None
+        return {"pairs": out[0], "items": out[1], "split": out[2], "heavy": out[3]}
+
     def packed(self) -> "PackedCommands":
         """A packing front end of this context: its draw and state calls go
         to the library as one array per submit() (ExecuteCommands)."""
