@@ -152,6 +152,17 @@ void DrawTexturedTriangles(RenderContext* ctx, Texture* tex, const f64* xy, cons
                            i64 n);                                        /* NEW: host arrays */
 void DrawTexturedTrianglesDevice(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv,
                                  i64 n);                                  /* NEW: device pointers (as DrawTrianglesDevice) */
+/* NEW: perspective-correct textured triangles (DESIGN §3 "Perspective-correct texture mapping").  q: n*3, laid
+   out like z, each corner's 1/w.  Per triangle a_k = u_k * q_k, b_k = v_k * q_k; per fragment U, V, Q are
+   interpolated from a, b, q like a Gouraud channel and the texel is that of (U * (1 / Q), V * (1 / Q)).  q is
+   not validated (a zero, negative or non-finite q gives a defined texel); q all 1 gives DrawTexturedTriangles'
+   frame bit for bit; depth stays affine.  A NULL q latches an error and draws nothing; every texture check of
+   DrawTexturedTriangles applies. */
+void DrawTexturedTrianglesPerspective(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv,
+                                      const f64* q, i64 n);               /* NEW: host arrays */
+void DrawTexturedTrianglesPerspectiveDevice(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z,
+                                            const f64* uv, const f64* q, i64 n);   /* NEW: device pointers (as
+                                 DrawTrianglesDevice) */
 TriangleBuffer* CreateTexturedTriangleBuffer(i64 n, const f64* xy, const f64* z,
                                              const f64* uv);              /* NEW: one H2D upload; no texture bound */
 void DrawTexturedTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb, Texture* tex);   /* NEW: texture chosen per
@@ -162,7 +173,7 @@ void DrawTexturedTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb, Texture*
    matrix16 with the viewport baked in (NULL = identity): c = M * (px, py, pz, 1), a vertex with cw <= 0 becomes
    NaN (its triangles are dropped; no near-plane clipping), otherwise (x, y, z) = (cx, cy, cz) / cw.  The assembled
    soup is then drawn like DrawTrianglesDevice's: the context's 2D transform, depth state and colour transform
-   apply, attributes stay affine in screen space.  Creation returns NULL and latches an error for an index >= nv,
+   apply, attributes stay affine in screen space (a textured mesh: unless SetMeshPerspective is on).  Creation returns NULL and latches an error for an index >= nv,
    a NULL attribute array with n > 0, or nv beyond 32 bits; n == 0 is a valid mesh that draws nothing.  A mesh on
    another device than the context's, or the wrong draw call for its kind, latches an error and draws nothing. */
 typedef struct Mesh Mesh;
@@ -196,6 +207,19 @@ bool AssembleMeshClipped(RenderContext* ctx, Mesh* m, const f64* matrix16, i64 c
                                  ctx's near plane and cull mode (the draw's own kernels): the full count in *n_out, the
                                  first min(cap, *n_out) triangles copied to the host (xy x6, z x3, attr x12 Gouraud / x4
                                  flat / x6 textured); a sync point; either mesh kind */
+/* NEW: perspective-correct texture mapping of DrawTexturedMesh.  Per context, off by default, not
+   part of the save / restore stack, not recorded in command lists.  On: the vertex stage keeps q = 1.0 / cw per
+   vertex (NaN where cw <= 0; a cut vertex of the clip stage: 1.0 / wNear) and the draw is a
+   DrawTexturedTrianglesPerspective batch; under a matrix whose last row is (0, 0, 0, 1) q == 1 and the frame is
+   the state-off frame bit for bit.  DrawMesh of a colour mesh ignores the state: colours stay affine. */
+bool SetMeshPerspective(RenderContext* ctx, bool on);                    /* NEW: returns true */
+bool GetMeshPerspective(RenderContext* ctx);                             /* NEW */
+bool AssembleMeshPerspective(RenderContext* ctx, Mesh* m, const f64* matrix16, i64 cap, f64* xy_out, f64* z_out,
+                             f64* uv_out, f64* q_out, i64* n_out);       /* NEW: the soup a DrawTexturedMesh of m
+                                 rasterises under ctx's near plane, cull mode and perspective state (the draw's own
+                                 kernels): the full count in *n_out, the first min(cap, *n_out) triangles copied to the
+                                 host (xy x6, z x3, uv x6, q x3; q is 1.0 with the state off); a sync point; a textured
+                                 mesh only */
 void SetFragmentCounting(RenderContext* ctx, bool on);                   /* NEW: covered-fragment counter */
 i64 GetFragmentCount(RenderContext* ctx);                                /* NEW */
 i64 GetLastRasterPath(RenderContext* ctx);                               /* NEW: 1 order-free tiled, 2 ordered, 3 order-free frame */

@@ -78,6 +78,8 @@ DEVICE_ABI = {
     "GetTriangleBufferCount": (L, (P,)),
     "DrawTexturedTriangles": (None, (P, P, P, P, P, L)),
     "DrawTexturedTrianglesDevice": (None, (P, P, P, P, P, L)),
+    "DrawTexturedTrianglesPerspective": (None, (P, P, P, P, P, P, L)),
+    "DrawTexturedTrianglesPerspectiveDevice": (None, (P, P, P, P, P, P, L)),
     "CreateTexturedTriangleBuffer": (P, (L, P, P, P)),
     "DrawTexturedTriangleBuffer": (None, (P, P, P)),
     "CreateMesh": (P, (L, P, L, P, P, B)),
@@ -95,6 +97,9 @@ DEVICE_ABI = {
     "GetMeshCull": (L, (P,)),
     "GetMeshLastTriangleCount": (L, (P,)),
     "AssembleMeshClipped": (B, (P, P, P, L, P, P, P, P)),
+    "SetMeshPerspective": (B, (P, B)),
+    "GetMeshPerspective": (B, (P,)),
+    "AssembleMeshPerspective": (B, (P, P, P, L, P, P, P, P, P)),
     "SetFragmentCounting": (None, (P, B)),
     "GetFragmentCount": (L, (P,)),
     "GetLastRasterPath": (L, (P,)),

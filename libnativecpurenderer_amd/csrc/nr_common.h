@@ -147,12 +147,14 @@ struct TriScratch {
     u32 splitAt = 0, dslice = 0;            // dense-tile split limits (SetSplitLimits; 0: NR_SPLIT_AT / NR_DSLICE)
     DevArray<f64> stage;                    // DrawTriangles() with host arrays
     // DrawMesh (nr_mesh.hip): the draw's transformed vertices and assembled soup -- (x, y) nv*2, z nv (padded
-    // to an even count), xy n*6, z n*3; read by the batch until it is settled, like `stage`
+    // to an even count), xy n*6, z n*3; read by the batch until it is settled, like `stage`.  A perspective
+    // textured draw (SetMeshPerspective) adds the vertices' 1/w, nv padded like z, before the soup and the
+    // soup's q n*3 after its z
     DevArray<f64> mstage;
     // clipped / culled mesh draws (nr_mesh.hip, SetMeshNearPlane / SetMeshCull): the draw's clip coordinates
     // (cx, cy, cz, cw) nv*4, and per source triangle its keep mask | output count | scanned offset, n each
     // (+ the total); the emitted soup -- xy n_out*6, z n_out*3 (padded to an even count), attributes
-    // n_out*attr_stride -- is then what mstage holds
+    // n_out*attr_stride, and a perspective textured draw's q n_out*3 -- is then what mstage holds
     DevArray<f64> mclip;
     DevArray<u32> mscan;
     // warm binning (nr_tri_free.hip): the tile offsets, k_vis work items and
@@ -302,6 +304,7 @@ struct RenderContext {
     // triangle count the last mesh draw handed to the rasters
     f64 meshNear = 0;
     int meshCull = 0;
+    bool meshPersp = false;           // textured mesh draws carry 1/cw to the rasters (SetMeshPerspective); same rule
     i64 meshLastCount = 0;
     iu8* u8buf = nullptr; size_t u8cap = 0;   // GetBufferAsUInt8 staging
     // multi-GPU: owned tile rows ty % nshards == shard (nr_dist.hip)

@@ -14,6 +14,9 @@
 //   cx = ((M[0]*px + M[1]*py) + M[2]*pz) + M[3]      cy, cz, cw: rows 1, 2, 3
 //   !(cw > 0): x = y = z = NaN;  else x = cx / cw, y = cy / cw, z = cz / cw
 // With the last row (0, 0, 0, 1) cw is exactly 1 and x == cx.
+// With the context's perspective state on (SetMeshPerspective) a textured draw
+// also keeps q = 1.0 / cw (NaN where !(cw > 0)) per vertex, gathers it like z
+// and hands it to the rasters as the batch's 1/w (ATTR_TEX_PERSP).
 //
 // The per-draw output lives in the context (TriScratch::mstage), not in the
 // mesh: one mesh may be drawn on several contexts.  A pending batch, or its
@@ -54,8 +57,11 @@ namespace {
 struct Mat4 { f64 m[16]; };
 
 // Pass 1: one thread per vertex.  (x, y) as one 16-byte store, z beside it.
+// Q: also q = 1.0 / cw (vq).
+template <bool Q>
 __global__ __launch_bounds__(256) void k_mesh_vertex(const f64* __restrict__ pos, i64 nv, Mat4 M,
-                                                     double2* __restrict__ vxy, f64* __restrict__ vz) {
+                                                     double2* __restrict__ vxy, f64* __restrict__ vz,
+                                                     f64* __restrict__ vq) {
     const i64 v = (i64)blockIdx.x * 256 + threadIdx.x;
     if (v >= nv) return;
     const f64 px = pos[v * 3], py = pos[v * 3 + 1], pz = pos[v * 3 + 2];
@@ -71,19 +77,23 @@ __global__ __launch_bounds__(256) void k_mesh_vertex(const f64* __restrict__ pos
     }
     vxy[v] = make_double2(x, y);
     vz[v] = z;
+    if constexpr (Q) vq[v] = cw > 0 ? 1.0 / cw : NAN;
 }
 
 // Pass 2: one thread per triangle corner (3n): indices, xy and z are read or
 // written contiguously across a wave; only the gather from the vertex table
-// (cache-resident) is irregular.
+// (cache-resident) is irregular.  Q: q is gathered as z is.
+template <bool Q>
 __global__ __launch_bounds__(256) void k_mesh_assemble(const u32* __restrict__ idx, i64 ncorner,
                                                        const double2* __restrict__ vxy, const f64* __restrict__ vz,
-                                                       double2* __restrict__ xy, f64* __restrict__ z) {
+                                                       double2* __restrict__ xy, f64* __restrict__ z,
+                                                       const f64* __restrict__ vq, f64* __restrict__ q) {
     const i64 c = (i64)blockIdx.x * 256 + threadIdx.x;
     if (c >= ncorner) return;
     const u32 i = idx[c];
     xy[c] = vxy[i];
     z[c] = vz[i];
+    if constexpr (Q) q[c] = vq[i];
 }
 
 // Creation: per-vertex attributes (w2 16-byte words each: 2 for RGBA, 1 for a
@@ -190,6 +200,15 @@ __device__ __forceinline__ ClipPos clip_slot_pos(const ClipTri& c, int a, int b,
     return q;
 }
 
+// 1/w of polygon vertex (a, b): a corner's 1.0 / cw (NaN where !(cw > 0), the
+// vertex stage's q), a cut's 1.0 / wNear -- the same value from either triangle
+// that shares the cut edge.
+__device__ __forceinline__ f64 clip_slot_q(const ClipTri& c, int a, int b, f64 wNear) {
+    if (a != b) return 1.0 / wNear;
+    const f64 aw = sel3(a, c.cw);
+    return aw > 0 ? 1.0 / aw : NAN;
+}
+
 // cull 1 drops area2 > 0, cull 2 drops area2 < 0; a zero or NaN area is never culled
 __device__ __forceinline__ bool clip_culled(const ClipPos& p0, const ClipPos& p1, const ClipPos& p2, int cull) {
     const f64 area2 = (p1.x - p0.x) * (p2.y - p0.y) - (p2.x - p0.x) * (p1.y - p0.y);
@@ -247,13 +266,15 @@ __device__ __forceinline__ void clip_store_pos(i64 o, const ClipPos& p0, const C
 // (UV), or 0 for a flat mesh, whose one colour (two words per triangle) is
 // copied to each output.  The attributes go word by word -- the three corners'
 // word j in, the polygon's word j out -- so nothing is held in an array.
-template <int H>
+// Q (a perspective textured draw): also each output corner's 1/w (clip_slot_q)
+// into oq, laid out like z.
+template <int H, bool Q = false>
 __global__ __launch_bounds__(256) void k_mesh_clip_emit(const u32* __restrict__ idx, i64 n,
                                                         const double2* __restrict__ clip,
                                                         const double2* __restrict__ attr, f64 wNear,
                                                         const u32* __restrict__ keep, const u32* __restrict__ off,
                                                         double2* __restrict__ xy, f64* __restrict__ z,
-                                                        double2* __restrict__ oattr) {
+                                                        double2* __restrict__ oattr, f64* __restrict__ oq) {
     const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
     if (t >= n) return;
     const u32 k = keep[t];
@@ -277,6 +298,19 @@ __global__ __launch_bounds__(256) void k_mesh_clip_emit(const u32* __restrict__ 
         const ClipPos q3 = clip_slot_pos(c, a3, b3, wNear);
         t3 = q3.t;
         clip_store_pos(o1, q0, q2, q3, xy, z);
+    }
+    if constexpr (Q) {
+        const f64 w0 = clip_slot_q(c, a0, b0, wNear), w2 = clip_slot_q(c, a2, b2, wNear);
+        if (k & 1u) {
+            oq[o0 * 3] = w0;
+            oq[o0 * 3 + 1] = clip_slot_q(c, a1, b1, wNear);
+            oq[o0 * 3 + 2] = w2;
+        }
+        if (k & 2u) {
+            oq[o1 * 3] = w0;
+            oq[o1 * 3 + 1] = w2;
+            oq[o1 * 3 + 2] = clip_slot_q(c, a3, b3, wNear);
+        }
     }
     if constexpr (H == 0) {
         const double2 c0 = attr[t * 2], c1 = attr[t * 2 + 1];
@@ -376,42 +410,57 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
     return m;
 }
 
-struct Soup { const f64* xy; const f64* z; };
+struct Soup { const f64* xy; const f64* z; const f64* q; };   // q: a perspective draw's 1/w (else null)
 
 // The vertex stage and the assembly of `m` under `matrix` into ctx's mesh
 // staging, on the context's stream (m->n > 0).  False: the staging could not
-// be grown (error latched).
-bool assemble(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out) {
+// be grown (error latched).  persp: the q-writing instances (out->q).
+bool assemble(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out, bool persp = false) {
     nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
     TriScratch& sc = ctx->tri;
     const size_t nv = (size_t)m->nv, n = (size_t)m->n;
     const size_t vzn = (nv + 1) & ~(size_t)1;   // keeps the soup's xy 16-byte aligned
-    if (!sc.mstage.ensure(nv * 2 + vzn + n * 9)) return false;
+    if (!sc.mstage.ensure(nv * 2 + vzn + n * 9 + (persp ? vzn + n * 3 : 0))) return false;
     f64* vxy = sc.mstage;
     f64* vz = vxy + nv * 2;
-    f64* xy = vz + vzn;
+    f64* vq = persp ? vz + vzn : nullptr;   // (padded like vz: the soup's xy stays 16-byte aligned)
+    f64* xy = vz + vzn + (persp ? vzn : 0);
     f64* z = xy + n * 6;
+    f64* q = persp ? z + n * 3 : nullptr;
     Mat4 M = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
     if (matrix)
         for (int k = 0; k < 16; ++k) M.m[k] = matrix[k];
     hipEvent_t a, b;
     nr_timing_begin(ctx, NRK_MESH_VERTEX, &a, &b);
-    hipLaunchKernelGGL(k_mesh_vertex, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv, M,
-                       reinterpret_cast<double2*>(vxy), vz);
+    if (persp)
+        hipLaunchKernelGGL(k_mesh_vertex<true>, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv, M,
+                           reinterpret_cast<double2*>(vxy), vz, vq);
+    else
+        hipLaunchKernelGGL(k_mesh_vertex<false>, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv, M,
+                           reinterpret_cast<double2*>(vxy), vz, vq);
     NR_CHECK(hipGetLastError());
     nr_timing_end(ctx, NRK_MESH_VERTEX, a, b);
     nr_timing_begin(ctx, NRK_MESH_ASSEMBLE, &a, &b);
-    hipLaunchKernelGGL(k_mesh_assemble, dim3(blocks_for(m->n * 3)), dim3(256), 0, ctx->stream, m->idx, m->n * 3,
-                       reinterpret_cast<const double2*>(vxy), vz, reinterpret_cast<double2*>(xy), z);
+    if (persp)
+        hipLaunchKernelGGL(k_mesh_assemble<true>, dim3(blocks_for(m->n * 3)), dim3(256), 0, ctx->stream, m->idx,
+                           m->n * 3, reinterpret_cast<const double2*>(vxy), vz, reinterpret_cast<double2*>(xy), z, vq, q);
+    else
+        hipLaunchKernelGGL(k_mesh_assemble<false>, dim3(blocks_for(m->n * 3)), dim3(256), 0, ctx->stream, m->idx,
+                           m->n * 3, reinterpret_cast<const double2*>(vxy), vz, reinterpret_cast<double2*>(xy), z, vq, q);
     NR_CHECK(hipGetLastError());
     nr_timing_end(ctx, NRK_MESH_ASSEMBLE, a, b);
     out->xy = xy;
     out->z = z;
+    out->q = q;
     return true;
 }
 
 // What a mesh draw hands to the rasters: n triangles and their attributes.
-struct DrawSoup { const f64* xy; const f64* z; const f64* attr; i64 n; };
+// q: the corners' 1/w of a perspective textured draw (else null).
+struct DrawSoup { const f64* xy; const f64* z; const f64* attr; i64 n; const f64* q; };
+
+// A textured mesh drawn with the context's perspective state on; colour meshes ignore the state.
+inline bool persp_draw(const RenderContext* ctx, const Mesh* m) { return ctx->meshPersp && m->mode == ATTR_TEX; }
 
 inline bool clip_stage_on(const RenderContext* ctx) { return ctx->meshNear > 0 || ctx->meshCull != 0; }
 
@@ -420,7 +469,7 @@ inline bool clip_stage_on(const RenderContext* ctx) { return ctx->meshNear > 0 |
 // the total n_out has been read back, the one wait of such a draw -- the emit
 // pass into ctx's mesh staging, sized to n_out.  out->n == 0: nothing is left
 // to draw (no staging is touched).  False: scratch could not be grown (latched).
-bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, DrawSoup* out) {
+bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, DrawSoup* out, bool persp) {
     if (m->n > (i64)INT_MAX) return fail("mesh clip stage", "more than 2^31 - 1 triangles");
     nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
     TriScratch& sc = ctx->tri;
@@ -459,16 +508,17 @@ bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Draw
     NR_CHECK(hipMemcpyAsync(&h[1], cnt + (n - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("mesh clip stage", "the count could not be read back");
     const size_t nout = (size_t)h[0] + (size_t)h[1];
-    out->xy = out->z = out->attr = nullptr;
+    out->xy = out->z = out->attr = out->q = nullptr;
     out->n = (i64)nout;
     if (nout == 0) return true;
     if (nout > 2 * n) return fail("mesh clip stage", "inconsistent triangle count");   // (never: the counts are 0, 1 or 2)
     const size_t stride = (size_t)nrtri::attr_stride(m->mode);
     const size_t zn = (nout * 3 + 1) & ~(size_t)1;   // keeps the attributes 16-byte aligned
-    if (!sc.mstage.ensure(nout * 6 + zn + nout * stride)) return false;
+    if (!sc.mstage.ensure(nout * 6 + zn + nout * stride + (persp ? nout * 3 : 0))) return false;
     f64* xy = sc.mstage;
     f64* z = xy + nout * 6;
     f64* attr = z + zn;
+    f64* q = persp ? attr + nout * stride : nullptr;
     nr_timing_begin(ctx, NRK_MESH_CLIP_EMIT, &a, &b);
     const dim3 grid(blocks_for(m->n)), block(256);
     const double2* mattr = reinterpret_cast<const double2*>(m->attr);
@@ -476,29 +526,35 @@ bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Draw
     double2* attr2 = reinterpret_cast<double2*>(attr);
     if (m->mode == nrtri::ATTR_GOURAUD)
         hipLaunchKernelGGL(k_mesh_clip_emit<2>, grid, block, 0, ctx->stream, m->idx, m->n, clip, mattr, wNear, keep, off,
-                           xy2, z, attr2);
+                           xy2, z, attr2, q);
+    else if (m->mode == nrtri::ATTR_TEX && persp)
+        hipLaunchKernelGGL((k_mesh_clip_emit<1, true>), grid, block, 0, ctx->stream, m->idx, m->n, clip, mattr, wNear,
+                           keep, off, xy2, z, attr2, q);
     else if (m->mode == nrtri::ATTR_TEX)
         hipLaunchKernelGGL(k_mesh_clip_emit<1>, grid, block, 0, ctx->stream, m->idx, m->n, clip, mattr, wNear, keep, off,
-                           xy2, z, attr2);
+                           xy2, z, attr2, q);
     else
         hipLaunchKernelGGL(k_mesh_clip_emit<0>, grid, block, 0, ctx->stream, m->idx, m->n, clip, mattr, wNear, keep, off,
-                           xy2, z, attr2);
+                           xy2, z, attr2, q);
     NR_CHECK(hipGetLastError());
     nr_timing_end(ctx, NRK_MESH_CLIP_EMIT, a, b);
     out->xy = xy;
     out->z = z;
     out->attr = attr;
+    out->q = q;
     return true;
 }
 
 // The soup a draw of `m` rasterises under the context's clip state: the unclipped
 // path's (vertex stage + assembly, the mesh's own attributes) when it is off.
 bool draw_soup(RenderContext* ctx, const Mesh* m, const f64* matrix, DrawSoup* out) {
-    if (clip_stage_on(ctx)) return assemble_clipped(ctx, m, matrix, out);
+    const bool persp = persp_draw(ctx, m);
+    if (clip_stage_on(ctx)) return assemble_clipped(ctx, m, matrix, out, persp);
     Soup s;
-    if (!assemble(ctx, m, matrix, &s)) return false;
+    if (!assemble(ctx, m, matrix, &s, persp)) return false;
     out->xy = s.xy;
     out->z = s.z;
+    out->q = s.q;
     out->attr = m->attr;
     out->n = m->n;
     return true;
@@ -606,7 +662,7 @@ void DrawTexturedMesh(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matr
     if (!draw_soup(ctx, m, matrix16, &s)) return;
     ctx->meshLastCount = s.n;
     if (s.n <= 0) return;
-    nrtri::draw_textured(ctx, tex, s.xy, s.z, s.attr, s.n, nullptr, false);
+    nrtri::draw_textured(ctx, tex, s.xy, s.z, s.attr, s.n, nullptr, false, s.q);   // (s.q: the perspective state)
 }
 
 // New: the vertex stage and the assembly alone -- exactly the kernels DrawMesh
@@ -647,6 +703,50 @@ bool SetMeshCull(RenderContext* ctx, i64 mode) {
     return true;
 }
 i64 GetMeshCull(RenderContext* ctx) { return ctx->meshCull; }
+
+// New: perspective-correct texture mapping of this context's DrawTexturedMesh
+// draws: the vertex stage keeps q = 1.0 / cw per vertex (a cut
+// vertex: 1.0 / wNear) and the rasters sample at (U / Q, V / Q) instead of the
+// screen-affine (u, v).  Off by default; per context; not part of the save /
+// restore stack, not recorded (the clip state's rule).  DrawMesh of a colour
+// mesh ignores it: colours stay affine in screen space.  Returns true.
+bool SetMeshPerspective(RenderContext* ctx, bool on) {
+    ctx->meshPersp = on;
+    return true;
+}
+bool GetMeshPerspective(RenderContext* ctx) { return ctx->meshPersp; }
+
+// New: the soup a DrawTexturedMesh of `m` rasterises under the context's near
+// plane, cull mode and perspective state -- the draw's own kernels -- copied to
+// the host: *n_out = the full count, the first min(cap, *n_out) triangles in
+// xy_out (x6), z_out (x3), uv_out (x6) and q_out (x3; 1.0 everywhere with the
+// perspective state off).  A sync point; a textured mesh only.
+bool AssembleMeshPerspective(RenderContext* ctx, Mesh* m, const f64* matrix16, i64 cap, f64* xy_out, f64* z_out,
+                             f64* uv_out, f64* q_out, i64* n_out) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    if (!m) return fail("AssembleMeshPerspective", "NULL mesh");
+    if (m->mode != nrtri::ATTR_TEX) return fail("AssembleMeshPerspective", "a colour mesh");
+    if (m->device != ctx->device) return fail("AssembleMeshPerspective", "mesh on another device");
+    if (!n_out) return fail("AssembleMeshPerspective", "NULL output");
+    *n_out = 0;
+    if (cap < 0) return fail("AssembleMeshPerspective", "negative capacity");
+    if (cap > 0 && (!xy_out || !z_out || !uv_out || !q_out)) return fail("AssembleMeshPerspective", "NULL output");
+    if (m->n <= 0) return true;
+    DrawSoup s;
+    if (!draw_soup(ctx, m, matrix16, &s)) return false;
+    *n_out = s.n;
+    const size_t k = (size_t)(s.n < cap ? s.n : cap);
+    if (k > 0) {
+        NR_CHECK(hipMemcpyAsync(xy_out, s.xy, k * 6 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
+        NR_CHECK(hipMemcpyAsync(z_out, s.z, k * 3 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
+        NR_CHECK(hipMemcpyAsync(uv_out, s.attr, k * 6 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
+        if (s.q) NR_CHECK(hipMemcpyAsync(q_out, s.q, k * 3 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    NR_CHECK(hipStreamSynchronize(ctx->stream));
+    if (!s.q)
+        for (size_t i = 0; i < k * 3; ++i) q_out[i] = 1.0;
+    return true;
+}
 
 // New: the triangles the context's last mesh draw handed to the rasters: n_out of
 // the clip stage, or the mesh's n when the stage was off.

@@ -5,7 +5,9 @@
 //   vertices -> context transform (cpp:446-453) -> screen space;
 //   coverage = even-odd pointInPolygon (cpp:822-845) at integer pixels;
 //   w1,w2 barycentric in f64, attr = a0 + (a1-a0)*w1 + (a2-a0)*w2 (a colour
-//   channel, or a texture coordinate whose texel is then the colour);
+//   channel, or a texture coordinate whose texel is then the colour; a
+//   perspective textured batch interpolates u q, v q and q that way and
+//   samples at (U * (1 / Q), V * (1 / Q)));
 //   depth u32 LESS, written only when test+write are on;
 //   blend = ApplyPixel (cpp:515-549) in submission order.
 //
@@ -24,8 +26,12 @@ constexpr int TW = 64;   // tile width  (= one wave's lanes)
 constexpr int TH = 32;   // tile height
 
 // Per-triangle attribute of a batch: one colour, a colour per vertex, or a
-// texture coordinate per vertex (texel units) sampled from FrameParams::tex.
-enum AttrMode { ATTR_FLAT = 0, ATTR_GOURAUD = 1, ATTR_TEX = 2 };
+// texture coordinate per vertex (texel units) sampled from FrameParams::tex --
+// interpolated affinely in screen space (ATTR_TEX), or perspective-correct
+// with a 1/w per vertex, FrameParams::q (ATTR_TEX_PERSP).
+enum AttrMode { ATTR_FLAT = 0, ATTR_GOURAUD = 1, ATTR_TEX = 2, ATTR_TEX_PERSP = 3 };
+// either textured mode: the attribute array is the uv array, the colour a texel
+__host__ __device__ constexpr bool attr_textured(int mode) { return mode == ATTR_TEX || mode == ATTR_TEX_PERSP; }
 
 struct TriSrc {
     const f64* xy;    // n*6
@@ -37,7 +43,7 @@ struct TriSrc {
     __host__ __device__ const f64* uv() const { return attr; }     // (textured batches)
 };
 // doubles of the attribute array per triangle
-__host__ __device__ inline int attr_stride(int mode) { return mode == ATTR_GOURAUD ? 12 : (mode == ATTR_TEX ? 6 : 4); }
+__host__ __device__ inline int attr_stride(int mode) { return mode == ATTR_GOURAUD ? 12 : (attr_textured(mode) ? 6 : 4); }
 
 // The texture a textured batch samples (nearest, tex_index): texels as the
 // framebuffer stores them, ipp doubles each, w >= 2 and h >= 2 (a side below
@@ -381,8 +387,12 @@ struct FrameParams {
     u32 tileEpoch;    // RenderContext::tileStamp) and writes only its frame output
     u64* tstamp;      // non-null (kernel timing): {~first start, last end} of the raster on the device's
                       // 100 MHz clock (raster_stamp_begin / _end, nr_timing_stamp)
-    TexView tex;      // ATTR_TEX batches: the texture (a snapshot when it aliases fb)
+    TexView tex;      // textured batches: the texture (a snapshot when it aliases fb)
     u32* winMask;     // a marking frame (k_vis MARK instances only): bit t is set when triangle t wins a pixel
+    // ATTR_TEX_PERSP batches: each corner's 1/w, n*3 laid out like src.z (else null).  Only the shading reads it,
+    // so it lives here and not in TriSrc, and last: the binning's BinParams and every offset of the snapshot
+    // the existing instances read stay as they were.
+    const f64* q;
 };
 
 // Texel of a fragment's interpolated (u, v), as an offset in doubles: the
@@ -516,7 +526,7 @@ enum PlanWord {
 
 bool grow_temp(TriScratch& sc, size_t need);
 
-FrameParams frame_params(RenderContext* ctx, const TriSrc& src, const TexView* tex = nullptr);
+FrameParams frame_params(RenderContext* ctx, const TriSrc& src, const TexView* tex = nullptr, const f64* q = nullptr);
 inline BinParams bin_params(const FrameParams& fp) {   // the binning's view of the same snapshot
     BinParams bp;
     bp.src = fp.src;
@@ -536,7 +546,7 @@ u32* tile_stamps(RenderContext* ctx, i64 ntiles);   // the context's tile stamps
 // global-sort path (draw_ordered_sorted) otherwise, and for a batch with a tile
 // of more than ORD_SORT_CAP triangles (detected by the plan, re-run)
 void draw_ordered(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned,
-                  const TexView* tex = nullptr);
+                  const TexView* tex = nullptr, const f64* q = nullptr);
 void draw_ordered_sorted(RenderContext* ctx, const TriSrc& src, const FrameParams& fp, const BinParams& bp);
 // the same kernels for a deferred re-run (nr_settle): the batch's snapshot only, context flags untouched
 void rerun_ordered_sorted(RenderContext* ctx, const TriSrc& src, const FrameParams& fp, const BinParams& bp);
@@ -554,17 +564,19 @@ void launch_ordered_binned(const FrameParams& fp, const u32* list, const u32* of
 // so the batch is sized exactly in the call -- an overflow re-run never reads
 // them after it returns
 void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, bool ordered = false,
-               const TexView* tex = nullptr);
+               const TexView* tex = nullptr, const f64* q = nullptr);
 void settle(RenderContext* ctx);
 i64 visible_pairs(RenderContext* ctx);   // pairs kept in the schedule's visible list (0: none)
 
 // the batch entry points behind every triangle draw call (nr_tri.hip), shared with the mesh front end
 // (nr_mesh.hip): draw picks the raster; draw_textured resolves the texture first (check_texture: its
-// preconditions, an error latched under the caller's name `what` when one fails)
+// preconditions, an error latched under the caller's name `what` when one fails); q: the 1/w array of a
+// perspective textured batch (ATTR_TEX_PERSP), null otherwise
 void draw(RenderContext* ctx, const f64* xy, const f64* z, const f64* attr, i64 n, int mode, Opacity opq,
-          TriangleBuffer* tb = nullptr, bool callerOwned = false, const TexView* tex = nullptr);
+          TriangleBuffer* tb = nullptr, bool callerOwned = false, const TexView* tex = nullptr,
+          const f64* q = nullptr);
 bool check_texture(RenderContext* ctx, const Texture* tex, const char* what);
 void draw_textured(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv, i64 n,
-                   TriangleBuffer* tb, bool callerOwned);
+                   TriangleBuffer* tb, bool callerOwned, const f64* q = nullptr);
 
 }  // namespace nrtri

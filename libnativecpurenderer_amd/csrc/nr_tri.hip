@@ -29,7 +29,7 @@ bool grow_temp(TriScratch& sc, size_t need) {
     return true;
 }
 
-FrameParams frame_params(RenderContext* ctx, const TriSrc& src, const TexView* tex) {
+FrameParams frame_params(RenderContext* ctx, const TriSrc& src, const TexView* tex, const f64* q) {
     TriScratch& sc = ctx->tri;
     if (!sc.h_total) NR_CHECK(hipHostMalloc((void**)&sc.h_total, 4 * sizeof(u64)));
     if (ctx->depthTest) nr_ensure_depth(ctx);
@@ -61,6 +61,7 @@ FrameParams frame_params(RenderContext* ctx, const TriSrc& src, const TexView* t
     fp.tstamp = nullptr;
     fp.tex = tex ? *tex : tex_view(nullptr, 2, 2, false);
     fp.winMask = nullptr;
+    fp.q = q;
     if (ctx->countFragments) {
         if (!sc.d_frag) NR_CHECK(hipMalloc(&sc.d_frag, sizeof(u64)));
         NR_CHECK(hipMemsetAsync(sc.d_frag, 0, sizeof(u64), ctx->stream));
@@ -190,9 +191,9 @@ Opacity device_opacity(RenderContext* ctx, const TriSrc& src) {
 }  // namespace
 
 // attr: the batch's colours (mode ATTR_FLAT / ATTR_GOURAUD) or its texture
-// coordinates (ATTR_TEX, sampled from *tex).
+// coordinates (ATTR_TEX / ATTR_TEX_PERSP, sampled from *tex; q: the latter's 1/w per corner).
 void draw(RenderContext* ctx, const f64* xy, const f64* z, const f64* attr, i64 n, int mode, Opacity opq,
-          TriangleBuffer* tb, bool callerOwned, const TexView* tex) {
+          TriangleBuffer* tb, bool callerOwned, const TexView* tex, const f64* q) {
     NR_CHECK(hipSetDevice(ctx->device));
     nr_settle(ctx);   // recorded draws come first (the colour entry points reach here with their list still queued)
     if (n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
@@ -201,8 +202,8 @@ void draw(RenderContext* ctx, const f64* xy, const f64* z, const f64* attr, i64 
     src.xy = xy; src.z = z; src.attr = attr; src.mode = mode; src.n = n;
     const bool freeEligible = ctx->ct[3] == 1 && ctx->forceOrdered == 0;
     if (freeEligible && opq == OPQ_UNKNOWN) opq = device_opacity(ctx, src);
-    if (freeEligible && opq == OPQ_OPAQUE) draw_free(ctx, src, tb, callerOwned, false, tex);
-    else draw_ordered(ctx, src, tb, callerOwned, tex);
+    if (freeEligible && opq == OPQ_OPAQUE) draw_free(ctx, src, tb, callerOwned, false, tex, q);
+    else draw_ordered(ctx, src, tb, callerOwned, tex, q);
 }
 
 // A textured batch: the texture is checked (the sampler's clamp to w-2 / h-2
@@ -222,12 +223,14 @@ bool check_texture(RenderContext* ctx, const Texture* tex, const char* what) {
     return false;
 }
 
+// q non-null: a perspective textured batch (ATTR_TEX_PERSP).
 void draw_textured(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv, i64 n,
-                   TriangleBuffer* tb, bool callerOwned) {
+                   TriangleBuffer* tb, bool callerOwned, const f64* q) {
     settle(ctx);   // (a re-run of the pending batch comes before a snapshot of the target)
     TexSrc ts = nr_tex_source(ctx, tex);
     const TexView tv = tex_view(ts.ptr, tex->width, tex->height, tex->enableAlpha);
-    draw(ctx, xy, z, uv, n, ATTR_TEX, tex->enableAlpha ? OPQ_BLENDED : OPQ_OPAQUE, tb, callerOwned, &tv);
+    draw(ctx, xy, z, uv, n, q ? ATTR_TEX_PERSP : ATTR_TEX, tex->enableAlpha ? OPQ_BLENDED : OPQ_OPAQUE, tb, callerOwned,
+         &tv, q);
     if (ts.tmp) {   // (rare: the snapshot must outlive the batch and any re-run of it)
         settle(ctx);
         nr_tex_release(ctx, ts);
@@ -261,16 +264,18 @@ void nr_settle(RenderContext* ctx) {
 
 // The context's staging array (TriScratch::stage) laid out for a batch of n
 // triangles with ncol attribute doubles each: xy n*6 | z n*3, padded to an even
-// count (keeps the attributes 16-byte aligned) | attributes n*ncol.  The caller
+// count (keeps the attributes 16-byte aligned) | attributes n*ncol | with
+// `persp` the 1/w array q n*3 (read as single doubles, like z).  The caller
 // has settled the context (a pending batch may still read the array).  False:
 // it could not be grown (error latched).
-struct Stage { f64* xy; f64* z; f64* attr; };
-static bool stage_batch(RenderContext* ctx, i64 n, size_t ncol, Stage* st) {
+struct Stage { f64* xy; f64* z; f64* attr; f64* q; };
+static bool stage_batch(RenderContext* ctx, i64 n, size_t ncol, Stage* st, bool persp = false) {
     const size_t zn = ((size_t)n * 3 + 1) & ~(size_t)1;
-    if (!ctx->tri.stage.ensure((size_t)n * (6 + ncol) + zn)) return false;
+    if (!ctx->tri.stage.ensure((size_t)n * (6 + ncol) + zn + (persp ? (size_t)n * 3 : 0))) return false;
     st->xy = ctx->tri.stage;
     st->z = st->xy + (size_t)n * 6;
     st->attr = st->z + zn;
+    st->q = persp ? st->attr + (size_t)n * ncol : nullptr;
     return true;
 }
 
@@ -368,6 +373,53 @@ void DrawTexturedTrianglesDevice(RenderContext* ctx, Texture* tex, const f64* xy
         return;
     }
     draw_textured(ctx, tex, xy, z, uv, n, nullptr, true);
+}
+
+// New: perspective-correct textured triangles from host arrays (DESIGN.md §3
+// "Perspective-correct texture mapping"): q, n*3 laid out like z, is each
+// corner's 1/w.  Not validated: any value gives a defined texel.  A NULL q
+// latches an error and draws nothing; otherwise as DrawTexturedTriangles.
+void DrawTexturedTrianglesPerspective(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv,
+                                      const f64* q, i64 n) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    nr_settle(ctx);   // a pending batch may still read the staging buffer; recorded draws come first
+    if (!check_texture(ctx, tex, "DrawTexturedTrianglesPerspective")) return;
+    if (!q) {
+        nr_set_error_msg("DrawTexturedTrianglesPerspective: NULL q");
+        return;
+    }
+    if (n <= 0) return;
+    Stage st;
+    if (!stage_batch(ctx, n, 6, &st, true)) return;
+    NR_CHECK(hipMemcpyAsync(st.xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    if (z) NR_CHECK(hipMemcpyAsync(st.z, z, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    NR_CHECK(hipMemcpyAsync(st.attr, uv, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    NR_CHECK(hipMemcpyAsync(st.q, q, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    NR_CHECK(hipStreamSynchronize(ctx->stream));   // caller may reuse its arrays on return
+    draw_textured(ctx, tex, st.xy, z ? st.z : nullptr, st.attr, n, nullptr, false, st.q);
+}
+
+// New: the same from device-resident arrays (as DrawTexturedTrianglesDevice; q
+// stays the caller's like z: it is read as single doubles).
+void DrawTexturedTrianglesPerspectiveDevice(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z,
+                                            const f64* uv, const f64* q, i64 n) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    nr_settle(ctx);
+    if (!check_texture(ctx, tex, "DrawTexturedTrianglesPerspectiveDevice")) return;
+    if (!q) {
+        nr_set_error_msg("DrawTexturedTrianglesPerspectiveDevice: NULL q");
+        return;
+    }
+    if (n <= 0) return;
+    if (((uintptr_t)xy | (uintptr_t)uv) & 15) {   // (16-byte vector loads: re-stage, as DrawTrianglesDevice)
+        Stage st;
+        if (!stage_batch(ctx, n, 6, &st)) return;
+        NR_CHECK(hipMemcpyAsync(st.xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
+        NR_CHECK(hipMemcpyAsync(st.attr, uv, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
+        draw_textured(ctx, tex, st.xy, z, st.attr, n, nullptr, true, q);   // (z and q stay the caller's)
+        return;
+    }
+    draw_textured(ctx, tex, xy, z, uv, n, nullptr, true, q);
 }
 
 // New: a device-resident triangle soup (the H2D point; drawn many times).

@@ -940,8 +940,9 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
     __syncthreads();
     NR_PROBE_STAMP(5);
     const TexView& tv = fp.tex;   // (textured batches)
-    if constexpr (MODE == ATTR_TEX) {
-        // Textured: a pixel's colour is a dependent gather (record -> u, v ->
+    if constexpr (attr_textured(MODE)) {
+        // Textured (either mode; the perspective record's texel carries the
+        // divide, record_texel_persp): a pixel's colour is a dependent gather (record -> u, v ->
         // texel, 24 B), so a thread first forms the texel offsets of TQ of its
         // pixels, then issues their loads together, and only then consumes
         // them (as the flat path keeps FQ loads in flight).  Ordinary cached
@@ -981,7 +982,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                     ovf |= 1u << k;
                     continue;
                 }
-                ti[j] = record_texel(tv, rec + d * St::REC, px, py);
+                ti[j] = record_texel_of<MODE>(tv, rec + d * St::REC, px, py);
             }
             f64 c[TQ][3];
 #pragma unroll
@@ -1392,7 +1393,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
             // instances 8-24 B/lane of spills), and so do textured batches in
             // the lane raster (with the f32 spans its LESS + write instances
             // need 12 B/lane of scratch; with the f64 ones 119 VGPRs, none).
-            constexpr bool SPAN32 = (MODE == ATTR_GOURAUD || (MODE == ATTR_TEX && FLAT)) && ZMODE != 2 && !COUNT;
+            constexpr bool SPAN32 = (MODE == ATTR_GOURAUD || (attr_textured(MODE) && FLAT)) && ZMODE != 2 && !COUNT;
             if constexpr (FLAT) {
                 // rows: the chunk's (triangle, row) pairs, 64 per window
                 const u32 nr = r0 < r1 ? (u32)(r1 - r0) : 0u;
@@ -1692,7 +1693,11 @@ static void launch_vis_any(const FrameParams& fp, const TriScratch& sc, const Ba
     const int zmode = z_mode(fp), mode = fp.src.mode;
 #define NR_VG(ZM, G) (fp.fragCounter ? launch_vis<ZM, true, G>(fp, sc, t, va, grid, s, start, stop) \
                                      : launch_vis<ZM, false, G>(fp, sc, t, va, grid, s, start, stop))
-#define NR_VZ(ZM) (mode == ATTR_TEX ? NR_VG(ZM, ATTR_TEX) : mode == ATTR_GOURAUD ? NR_VG(ZM, ATTR_GOURAUD) : NR_VG(ZM, ATTR_FLAT))
+#define NR_VZ(ZM)                                            \
+    (mode == ATTR_TEX_PERSP ? NR_VG(ZM, ATTR_TEX_PERSP)      \
+     : mode == ATTR_TEX     ? NR_VG(ZM, ATTR_TEX)            \
+     : mode == ATTR_GOURAUD ? NR_VG(ZM, ATTR_GOURAUD)        \
+                            : NR_VG(ZM, ATTR_FLAT))
     if (zmode == 1) NR_VZ(1);
     else if (zmode == 2) NR_VZ(2);
     else NR_VZ(0);
@@ -2585,8 +2590,8 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
 // ordered: the batch is rasterised by the ordered raster (blending, Z test
 // without write...): the same binning, each tile's list sorted in LDS.
 void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, bool ordered,
-               const TexView* tex) {
-    FrameParams fp = frame_params(ctx, src, tex);
+               const TexView* tex, const f64* q) {
+    FrameParams fp = frame_params(ctx, src, tex, q);
     if (ctx->frameOutput && fp.pendColor) {
         const size_t n = (size_t)nr_frame_bytes(ctx);
         if (n <= ctx->frameU8cap) fp.frameU8 = ctx->frameU8;

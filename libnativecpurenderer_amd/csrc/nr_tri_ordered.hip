@@ -99,6 +99,7 @@ enum {
     S_C0,                                      // colour c0[4] (flat: the colour; textured: u0 v0)
     S_D1 = S_C0 + 4,                           // c1-c0 [4] (Gouraud; textured: u1-u0 v1-v0)
     S_D2 = S_D1 + 4,                           // c2-c0 [4] (Gouraud; textured: u2-u0 v2-v0)
+    // (perspective textured: a0 b0 q0 | a1-a0 b1-b0 q1-q0 | a2-a0 b2-b0 q2-q0, a = u q, b = v q)
     // flat: ApplyPixel's per-triangle terms (cpp:529-535), formed once at setup
     S_FR = S_D2 + 4, S_FG, S_FB, S_FA,         // src * colourTransform
     S_OM, S_RA, S_GA, S_BA,                    // 1 - a, src * a
@@ -129,13 +130,15 @@ __device__ __forceinline__ u64 window_bits(int xs, int xe) {
 // MODE (AttrMode): a textured batch interpolates (u, v) where a Gouraud batch
 // interpolates its colour, fetches the texel (tex_index; rgb, and alpha from
 // an RGBA texture) and blends it by the same ApplyPixel arithmetic.  Its colour
-// varies over the triangle, so it takes none of the flat shortcuts.
+// varies over the triangle, so it takes none of the flat shortcuts.  A
+// perspective textured batch (ATTR_TEX_PERSP) interpolates U = u q, V = v q and
+// Q = q in three of those slots and samples at (U / Q, V / Q) (as U * (1 / Q)).
 // 4 waves per SIMD (6: 80 VGPRs, 85 spilled -- C5 raster 740 -> 1355 us)
 template <int MODE, bool DEPTH, bool COUNT, bool RGBA, bool BINNED>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_tile_raster(const FrameParams fp, const u32* __restrict__ list,
                                                     const u32* __restrict__ tstart, const u32* __restrict__ tend,
                                                     const f64* __restrict__ rec, const u32* __restrict__ plan) {
-    constexpr bool GOURAUD = MODE == ATTR_GOURAUD, TEX = MODE == ATTR_TEX;
+    constexpr bool GOURAUD = MODE == ATTR_GOURAUD, TEX = attr_textured(MODE), PERSP = MODE == ATTR_TEX_PERSP;
     constexpr bool FLATC = MODE == ATTR_FLAT;   // one colour per triangle: the per-triangle blend terms apply
     const int tile = blockIdx.x;
     const int tx = tile % fp.tiles_x, ty = tile / fp.tiles_x;
@@ -240,7 +243,17 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                 zok = !fp.depthWrite && zb < zTileMin;   // zpass_all
                 ZPASS[sb][k] = zok;
             }
-            if (TEX) {
+            if (PERSP) {
+                f64 uv[6];
+                load_tri_xy(fp.src.uv(), t, uv);
+                const f64* qs = fp.q + t * 3;
+                const f64 q0 = qs[0], q1 = qs[1], q2 = qs[2];
+                const f64 a0 = uv[0] * q0, b0 = uv[1] * q0, a1 = uv[2] * q1, b1 = uv[3] * q1;
+                const f64 a2 = uv[4] * q2, b2 = uv[5] * q2;
+                S[sb][S_C0][k] = a0; S[sb][S_C0 + 1][k] = b0; S[sb][S_C0 + 2][k] = q0;
+                S[sb][S_D1][k] = a1 - a0; S[sb][S_D1 + 1][k] = b1 - b0; S[sb][S_D1 + 2][k] = q1 - q0;
+                S[sb][S_D2][k] = a2 - a0; S[sb][S_D2 + 1][k] = b2 - b0; S[sb][S_D2 + 2][k] = q2 - q0;
+            } else if (TEX) {
                 f64 uv[6];
                 load_tri_xy(fp.src.uv(), t, uv);
                 S[sb][S_C0][k] = uv[0]; S[sb][S_C0 + 1][k] = uv[1];
@@ -439,8 +452,14 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                     if (!(zq < cz[r])) continue;
                 }
                 if (TEX) {
-                    const f64 u = S[sb][S_C0 + 0][k] + S[sb][S_D1 + 0][k] * w1 + S[sb][S_D2 + 0][k] * w2;
-                    const f64 v = S[sb][S_C0 + 1][k] + S[sb][S_D1 + 1][k] * w1 + S[sb][S_D2 + 1][k] * w2;
+                    f64 u = S[sb][S_C0 + 0][k] + S[sb][S_D1 + 0][k] * w1 + S[sb][S_D2 + 0][k] * w2;
+                    f64 v = S[sb][S_C0 + 1][k] + S[sb][S_D1 + 1][k] * w1 + S[sb][S_D2 + 1][k] * w2;
+                    if (PERSP) {   // (u, v hold U, V)
+                        const f64 Q = S[sb][S_C0 + 2][k] + S[sb][S_D1 + 2][k] * w1 + S[sb][S_D2 + 2][k] * w2;
+                        const f64 rq = 1.0 / Q;
+                        u = u * rq;
+                        v = v * rq;
+                    }
                     const f64* tq = fp.tex.ptr + tex_index(fp.tex, u, v);
                     f64 R = tq[0], G = tq[1], B = tq[2];
                     f64 A = fp.tex.ipp == 4 ? tq[3] : 1.0;
@@ -567,7 +586,10 @@ void launch_raster_c(const FrameParams& fp, const u32* list, const u32* ts, cons
                      hipStream_t s, const f64* rec, const u32* plan = nullptr, hipEvent_t start = nullptr,
                      hipEvent_t stop = nullptr) {
     const bool g = fp.src.mode == ATTR_GOURAUD, t = fp.src.mode == ATTR_TEX, d = fp.depthTest != 0;
-    if (t && d) launch_raster<ATTR_TEX, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    const bool p = fp.src.mode == ATTR_TEX_PERSP;
+    if (p && d) launch_raster<ATTR_TEX_PERSP, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (p) launch_raster<ATTR_TEX_PERSP, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (t && d) launch_raster<ATTR_TEX, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
     else if (t) launch_raster<ATTR_TEX, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
     else if (g && d) launch_raster<ATTR_GOURAUD, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
     else if (g) launch_raster<ATTR_GOURAUD, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
@@ -587,13 +609,14 @@ void launch_ordered_binned(const FrameParams& fp, const u32* list, const u32* of
     else launch_raster_c<false, true>(fp, list, off, nullptr, ntiles, s, rec, plan, start, stop);
 }
 
-void draw_ordered(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, const TexView* tex) {
+void draw_ordered(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, const TexView* tex,
+                  const f64* q) {
     const i64 ntiles = (i64)((ctx->width + TW - 1) / TW) * ((ctx->height + TH - 1) / TH);
     if (ntiles <= ORD_BIN_TILES) {
-        draw_free(ctx, src, tb, callerOwned, true, tex);
+        draw_free(ctx, src, tb, callerOwned, true, tex, q);
         return;
     }
-    FrameParams fp = frame_params(ctx, src, tex);
+    FrameParams fp = frame_params(ctx, src, tex, q);
     draw_ordered_sorted(ctx, src, fp, bin_params(fp));
 }
 
@@ -646,6 +669,7 @@ void ordered_sorted_kernels(RenderContext* ctx, const TriSrc& src, const FramePa
         ba.src = a; bb.src = b;
         FrameParams fa = fp, fb = fp;
         fa.src = a; fb.src = b;
+        if (fp.q) fb.q = fp.q + a.n * 3;
         // (fb keeps the frame output: the second half rewrites the tiles it covers)
         ordered_sorted_kernels(ctx, a, fa, ba);
         if (fa.fragCounter) {   // fragments of the first half, then the counter restarts for the second

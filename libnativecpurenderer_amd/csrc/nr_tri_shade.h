@@ -29,7 +29,9 @@ namespace nrtri {
 // Doubles of a shading record (build_record): Gouraud sx0 sy0 e1x e1y e2x e2y
 // inv | c0 rgb | (c1-c0) rgb | (c2-c0) rgb; flat rgb; textured the same 7
 // geometry terms | u0 v0 | (u1-u0) (v1-v0) | (u2-u0) (v2-v0): 13 doubles in
-// the Gouraud record's 16-double slot.  MODE: AttrMode.
+// the Gouraud record's 16-double slot; perspective textured the 7 geometry
+// terms | a0 b0 | (a1-a0) (b1-b0) | (a2-a0) (b2-b0) | q0 (q1-q0) (q2-q0) with
+// a_k = u_k * q_k, b_k = v_k * q_k: all 16.  MODE: AttrMode.
 template <int MODE>
 struct RecLen {
     static constexpr int REC = MODE != ATTR_FLAT ? 16 : 3;
@@ -88,7 +90,8 @@ __device__ __forceinline__ void store_clear(const FrameParams& fp, i64 p, i64 px
 template <int MODE>
 struct RecordSrc {
     f64 p[MODE != ATTR_FLAT ? 6 : 1];
-    f64 c[MODE == ATTR_GOURAUD ? 9 : (MODE == ATTR_TEX ? 6 : 3)];   // textured: the six uv
+    // textured: the six uv; perspective textured: the six uv, then the three q
+    f64 c[MODE == ATTR_GOURAUD || MODE == ATTR_TEX_PERSP ? 9 : (MODE == ATTR_TEX ? 6 : 3)];
 };
 
 template <int MODE>
@@ -97,6 +100,15 @@ __device__ __forceinline__ void load_record_src(const FrameParams& fp, i64 t, Re
     if constexpr (MODE != ATTR_FLAT) load_tri_xy(fp.src.xy, t, s.p);
     if constexpr (MODE == ATTR_TEX) {
         load_tri_xy(fp.src.uv(), t, s.c);   // (the same 3 x 16-byte layout)
+        return;
+    }
+    if constexpr (MODE == ATTR_TEX_PERSP) {
+        f64 uv[6];
+        load_tri_xy(fp.src.uv(), t, uv);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s.c[k] = uv[k];
+        const f64* q = fp.q + t * 3;   // (8-byte aligned only: n*3 doubles per batch, like z)
+        s.c[6] = q[0]; s.c[7] = q[1]; s.c[8] = q[2];
         return;
     }
     const int nv = GOURAUD ? 3 : 1, stride = GOURAUD ? 12 : 4;
@@ -121,6 +133,21 @@ __device__ __forceinline__ void build_record(const FrameParams& fp, const Record
         r[7] = s.c[0]; r[8] = s.c[1];
         r[9] = s.c[2] - s.c[0]; r[10] = s.c[3] - s.c[1];
         r[11] = s.c[4] - s.c[0]; r[12] = s.c[5] - s.c[1];
+    } else if constexpr (MODE == ATTR_TEX_PERSP) {
+        f64 sx[3], sy[3];
+#pragma unroll
+        for (int v = 0; v < 3; ++v) nr_xform(fp.m, s.p[2 * v], s.p[2 * v + 1], sx[v], sy[v]);
+        const f64 e1x = sx[1] - sx[0], e1y = sy[1] - sy[0], e2x = sx[2] - sx[0], e2y = sy[2] - sy[0];
+        r[0] = sx[0]; r[1] = sy[0]; r[2] = e1x; r[3] = e1y; r[4] = e2x; r[5] = e2y;
+        r[6] = 1.0 / (e1x * e2y - e2x * e1y);
+        // a_k = u_k * q_k, b_k = v_k * q_k (rounded products), then the differences
+        const f64 a0 = s.c[0] * s.c[6], b0 = s.c[1] * s.c[6];
+        const f64 a1 = s.c[2] * s.c[7], b1 = s.c[3] * s.c[7];
+        const f64 a2 = s.c[4] * s.c[8], b2 = s.c[5] * s.c[8];
+        r[7] = a0; r[8] = b0;
+        r[9] = a1 - a0; r[10] = b1 - b0;
+        r[11] = a2 - a0; r[12] = b2 - b0;
+        r[13] = s.c[6]; r[14] = s.c[7] - s.c[6]; r[15] = s.c[8] - s.c[6];
     } else if constexpr (MODE == ATTR_GOURAUD) {
         f64 sx[3], sy[3];
 #pragma unroll
@@ -157,6 +184,24 @@ __device__ __forceinline__ i64 record_texel(const TexView& tv, const f64* r, i64
     const f64 v = r[8] + r[10] * w1 + r[12] * w2;
     return tex_index(tv, u, v);
 }
+// ... from a perspective textured record: U, V, Q by that expression, then the
+// divide (IEEE) and the two products, u = U * (1 / Q), v = V * (1 / Q).  Any Q
+// (zero, negative, non-finite) gives a defined texel: tex_index clamps.
+__device__ __forceinline__ i64 record_texel_persp(const TexView& tv, const f64* r, i64 px, i64 py) {
+    const f64 dx = (f64)px - r[0], dy = (f64)py - r[1];
+    const f64 w1 = (dx * r[5] - r[4] * dy) * r[6];
+    const f64 w2 = (r[2] * dy - dx * r[3]) * r[6];
+    const f64 U = r[7] + r[9] * w1 + r[11] * w2;
+    const f64 V = r[8] + r[10] * w1 + r[12] * w2;
+    const f64 Q = r[13] + r[14] * w1 + r[15] * w2;
+    const f64 rq = 1.0 / Q;
+    return tex_index(tv, U * rq, V * rq);
+}
+template <int MODE>
+__device__ __forceinline__ i64 record_texel_of(const TexView& tv, const f64* r, i64 px, i64 py) {
+    if constexpr (MODE == ATTR_TEX_PERSP) return record_texel_persp(tv, r, px, py);
+    else return record_texel(tv, r, px, py);
+}
 
 // Colour of pixel (px, py) from a record.  (Textured: the texel's rgb from
 // the view tv, an ordinary cached load; alpha is 1 -- only textures without
@@ -166,6 +211,9 @@ __device__ __forceinline__ void record_colour(const TexView& tv, const f64* r, i
                                               f64& cb, f64& ca) {
     if constexpr (MODE == ATTR_TEX) {
         const f64* q = tv.ptr + record_texel(tv, r, px, py);
+        cr = q[0]; cg = q[1]; cb = q[2]; ca = 1.0;
+    } else if constexpr (MODE == ATTR_TEX_PERSP) {
+        const f64* q = tv.ptr + record_texel_persp(tv, r, px, py);
         cr = q[0]; cg = q[1]; cb = q[2]; ca = 1.0;
     } else if (MODE == ATTR_GOURAUD) {
         const f64 dx = (f64)px - r[0], dy = (f64)py - r[1];

@@ -296,13 +296,15 @@ class RenderContext:
                 raise ValueError("a colour TriangleBuffer takes no texture")
             lib.DrawTriangleBuffer(self._ptr, buf._ptr)
 
-    def draw_textured_triangles(self, tex: "Texture", xy, uv, z=None):
+    def draw_textured_triangles(self, tex: "Texture", xy, uv, z=None, q=None):
         """Draws n textured triangles in the current transform.
 
         xy: (n, 3, 2) or (n, 6) vertex positions; uv: (n, 3, 2) or (n, 6)
         per-vertex texture coordinates in texels of `tex` (interpolated like a
         Gouraud channel, sampled with draw_texture's nearest sampler, tinted
-        by the colour transform); z: (n, 3) depths in [0, 1] or None."""
+        by the colour transform); z: (n, 3) depths in [0, 1] or None; q: (n, 3)
+        per-vertex 1/w for perspective-correct sampling at (U / Q, V / Q) with
+        U, V, Q interpolated from u q, v q, q (None: affine, as before)."""
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 6)
         n = xy.shape[0]
         uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(n, 6)
@@ -310,15 +312,23 @@ class RenderContext:
         if z is not None:
             z = np.ascontiguousarray(z, dtype=np.float64).reshape(n, 3)
             zp = _f64_ptr(z)
+        if q is not None:
+            q = np.ascontiguousarray(q, dtype=np.float64).reshape(n, 3)
+            lib.DrawTexturedTrianglesPerspective(self._ptr, tex._ptr, _f64_ptr(xy), zp, _f64_ptr(uv), _f64_ptr(q), n)
+            return
         lib.DrawTexturedTriangles(self._ptr, tex._ptr, _f64_ptr(xy), zp, _f64_ptr(uv), n)
 
-    def draw_textured_triangles_device(self, tex: "Texture", xy, uv, n: int, z=None):
+    def draw_textured_triangles_device(self, tex: "Texture", xy, uv, n: int, z=None, q=None):
         """DrawTexturedTrianglesDevice: xy / uv / z are device addresses or
-        objects with .data_ptr(), as for draw_triangles_device."""
+        objects with .data_ptr(), as for draw_triangles_device; with q (the
+        per-vertex 1/w, n*3) DrawTexturedTrianglesPerspectiveDevice."""
         def addr(a):
             if a is None:
                 return None
             return a.data_ptr() if hasattr(a, "data_ptr") else int(a)
+        if q is not None:
+            lib.DrawTexturedTrianglesPerspectiveDevice(self._ptr, tex._ptr, addr(xy), addr(z), addr(uv), addr(q), int(n))
+            return
         lib.DrawTexturedTrianglesDevice(self._ptr, tex._ptr, addr(xy), addr(z), addr(uv), int(n))
 
     @staticmethod
@@ -399,6 +409,35 @@ class RenderContext:
             raise RuntimeError("AssembleMeshClipped failed: " + _lib.last_error())
         k = nout.value
         return xy[:k].copy(), z[:k].copy(), attr[:k].copy()
+
+    # perspective-correct texture mapping of textured mesh draws: per context,
+    # not saved / restored, not recorded; colour meshes ignore it
+    def set_mesh_perspective(self, on: bool):
+        """On: draw_mesh of a textured Mesh carries 1/cw from the vertex stage
+        to the rasters and samples perspective-correct (off: affine in screen
+        space, the default)."""
+        lib.SetMeshPerspective(self._ptr, bool(on))
+
+    def mesh_perspective(self) -> bool:
+        return bool(lib.GetMeshPerspective(self._ptr))
+
+    def assemble_mesh_perspective(self, mesh: "Mesh", matrix=None):
+        """(xy (n_out, 6), z (n_out, 3), uv (n_out, 6), q (n_out, 3)): the soup
+        draw_mesh of a textured `mesh` would rasterise under `matrix` and this
+        context's near plane, cull mode and perspective state -- the draw's own
+        kernels (a sync point).  q is 1.0 with the perspective state off."""
+        m, mp = self._matrix16(matrix)
+        cap = 2 * mesh.triangle_count
+        xy = np.empty((cap, 6), dtype=np.float64)
+        z = np.empty((cap, 3), dtype=np.float64)
+        uv = np.empty((cap, 6), dtype=np.float64)
+        q = np.empty((cap, 3), dtype=np.float64)
+        nout = ctypes.c_long(0)
+        if not lib.AssembleMeshPerspective(self._ptr, mesh._ptr, mp, cap, _f64_ptr(xy), _f64_ptr(z), _f64_ptr(uv),
+                                           _f64_ptr(q), ctypes.byref(nout)):
+            raise RuntimeError("AssembleMeshPerspective failed: " + _lib.last_error())
+        k = nout.value
+        return xy[:k].copy(), z[:k].copy(), uv[:k].copy(), q[:k].copy()
 
     # ---- additions: sync, device interop, measurement ------------------
     def flush(self):
