@@ -103,7 +103,11 @@ struct TriScratch {
     DevArray<u32> keys[2], vals[2];                                     // pairs (grown together)
     DevArray<u32> tile_start, tile_end;                                 // per tile (grown together)
     void* temp = nullptr; size_t temp_bytes = 0;                        // hipcub scratch
-    u64* h_total = nullptr;                 // pinned readback: [0] pairs, [1] last count, [2] fragments
+    u64* h_total = nullptr;                 // pinned readback: [0] pairs, [1] last count, [2] fragments, [3] opacity
+    u64* totals() {                         // h_total, allocated on first use (null: hipHostMalloc failed, latched)
+        if (!h_total) NR_CHECK(hipHostMalloc((void**)&h_total, 4 * sizeof(u64)));
+        return h_total;
+    }
     u64* d_frag = nullptr;                  // device fragment counter
     u32* d_flag = nullptr;                  // device non-opaque flag
     // visibility-buffer raster (nr_tri_free.hip).  The binning outputs are

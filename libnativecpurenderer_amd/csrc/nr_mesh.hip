@@ -39,6 +39,7 @@
 
 #include <climits>
 #include <cmath>
+#include <initializer_list>
 #include <string>
 
 struct Mesh {
@@ -410,12 +411,19 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
     return m;
 }
 
-struct Soup { const f64* xy; const f64* z; const f64* q; };   // q: a perspective draw's 1/w (else null)
+// `matrix`, or the identity for null.
+Mat4 mat4_of(const f64* matrix) {
+    Mat4 M = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
+    if (matrix)
+        for (int k = 0; k < 16; ++k) M.m[k] = matrix[k];
+    return M;
+}
 
 // The vertex stage and the assembly of `m` under `matrix` into ctx's mesh
-// staging, on the context's stream (m->n > 0).  False: the staging could not
-// be grown (error latched).  persp: the q-writing instances (out->q).
-bool assemble(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out, bool persp = false) {
+// staging, on the context's stream (m->n > 0): *out is the soup with the mesh's
+// own attributes.  False: the staging could not be grown (error latched).
+// persp: the q-writing instances (out->q, else null).
+bool assemble(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out, bool persp) {
     nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
     TriScratch& sc = ctx->tri;
     const size_t nv = (size_t)m->nv, n = (size_t)m->n;
@@ -427,37 +435,22 @@ bool assemble(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out, b
     f64* xy = vz + vzn + (persp ? vzn : 0);
     f64* z = xy + n * 6;
     f64* q = persp ? z + n * 3 : nullptr;
-    Mat4 M = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
-    if (matrix)
-        for (int k = 0; k < 16; ++k) M.m[k] = matrix[k];
+    const auto vertex = persp ? k_mesh_vertex<true> : k_mesh_vertex<false>;
+    const auto gather = persp ? k_mesh_assemble<true> : k_mesh_assemble<false>;
     hipEvent_t a, b;
     nr_timing_begin(ctx, NRK_MESH_VERTEX, &a, &b);
-    if (persp)
-        hipLaunchKernelGGL(k_mesh_vertex<true>, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv, M,
-                           reinterpret_cast<double2*>(vxy), vz, vq);
-    else
-        hipLaunchKernelGGL(k_mesh_vertex<false>, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv, M,
-                           reinterpret_cast<double2*>(vxy), vz, vq);
+    hipLaunchKernelGGL(vertex, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv, mat4_of(matrix),
+                       reinterpret_cast<double2*>(vxy), vz, vq);
     NR_CHECK(hipGetLastError());
     nr_timing_end(ctx, NRK_MESH_VERTEX, a, b);
     nr_timing_begin(ctx, NRK_MESH_ASSEMBLE, &a, &b);
-    if (persp)
-        hipLaunchKernelGGL(k_mesh_assemble<true>, dim3(blocks_for(m->n * 3)), dim3(256), 0, ctx->stream, m->idx,
-                           m->n * 3, reinterpret_cast<const double2*>(vxy), vz, reinterpret_cast<double2*>(xy), z, vq, q);
-    else
-        hipLaunchKernelGGL(k_mesh_assemble<false>, dim3(blocks_for(m->n * 3)), dim3(256), 0, ctx->stream, m->idx,
-                           m->n * 3, reinterpret_cast<const double2*>(vxy), vz, reinterpret_cast<double2*>(xy), z, vq, q);
+    hipLaunchKernelGGL(gather, dim3(blocks_for(m->n * 3)), dim3(256), 0, ctx->stream, m->idx, m->n * 3,
+                       reinterpret_cast<const double2*>(vxy), vz, reinterpret_cast<double2*>(xy), z, vq, q);
     NR_CHECK(hipGetLastError());
     nr_timing_end(ctx, NRK_MESH_ASSEMBLE, a, b);
-    out->xy = xy;
-    out->z = z;
-    out->q = q;
+    *out = Soup{xy, z, m->attr, q, m->n};
     return true;
 }
-
-// What a mesh draw hands to the rasters: n triangles and their attributes.
-// q: the corners' 1/w of a perspective textured draw (else null).
-struct DrawSoup { const f64* xy; const f64* z; const f64* attr; i64 n; const f64* q; };
 
 // A textured mesh drawn with the context's perspective state on; colour meshes ignore the state.
 inline bool persp_draw(const RenderContext* ctx, const Mesh* m) { return ctx->meshPersp && m->mode == ATTR_TEX; }
@@ -469,7 +462,7 @@ inline bool clip_stage_on(const RenderContext* ctx) { return ctx->meshNear > 0 |
 // the total n_out has been read back, the one wait of such a draw -- the emit
 // pass into ctx's mesh staging, sized to n_out.  out->n == 0: nothing is left
 // to draw (no staging is touched).  False: scratch could not be grown (latched).
-bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, DrawSoup* out, bool persp) {
+bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out, bool persp) {
     if (m->n > (i64)INT_MAX) return fail("mesh clip stage", "more than 2^31 - 1 triangles");
     nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
     TriScratch& sc = ctx->tri;
@@ -481,17 +474,14 @@ bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Draw
     size_t need = 0;
     NR_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, cnt, off, (int)m->n, ctx->stream));
     if (!grow_temp(sc, need > 0 ? need : 1)) return false;
-    if (!sc.h_total) NR_CHECK(hipHostMalloc((void**)&sc.h_total, 4 * sizeof(u64)));
-    if (!sc.h_total) return fail("mesh clip stage", "hipHostMalloc failed");
-    Mat4 M = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
-    if (matrix)
-        for (int k = 0; k < 16; ++k) M.m[k] = matrix[k];
+    u32* h = reinterpret_cast<u32*>(sc.totals());
+    if (!h) return fail("mesh clip stage", "hipHostMalloc failed");
     const f64 wNear = ctx->meshNear;
     const double2* clip = reinterpret_cast<const double2*>(sc.mclip.p);
     hipEvent_t a, b;
     nr_timing_begin(ctx, NRK_MESH_CLIP_VERTEX, &a, &b);
-    hipLaunchKernelGGL(k_mesh_clip_vertex, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv, M,
-                       reinterpret_cast<double2*>(sc.mclip.p));
+    hipLaunchKernelGGL(k_mesh_clip_vertex, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv,
+                       mat4_of(matrix), reinterpret_cast<double2*>(sc.mclip.p));
     NR_CHECK(hipGetLastError());
     nr_timing_end(ctx, NRK_MESH_CLIP_VERTEX, a, b);
     nr_timing_begin(ctx, NRK_MESH_CLIP_COUNT, &a, &b);
@@ -503,13 +493,11 @@ bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Draw
     NR_CHECK(hipcub::DeviceScan::ExclusiveSum(sc.temp, need, cnt, off, (int)m->n, ctx->stream));
     nr_timing_end(ctx, NRK_MESH_CLIP_SCAN, a, b);
     // n_out = the last offset + the last count (at most 2n < 2^32): the sync point of a clipped or culled draw
-    u32* h = reinterpret_cast<u32*>(&sc.h_total[0]);
     NR_CHECK(hipMemcpyAsync(&h[0], off + (n - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
     NR_CHECK(hipMemcpyAsync(&h[1], cnt + (n - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("mesh clip stage", "the count could not be read back");
     const size_t nout = (size_t)h[0] + (size_t)h[1];
-    out->xy = out->z = out->attr = out->q = nullptr;
-    out->n = (i64)nout;
+    *out = Soup{nullptr, nullptr, nullptr, nullptr, (i64)nout};
     if (nout == 0) return true;
     if (nout > 2 * n) return fail("mesh clip stage", "inconsistent triangle count");   // (never: the counts are 0, 1 or 2)
     const size_t stride = (size_t)nrtri::attr_stride(m->mode);
@@ -519,44 +507,48 @@ bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Draw
     f64* z = xy + nout * 6;
     f64* attr = z + zn;
     f64* q = persp ? attr + nout * stride : nullptr;
+    const auto emit = m->mode == nrtri::ATTR_GOURAUD ? k_mesh_clip_emit<2>
+                      : m->mode != nrtri::ATTR_TEX   ? k_mesh_clip_emit<0>
+                      : persp                        ? k_mesh_clip_emit<1, true>
+                                                     : k_mesh_clip_emit<1>;
     nr_timing_begin(ctx, NRK_MESH_CLIP_EMIT, &a, &b);
-    const dim3 grid(blocks_for(m->n)), block(256);
-    const double2* mattr = reinterpret_cast<const double2*>(m->attr);
-    double2* xy2 = reinterpret_cast<double2*>(xy);
-    double2* attr2 = reinterpret_cast<double2*>(attr);
-    if (m->mode == nrtri::ATTR_GOURAUD)
-        hipLaunchKernelGGL(k_mesh_clip_emit<2>, grid, block, 0, ctx->stream, m->idx, m->n, clip, mattr, wNear, keep, off,
-                           xy2, z, attr2, q);
-    else if (m->mode == nrtri::ATTR_TEX && persp)
-        hipLaunchKernelGGL((k_mesh_clip_emit<1, true>), grid, block, 0, ctx->stream, m->idx, m->n, clip, mattr, wNear,
-                           keep, off, xy2, z, attr2, q);
-    else if (m->mode == nrtri::ATTR_TEX)
-        hipLaunchKernelGGL(k_mesh_clip_emit<1>, grid, block, 0, ctx->stream, m->idx, m->n, clip, mattr, wNear, keep, off,
-                           xy2, z, attr2, q);
-    else
-        hipLaunchKernelGGL(k_mesh_clip_emit<0>, grid, block, 0, ctx->stream, m->idx, m->n, clip, mattr, wNear, keep, off,
-                           xy2, z, attr2, q);
+    hipLaunchKernelGGL(emit, dim3(blocks_for(m->n)), dim3(256), 0, ctx->stream, m->idx, m->n, clip,
+                       reinterpret_cast<const double2*>(m->attr), wNear, keep, off, reinterpret_cast<double2*>(xy), z,
+                       reinterpret_cast<double2*>(attr), q);
     NR_CHECK(hipGetLastError());
     nr_timing_end(ctx, NRK_MESH_CLIP_EMIT, a, b);
-    out->xy = xy;
-    out->z = z;
-    out->attr = attr;
-    out->q = q;
+    *out = Soup{xy, z, attr, q, (i64)nout};
     return true;
 }
 
 // The soup a draw of `m` rasterises under the context's clip state: the unclipped
 // path's (vertex stage + assembly, the mesh's own attributes) when it is off.
-bool draw_soup(RenderContext* ctx, const Mesh* m, const f64* matrix, DrawSoup* out) {
+bool draw_soup(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out) {
     const bool persp = persp_draw(ctx, m);
-    if (clip_stage_on(ctx)) return assemble_clipped(ctx, m, matrix, out, persp);
-    Soup s;
-    if (!assemble(ctx, m, matrix, &s, persp)) return false;
-    out->xy = s.xy;
-    out->z = s.z;
-    out->q = s.q;
-    out->attr = m->attr;
-    out->n = m->n;
+    return clip_stage_on(ctx) ? assemble_clipped(ctx, m, matrix, out, persp) : assemble(ctx, m, matrix, out, persp);
+}
+
+// Copy-out of the Assemble* entry points: the first k triangles of each part (`per` doubles a triangle; a null
+// source is skipped) to the host, then the wait.
+struct CopyOut { f64* dst; const f64* src; size_t per; };
+void copy_out(RenderContext* ctx, size_t k, std::initializer_list<CopyOut> parts) {
+    for (const CopyOut& c : parts)
+        if (k > 0 && c.src)
+            NR_CHECK(hipMemcpyAsync(c.dst, c.src, k * c.per * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
+    NR_CHECK(hipStreamSynchronize(ctx->stream));
+}
+
+// The checks AssembleMeshClipped and AssembleMeshPerspective (textured: a textured mesh only) share, in their
+// order; *n_out is zeroed once it is known to be there.  outputs: every output array is there.
+bool check_assemble(RenderContext* ctx, const Mesh* m, bool textured, i64 cap, bool outputs, i64* n_out,
+                    const char* what) {
+    if (!m) return fail(what, "NULL mesh");
+    if (textured && m->mode != nrtri::ATTR_TEX) return fail(what, "a colour mesh");
+    if (m->device != ctx->device) return fail(what, "mesh on another device");
+    if (!n_out) return fail(what, "NULL output");
+    *n_out = 0;
+    if (cap < 0) return fail(what, "negative capacity");
+    if (cap > 0 && !outputs) return fail(what, "NULL output");
     return true;
 }
 
@@ -642,12 +634,11 @@ void DrawMesh(RenderContext* ctx, Mesh* m, const f64* matrix16) {
     if (ctx->recording) nr_settle(ctx);   // recorded draws come first
     ctx->meshLastCount = 0;
     if (m->n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
-    DrawSoup s;
+    Soup s;
     if (!draw_soup(ctx, m, matrix16, &s)) return;
     ctx->meshLastCount = s.n;
     if (s.n <= 0) return;   // (clipped or culled away)
-    nrtri::draw(ctx, s.xy, s.z, s.attr, s.n, m->mode, m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED, nullptr,
-                false);
+    nrtri::draw(ctx, soup_batch(s, m->mode, m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED, nullptr, false));
 }
 
 // New: draws a textured mesh sampled from `tex` (chosen per draw).
@@ -658,11 +649,12 @@ void DrawTexturedMesh(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matr
     if (!nrtri::check_texture(ctx, tex, "DrawTexturedMesh")) return;
     ctx->meshLastCount = 0;
     if (m->n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
-    DrawSoup s;
+    Soup s;
     if (!draw_soup(ctx, m, matrix16, &s)) return;
     ctx->meshLastCount = s.n;
     if (s.n <= 0) return;
-    nrtri::draw_textured(ctx, tex, s.xy, s.z, s.attr, s.n, nullptr, false, s.q);   // (s.q: the perspective state)
+    Batch b = soup_batch(s, nrtri::ATTR_TEX, nrtri::OPQ_UNKNOWN, nullptr, false);   // (s.q: the perspective state)
+    nrtri::draw_textured(ctx, tex, b);
 }
 
 // New: the vertex stage and the assembly alone -- exactly the kernels DrawMesh
@@ -675,10 +667,8 @@ bool AssembleMesh(RenderContext* ctx, Mesh* m, const f64* matrix16, f64* xy_out,
     if (m->n <= 0) return true;
     if (!xy_out || !z_out) return fail("AssembleMesh", "NULL output");
     Soup s;
-    if (!assemble(ctx, m, matrix16, &s)) return false;
-    NR_CHECK(hipMemcpyAsync(xy_out, s.xy, (size_t)m->n * 6 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
-    NR_CHECK(hipMemcpyAsync(z_out, s.z, (size_t)m->n * 3 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
-    NR_CHECK(hipStreamSynchronize(ctx->stream));
+    if (!assemble(ctx, m, matrix16, &s, false)) return false;   // (the clip and perspective state are ignored)
+    copy_out(ctx, (size_t)s.n, {{xy_out, s.xy, 6}, {z_out, s.z, 3}});
     return true;
 }
 
@@ -724,25 +714,14 @@ bool GetMeshPerspective(RenderContext* ctx) { return ctx->meshPersp; }
 bool AssembleMeshPerspective(RenderContext* ctx, Mesh* m, const f64* matrix16, i64 cap, f64* xy_out, f64* z_out,
                              f64* uv_out, f64* q_out, i64* n_out) {
     NR_CHECK(hipSetDevice(ctx->device));
-    if (!m) return fail("AssembleMeshPerspective", "NULL mesh");
-    if (m->mode != nrtri::ATTR_TEX) return fail("AssembleMeshPerspective", "a colour mesh");
-    if (m->device != ctx->device) return fail("AssembleMeshPerspective", "mesh on another device");
-    if (!n_out) return fail("AssembleMeshPerspective", "NULL output");
-    *n_out = 0;
-    if (cap < 0) return fail("AssembleMeshPerspective", "negative capacity");
-    if (cap > 0 && (!xy_out || !z_out || !uv_out || !q_out)) return fail("AssembleMeshPerspective", "NULL output");
+    const bool outputs = xy_out && z_out && uv_out && q_out;
+    if (!check_assemble(ctx, m, true, cap, outputs, n_out, "AssembleMeshPerspective")) return false;
     if (m->n <= 0) return true;
-    DrawSoup s;
+    Soup s;
     if (!draw_soup(ctx, m, matrix16, &s)) return false;
     *n_out = s.n;
     const size_t k = (size_t)(s.n < cap ? s.n : cap);
-    if (k > 0) {
-        NR_CHECK(hipMemcpyAsync(xy_out, s.xy, k * 6 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
-        NR_CHECK(hipMemcpyAsync(z_out, s.z, k * 3 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
-        NR_CHECK(hipMemcpyAsync(uv_out, s.attr, k * 6 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
-        if (s.q) NR_CHECK(hipMemcpyAsync(q_out, s.q, k * 3 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    NR_CHECK(hipStreamSynchronize(ctx->stream));
+    copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {uv_out, s.attr, 6}, {q_out, s.q, 3}});
     if (!s.q)
         for (size_t i = 0; i < k * 3; ++i) q_out[i] = 1.0;
     return true;
@@ -759,24 +738,13 @@ i64 GetMeshLastTriangleCount(RenderContext* ctx) { return ctx->meshLastCount; }
 bool AssembleMeshClipped(RenderContext* ctx, Mesh* m, const f64* matrix16, i64 cap, f64* xy_out, f64* z_out,
                          f64* attr_out, i64* n_out) {
     NR_CHECK(hipSetDevice(ctx->device));
-    if (!m) return fail("AssembleMeshClipped", "NULL mesh");
-    if (m->device != ctx->device) return fail("AssembleMeshClipped", "mesh on another device");
-    if (!n_out) return fail("AssembleMeshClipped", "NULL output");
-    *n_out = 0;
-    if (cap < 0) return fail("AssembleMeshClipped", "negative capacity");
-    if (cap > 0 && (!xy_out || !z_out || !attr_out)) return fail("AssembleMeshClipped", "NULL output");
+    if (!check_assemble(ctx, m, false, cap, xy_out && z_out && attr_out, n_out, "AssembleMeshClipped")) return false;
     if (m->n <= 0) return true;
-    DrawSoup s;
+    Soup s;
     if (!draw_soup(ctx, m, matrix16, &s)) return false;
     *n_out = s.n;
     const size_t k = (size_t)(s.n < cap ? s.n : cap);
-    if (k > 0) {
-        const size_t stride = (size_t)nrtri::attr_stride(m->mode);
-        NR_CHECK(hipMemcpyAsync(xy_out, s.xy, k * 6 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
-        NR_CHECK(hipMemcpyAsync(z_out, s.z, k * 3 * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
-        NR_CHECK(hipMemcpyAsync(attr_out, s.attr, k * stride * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    NR_CHECK(hipStreamSynchronize(ctx->stream));
+    copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {attr_out, s.attr, (size_t)nrtri::attr_stride(m->mode)}});
     return true;
 }
 

@@ -526,7 +526,42 @@ enum PlanWord {
 
 bool grow_temp(TriScratch& sc, size_t need);
 
-FrameParams frame_params(RenderContext* ctx, const TriSrc& src, const TexView* tex = nullptr, const f64* q = nullptr);
+// Pointers to a triangle soup, on the host or the device: xy n*6, z n*3 or null, the attribute array (colours or
+// uv, by the batch's mode), q n*3 (a perspective textured soup's 1/w per corner) or null.
+struct Soup {
+    const f64* xy;
+    const f64* z;
+    const f64* attr;
+    const f64* q;
+    i64 n;
+};
+
+// What one triangle draw hands to the rasters: the host-side description of a batch, built on the caller's
+// stack and passed by reference down to the snapshot (frame_params).
+// callerOwned is true exactly when some array the batch reads (xy, z, the attributes, q) is still the caller's
+// device memory.  Such a batch is sized exactly inside the call (a host wait for its binning) and never re-run
+// later: after the call returns nothing of the library may read the caller's arrays again.  Arrays of the
+// context's staging, of a TriangleBuffer or of a mesh draw are not the caller's.
+struct Batch {
+    TriSrc src;
+    const f64* q;                                 // ATTR_TEX_PERSP: the corners' 1/w (else null)
+    TexView tex = tex_view(nullptr, 2, 2, false); // textured modes: what draw_textured resolved
+    Opacity opq;
+    TriangleBuffer* tb;   // non-null: the batch is that (immutable) buffer -- its binning may overlap the previous
+                          // raster, and a repeat draw is sized from its known totals
+    bool callerOwned;
+};
+inline Batch soup_batch(const Soup& s, int mode, Opacity opq, TriangleBuffer* tb, bool callerOwned) {
+    Batch b;
+    b.src = TriSrc{s.xy, s.z, s.attr, mode, s.n};
+    b.q = s.q;
+    b.opq = opq;
+    b.tb = tb;
+    b.callerOwned = callerOwned;
+    return b;
+}
+
+FrameParams frame_params(RenderContext* ctx, const Batch& b);
 inline BinParams bin_params(const FrameParams& fp) {   // the binning's view of the same snapshot
     BinParams bp;
     bp.src = fp.src;
@@ -545,11 +580,11 @@ u32* tile_stamps(RenderContext* ctx, i64 ntiles);   // the context's tile stamps
 // ORD_BIN_TILES tiles, each tile's list sorted in LDS (k_tile_sort); the
 // global-sort path (draw_ordered_sorted) otherwise, and for a batch with a tile
 // of more than ORD_SORT_CAP triangles (detected by the plan, re-run)
-void draw_ordered(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned,
-                  const TexView* tex = nullptr, const f64* q = nullptr);
-void draw_ordered_sorted(RenderContext* ctx, const TriSrc& src, const FrameParams& fp, const BinParams& bp);
+void draw_ordered(RenderContext* ctx, const Batch& b);
+// (fp.src == bp.src is the batch)
+void draw_ordered_sorted(RenderContext* ctx, const FrameParams& fp, const BinParams& bp);
 // the same kernels for a deferred re-run (nr_settle): the batch's snapshot only, context flags untouched
-void rerun_ordered_sorted(RenderContext* ctx, const TriSrc& src, const FrameParams& fp, const BinParams& bp);
+void rerun_ordered_sorted(RenderContext* ctx, const FrameParams& fp, const BinParams& bp);
 constexpr u32 ORD_SORT_CAP = 8192;    // longest tile list the ordered raster sorts in LDS
 constexpr int ORD_BIN_TILES = 16384;  // tiles of the binned ordered path (the register plan kernel's limit)
 // binned ordered batches: k_tile_sort sorts each tile's list [off[t], off[t + 1])
@@ -558,25 +593,17 @@ constexpr int ORD_BIN_TILES = 16384;  // tiles of the binned ordered path (the r
 void launch_tile_sort(const u32* off, u32* list, const u32* plan, int ntiles, hipStream_t s, hipEvent_t stop);
 void launch_ordered_binned(const FrameParams& fp, const u32* list, const u32* off, const u32* plan, const f64* rec,
                            int ntiles, hipStream_t s, hipEvent_t start, hipEvent_t stop);
-// tb: the batch is that (immutable) TriangleBuffer, so its binning may overlap
-// the previous raster and a repeat draw is sized from its known totals;
-// callerOwned: the arrays are the caller's device memory (DrawTrianglesDevice),
-// so the batch is sized exactly in the call -- an overflow re-run never reads
-// them after it returns
-void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, bool ordered = false,
-               const TexView* tex = nullptr, const f64* q = nullptr);
+// b.tb and b.callerOwned: see Batch
+void draw_free(RenderContext* ctx, const Batch& b, bool ordered);
 void settle(RenderContext* ctx);
 i64 visible_pairs(RenderContext* ctx);   // pairs kept in the schedule's visible list (0: none)
 
 // the batch entry points behind every triangle draw call (nr_tri.hip), shared with the mesh front end
-// (nr_mesh.hip): draw picks the raster; draw_textured resolves the texture first (check_texture: its
-// preconditions, an error latched under the caller's name `what` when one fails); q: the 1/w array of a
-// perspective textured batch (ATTR_TEX_PERSP), null otherwise
-void draw(RenderContext* ctx, const f64* xy, const f64* z, const f64* attr, i64 n, int mode, Opacity opq,
-          TriangleBuffer* tb = nullptr, bool callerOwned = false, const TexView* tex = nullptr,
-          const f64* q = nullptr);
+// (nr_mesh.hip): draw picks the raster; draw_textured first completes the batch from the texture (its view, the
+// mode by b.q, the opacity by the texture's alpha).  check_texture: a texture's preconditions, an error latched
+// under the caller's name `what` when one fails
+void draw(RenderContext* ctx, const Batch& b);
 bool check_texture(RenderContext* ctx, const Texture* tex, const char* what);
-void draw_textured(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv, i64 n,
-                   TriangleBuffer* tb, bool callerOwned, const f64* q = nullptr);
+void draw_textured(RenderContext* ctx, Texture* tex, Batch& b);
 
 }  // namespace nrtri

@@ -29,13 +29,13 @@ bool grow_temp(TriScratch& sc, size_t need) {
     return true;
 }
 
-FrameParams frame_params(RenderContext* ctx, const TriSrc& src, const TexView* tex, const f64* q) {
+FrameParams frame_params(RenderContext* ctx, const Batch& b) {
     TriScratch& sc = ctx->tri;
-    if (!sc.h_total) NR_CHECK(hipHostMalloc((void**)&sc.h_total, 4 * sizeof(u64)));
+    sc.totals();   // (the batch's readbacks use the record: finish_batch, the ordered raster)
     if (ctx->depthTest) nr_ensure_depth(ctx);
     nr_materialize_tiles(ctx, true, true);   // (a batch starts from whole-frame clear state)
     FrameParams fp;
-    fp.src = src;
+    fp.src = b.src;
     for (int k = 0; k < 6; ++k) fp.m[k] = ctx->m[k];
     for (int k = 0; k < 4; ++k) fp.ct[k] = ctx->ct[k];
     fp.fb = ctx->buffer;
@@ -59,9 +59,9 @@ FrameParams frame_params(RenderContext* ctx, const TriSrc& src, const TexView* t
     fp.tileStamp = nullptr;
     fp.tileEpoch = 0;
     fp.tstamp = nullptr;
-    fp.tex = tex ? *tex : tex_view(nullptr, 2, 2, false);
+    fp.tex = b.tex;
     fp.winMask = nullptr;
-    fp.q = q;
+    fp.q = b.q;
     if (ctx->countFragments) {
         if (!sc.d_frag) NR_CHECK(hipMalloc(&sc.d_frag, sizeof(u64)));
         NR_CHECK(hipMemsetAsync(sc.d_frag, 0, sizeof(u64), ctx->stream));
@@ -177,12 +177,11 @@ __global__ __launch_bounds__(256) void k_opacity(const f64* __restrict__ rgba, i
 Opacity device_opacity(RenderContext* ctx, const TriSrc& src) {
     TriScratch& sc = ctx->tri;
     if (!sc.d_flag) NR_CHECK(hipMalloc(&sc.d_flag, sizeof(u32)));
-    if (!sc.h_total) NR_CHECK(hipHostMalloc((void**)&sc.h_total, 4 * sizeof(u64)));
     NR_CHECK(hipMemsetAsync(sc.d_flag, 0, sizeof(u32), ctx->stream));
     hipLaunchKernelGGL(k_opacity, dim3((unsigned)((src.n + 255) / 256)), dim3(256), 0, ctx->stream, src.rgba(), src.n,
                        src.mode == ATTR_GOURAUD ? 1 : 0, sc.d_flag);
     NR_CHECK(hipGetLastError());
-    u32* h = reinterpret_cast<u32*>(&sc.h_total[3]);
+    u32* h = reinterpret_cast<u32*>(&sc.totals()[3]);
     NR_CHECK(hipMemcpyAsync(h, sc.d_flag, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
     NR_CHECK(hipStreamSynchronize(ctx->stream));
     return *h ? OPQ_BLENDED : OPQ_OPAQUE;
@@ -190,20 +189,16 @@ Opacity device_opacity(RenderContext* ctx, const TriSrc& src) {
 
 }  // namespace
 
-// attr: the batch's colours (mode ATTR_FLAT / ATTR_GOURAUD) or its texture
-// coordinates (ATTR_TEX / ATTR_TEX_PERSP, sampled from *tex; q: the latter's 1/w per corner).
-void draw(RenderContext* ctx, const f64* xy, const f64* z, const f64* attr, i64 n, int mode, Opacity opq,
-          TriangleBuffer* tb, bool callerOwned, const TexView* tex, const f64* q) {
+void draw(RenderContext* ctx, const Batch& b) {
     NR_CHECK(hipSetDevice(ctx->device));
     nr_settle(ctx);   // recorded draws come first (the colour entry points reach here with their list still queued)
-    if (n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
+    if (b.src.n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
     if (!ctx->depthTest) nr_materialize_depth(ctx);
-    TriSrc src;
-    src.xy = xy; src.z = z; src.attr = attr; src.mode = mode; src.n = n;
     const bool freeEligible = ctx->ct[3] == 1 && ctx->forceOrdered == 0;
-    if (freeEligible && opq == OPQ_UNKNOWN) opq = device_opacity(ctx, src);
-    if (freeEligible && opq == OPQ_OPAQUE) draw_free(ctx, src, tb, callerOwned, false, tex, q);
-    else draw_ordered(ctx, src, tb, callerOwned, tex, q);
+    Opacity opq = b.opq;
+    if (freeEligible && opq == OPQ_UNKNOWN) opq = device_opacity(ctx, b.src);
+    if (freeEligible && opq == OPQ_OPAQUE) draw_free(ctx, b, false);
+    else draw_ordered(ctx, b);
 }
 
 // A textured batch: the texture is checked (the sampler's clamp to w-2 / h-2
@@ -223,14 +218,14 @@ bool check_texture(RenderContext* ctx, const Texture* tex, const char* what) {
     return false;
 }
 
-// q non-null: a perspective textured batch (ATTR_TEX_PERSP).
-void draw_textured(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv, i64 n,
-                   TriangleBuffer* tb, bool callerOwned, const f64* q) {
+// b.q non-null: a perspective textured batch (ATTR_TEX_PERSP).
+void draw_textured(RenderContext* ctx, Texture* tex, Batch& b) {
     settle(ctx);   // (a re-run of the pending batch comes before a snapshot of the target)
     TexSrc ts = nr_tex_source(ctx, tex);
-    const TexView tv = tex_view(ts.ptr, tex->width, tex->height, tex->enableAlpha);
-    draw(ctx, xy, z, uv, n, q ? ATTR_TEX_PERSP : ATTR_TEX, tex->enableAlpha ? OPQ_BLENDED : OPQ_OPAQUE, tb, callerOwned,
-         &tv, q);
+    b.tex = tex_view(ts.ptr, tex->width, tex->height, tex->enableAlpha);
+    b.src.mode = b.q ? ATTR_TEX_PERSP : ATTR_TEX;
+    b.opq = tex->enableAlpha ? OPQ_BLENDED : OPQ_OPAQUE;
+    draw(ctx, b);
     if (ts.tmp) {   // (rare: the snapshot must outlive the batch and any re-run of it)
         settle(ctx);
         nr_tex_release(ctx, ts);
@@ -262,21 +257,55 @@ void nr_settle(RenderContext* ctx) {
     nr_flush_commands(ctx);   // recorded draws come after the last batch in program order
 }
 
-// The context's staging array (TriScratch::stage) laid out for a batch of n
-// triangles with ncol attribute doubles each: xy n*6 | z n*3, padded to an even
-// count (keeps the attributes 16-byte aligned) | attributes n*ncol | with
-// `persp` the 1/w array q n*3 (read as single doubles, like z).  The caller
-// has settled the context (a pending batch may still read the array).  False:
-// it could not be grown (error latched).
-struct Stage { f64* xy; f64* z; f64* attr; f64* q; };
-static bool stage_batch(RenderContext* ctx, i64 n, size_t ncol, Stage* st, bool persp = false) {
-    const size_t zn = ((size_t)n * 3 + 1) & ~(size_t)1;
-    if (!ctx->tri.stage.ensure((size_t)n * (6 + ncol) + zn + (persp ? (size_t)n * 3 : 0))) return false;
-    st->xy = ctx->tri.stage;
-    st->z = st->xy + (size_t)n * 6;
-    st->attr = st->z + zn;
-    st->q = persp ? st->attr + (size_t)n * ncol : nullptr;
+// Stages the soup `s` (s.n > 0, ncol attribute doubles per triangle) for a draw and points `s` at what the batch
+// reads; *callerOwned by Batch's rule.  False: the staging array could not be grown (error latched).
+//   host arrays: all of them are copied into the context's staging array (TriScratch::stage) -- xy n*6 | z n*3,
+//     padded to an even count (keeps the attributes 16-byte aligned) | attributes n*ncol | q n*3 -- and the copy
+//     is waited for, so nothing is the caller's afterwards;
+//   device arrays: the kernels load positions and attributes as 16-byte vectors, so when xy or the attribute
+//     array is not 16-byte aligned those two are re-staged (device-to-device); z and q, read as single
+//     doubles, stay the caller's; aligned arrays are used in place.
+// The array is overwritten only after settle: a pending batch may still read it.
+static bool stage_soup(RenderContext* ctx, Soup& s, size_t ncol, bool onDevice, bool* callerOwned) {
+    *callerOwned = onDevice;
+    if (onDevice && !(((uintptr_t)s.xy | (uintptr_t)s.attr) & 15)) return true;
+    NR_CHECK(hipSetDevice(ctx->device));
+    settle(ctx);
+    const size_t n = (size_t)s.n, zn = (n * 3 + 1) & ~(size_t)1;
+    const bool all = !onDevice;
+    if (!ctx->tri.stage.ensure(n * (6 + ncol) + zn + (all && s.q ? n * 3 : 0))) return false;
+    f64* const xy = ctx->tri.stage;
+    f64* const z = xy + n * 6;
+    f64* const attr = z + zn;
+    f64* const q = attr + n * ncol;
+    const hipMemcpyKind kind = onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    NR_CHECK(hipMemcpyAsync(xy, s.xy, n * 6 * sizeof(f64), kind, ctx->stream));
+    if (all && s.z) NR_CHECK(hipMemcpyAsync(z, s.z, n * 3 * sizeof(f64), kind, ctx->stream));
+    NR_CHECK(hipMemcpyAsync(attr, s.attr, n * ncol * sizeof(f64), kind, ctx->stream));
+    if (all && s.q) NR_CHECK(hipMemcpyAsync(q, s.q, n * 3 * sizeof(f64), kind, ctx->stream));
+    if (all) NR_CHECK(hipStreamSynchronize(ctx->stream));   // caller may reuse its arrays on return
+    s.xy = xy;
+    s.attr = attr;
+    if (all && s.z) s.z = z;
+    if (all && s.q) s.q = q;
+    *callerOwned = onDevice && (s.z || s.q);
     return true;
+}
+
+// The four textured soup entry points, under the caller's name `what`; persp: s.q is required.
+static void draw_textured_soup(RenderContext* ctx, Texture* tex, Soup s, bool persp, bool onDevice, const char* what) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    nr_settle(ctx);   // a pending batch may still read the staging buffer; recorded draws come first
+    if (!check_texture(ctx, tex, what)) return;
+    if (persp && !s.q) {
+        nr_set_error_msg((std::string(what) + ": NULL q").c_str());
+        return;
+    }
+    if (s.n <= 0) return;
+    bool callerOwned;
+    if (!stage_soup(ctx, s, 6, onDevice, &callerOwned)) return;
+    Batch b = soup_batch(s, ATTR_TEX, OPQ_UNKNOWN, nullptr, callerOwned);   // (mode and opacity: draw_textured)
+    draw_textured(ctx, tex, b);
 }
 
 extern "C" {
@@ -312,67 +341,32 @@ void GetDepthBuffer(RenderContext* ctx, u32* out) {
 // visibility path sizes such a batch exactly inside this call (a host wait for
 // its binning), so nothing reads the arrays after that point.
 void DrawTrianglesDevice(RenderContext* ctx, const f64* xy, const f64* z, const f64* rgba, i64 n, bool gouraud) {
-    // the kernels load positions and colours as 16-byte vectors: re-stage
-    // arrays that are not 16-byte aligned (device-to-device copy)
-    if ((((uintptr_t)xy | (uintptr_t)rgba) & 15) && n > 0) {
-        NR_CHECK(hipSetDevice(ctx->device));
-        settle(ctx);
-        const size_t ncol = gouraud ? 12 : 4;
-        Stage st;
-        if (!stage_batch(ctx, n, ncol, &st)) return;
-        NR_CHECK(hipMemcpyAsync(st.xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
-        NR_CHECK(hipMemcpyAsync(st.attr, rgba, (size_t)n * ncol * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
-        draw(ctx, st.xy, z, st.attr, n, gouraud ? ATTR_GOURAUD : ATTR_FLAT, OPQ_UNKNOWN, nullptr, z != nullptr);   // z stays the caller's
-        return;
-    }
-    draw(ctx, xy, z, rgba, n, gouraud ? ATTR_GOURAUD : ATTR_FLAT, OPQ_UNKNOWN, nullptr, true);
+    Soup s{xy, z, rgba, nullptr, n};
+    bool callerOwned = true;
+    if (n > 0 && !stage_soup(ctx, s, gouraud ? 12 : 4, true, &callerOwned)) return;
+    draw(ctx, soup_batch(s, gouraud ? ATTR_GOURAUD : ATTR_FLAT, OPQ_UNKNOWN, nullptr, callerOwned));
 }
 
 // New: triangles from host arrays (copied to HBM first).
 void DrawTriangles(RenderContext* ctx, const f64* xy, const f64* z, const f64* rgba, i64 n, bool gouraud) {
     NR_CHECK(hipSetDevice(ctx->device));
-    settle(ctx);   // a pending batch may still read the staging buffer
+    settle(ctx);
     if (n <= 0) return;
-    const size_t ncol = gouraud ? 12 : 4;
-    Stage st;
-    if (!stage_batch(ctx, n, ncol, &st)) return;
-    NR_CHECK(hipMemcpyAsync(st.xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    if (z) NR_CHECK(hipMemcpyAsync(st.z, z, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    NR_CHECK(hipMemcpyAsync(st.attr, rgba, (size_t)n * ncol * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    NR_CHECK(hipStreamSynchronize(ctx->stream));   // caller may reuse its arrays on return
-    draw(ctx, st.xy, z ? st.z : nullptr, st.attr, n, gouraud ? ATTR_GOURAUD : ATTR_FLAT, host_opacity(rgba, n, gouraud), nullptr,
-         false);
+    Soup s{xy, z, rgba, nullptr, n};
+    bool callerOwned;
+    if (!stage_soup(ctx, s, gouraud ? 12 : 4, false, &callerOwned)) return;
+    draw(ctx, soup_batch(s, gouraud ? ATTR_GOURAUD : ATTR_FLAT, host_opacity(rgba, n, gouraud), nullptr, callerOwned));
 }
 
 // New: textured triangles from host arrays (uv: n*6 texel coordinates).
 void DrawTexturedTriangles(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv, i64 n) {
-    NR_CHECK(hipSetDevice(ctx->device));
-    nr_settle(ctx);   // a pending batch may still read the staging buffer; recorded draws come first
-    if (!check_texture(ctx, tex, "DrawTexturedTriangles") || n <= 0) return;
-    Stage st;
-    if (!stage_batch(ctx, n, 6, &st)) return;
-    NR_CHECK(hipMemcpyAsync(st.xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    if (z) NR_CHECK(hipMemcpyAsync(st.z, z, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    NR_CHECK(hipMemcpyAsync(st.attr, uv, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    NR_CHECK(hipStreamSynchronize(ctx->stream));   // caller may reuse its arrays on return
-    draw_textured(ctx, tex, st.xy, z ? st.z : nullptr, st.attr, n, nullptr, false);
+    draw_textured_soup(ctx, tex, Soup{xy, z, uv, nullptr, n}, false, false, "DrawTexturedTriangles");
 }
 
 // New: textured triangles from device-resident arrays (as DrawTrianglesDevice).
 void DrawTexturedTrianglesDevice(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv,
                                  i64 n) {
-    NR_CHECK(hipSetDevice(ctx->device));
-    nr_settle(ctx);
-    if (!check_texture(ctx, tex, "DrawTexturedTrianglesDevice") || n <= 0) return;
-    if (((uintptr_t)xy | (uintptr_t)uv) & 15) {   // (16-byte vector loads: re-stage, as DrawTrianglesDevice)
-        Stage st;
-        if (!stage_batch(ctx, n, 6, &st)) return;
-        NR_CHECK(hipMemcpyAsync(st.xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
-        NR_CHECK(hipMemcpyAsync(st.attr, uv, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
-        draw_textured(ctx, tex, st.xy, z, st.attr, n, nullptr, z != nullptr);
-        return;
-    }
-    draw_textured(ctx, tex, xy, z, uv, n, nullptr, true);
+    draw_textured_soup(ctx, tex, Soup{xy, z, uv, nullptr, n}, false, true, "DrawTexturedTrianglesDevice");
 }
 
 // New: perspective-correct textured triangles from host arrays (DESIGN.md §3
@@ -381,45 +375,14 @@ void DrawTexturedTrianglesDevice(RenderContext* ctx, Texture* tex, const f64* xy
 // latches an error and draws nothing; otherwise as DrawTexturedTriangles.
 void DrawTexturedTrianglesPerspective(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv,
                                       const f64* q, i64 n) {
-    NR_CHECK(hipSetDevice(ctx->device));
-    nr_settle(ctx);   // a pending batch may still read the staging buffer; recorded draws come first
-    if (!check_texture(ctx, tex, "DrawTexturedTrianglesPerspective")) return;
-    if (!q) {
-        nr_set_error_msg("DrawTexturedTrianglesPerspective: NULL q");
-        return;
-    }
-    if (n <= 0) return;
-    Stage st;
-    if (!stage_batch(ctx, n, 6, &st, true)) return;
-    NR_CHECK(hipMemcpyAsync(st.xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    if (z) NR_CHECK(hipMemcpyAsync(st.z, z, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    NR_CHECK(hipMemcpyAsync(st.attr, uv, (size_t)n * 6 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    NR_CHECK(hipMemcpyAsync(st.q, q, (size_t)n * 3 * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
-    NR_CHECK(hipStreamSynchronize(ctx->stream));   // caller may reuse its arrays on return
-    draw_textured(ctx, tex, st.xy, z ? st.z : nullptr, st.attr, n, nullptr, false, st.q);
+    draw_textured_soup(ctx, tex, Soup{xy, z, uv, q, n}, true, false, "DrawTexturedTrianglesPerspective");
 }
 
 // New: the same from device-resident arrays (as DrawTexturedTrianglesDevice; q
 // stays the caller's like z: it is read as single doubles).
 void DrawTexturedTrianglesPerspectiveDevice(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z,
                                             const f64* uv, const f64* q, i64 n) {
-    NR_CHECK(hipSetDevice(ctx->device));
-    nr_settle(ctx);
-    if (!check_texture(ctx, tex, "DrawTexturedTrianglesPerspectiveDevice")) return;
-    if (!q) {
-        nr_set_error_msg("DrawTexturedTrianglesPerspectiveDevice: NULL q");
-        return;
-    }
-    if (n <= 0) return;
-    if (((uintptr_t)xy | (uintptr_t)uv) & 15) {   // (16-byte vector loads: re-stage, as DrawTrianglesDevice)
-        Stage st;
-        if (!stage_batch(ctx, n, 6, &st)) return;
-        NR_CHECK(hipMemcpyAsync(st.xy, xy, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
-        NR_CHECK(hipMemcpyAsync(st.attr, uv, (size_t)n * 6 * sizeof(f64), hipMemcpyDeviceToDevice, ctx->stream));
-        draw_textured(ctx, tex, st.xy, z, st.attr, n, nullptr, true, q);   // (z and q stay the caller's)
-        return;
-    }
-    draw_textured(ctx, tex, xy, z, uv, n, nullptr, true, q);
+    draw_textured_soup(ctx, tex, Soup{xy, z, uv, q, n}, true, true, "DrawTexturedTrianglesPerspectiveDevice");
 }
 
 // New: a device-resident triangle soup (the H2D point; drawn many times).
@@ -502,8 +465,8 @@ void DrawTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb) {
         return;
     }
     // a TriangleBuffer never changes: its binning may overlap the previous batch's raster
-    draw(ctx, tb->xy, tb->z, tb->rgba, tb->n, tb->gouraud ? ATTR_GOURAUD : ATTR_FLAT,
-         tb->opaque ? OPQ_OPAQUE : OPQ_BLENDED, tb, false);
+    draw(ctx, soup_batch(Soup{tb->xy, tb->z, tb->rgba, nullptr, tb->n}, tb->gouraud ? ATTR_GOURAUD : ATTR_FLAT,
+                         tb->opaque ? OPQ_OPAQUE : OPQ_BLENDED, tb, false));
 }
 
 // New: a textured TriangleBuffer sampled from `tex` (chosen per draw).
@@ -515,7 +478,8 @@ void DrawTexturedTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb, Texture*
     }
     if (ctx->recording) nr_settle(ctx);   // recorded draws come first
     if (!check_texture(ctx, tex, "DrawTexturedTriangleBuffer")) return;
-    draw_textured(ctx, tex, tb->xy, tb->z, tb->uv, tb->n, tb, false);
+    Batch b = soup_batch(Soup{tb->xy, tb->z, tb->uv, nullptr, tb->n}, ATTR_TEX, OPQ_UNKNOWN, tb, false);
+    draw_textured(ctx, tex, b);
 }
 
 // New: count covered on-screen pixel x triangle pairs (the "shaded+Z-tested
@@ -526,11 +490,6 @@ void SetFragmentCounting(RenderContext* ctx, bool on) {
     ctx->fragTotal = 0;
 }
 i64 GetFragmentCount(RenderContext* ctx) { return (i64)ctx->fragTotal; }
-
-// New (testing / A-B measurement): the whole-frame visibility buffer for
-// opaque Z LESS + write batches, 0 automatic (small triangles, NR_GVIS), 1
-// every such batch, 2 never (the tiled k_vis path).
-
 
 // New (testing / A-B measurement): warm binning of a TriangleBuffer drawn
 // again under the key of its last validated binning (one binning pass into
@@ -589,7 +548,7 @@ i64 GetWarmFailureCount(RenderContext* ctx) {
     return (i64)ctx->tri.warmFailures;
 }
 
-// New: which raster the last batch took (1 = order-free tiled, 2 = ordered, 3 = order-free frame buffer).
+// New: which raster the last batch took (1 = order-free tiled, 2 = ordered).
 i64 GetLastRasterPath(RenderContext* ctx) { return ctx->lastPath; }
 
 // New (testing): cap the visibility path's pair list (0 = automatic), to

@@ -1645,44 +1645,32 @@ struct VisArgs {
     WarmCheck wc;   // (a warm batch's checks; zero: a cold batch)
 };
 
+// The instance of a batch among its four shapes -- wide workgroups (never a counting batch) or not, the flattened
+// raster or not -- MARK: a marking frame's.
+template <int Z, bool C, int G, bool MARK>
+auto vis_kernel(bool wide, bool coop) {
+    if (wide) return coop ? k_vis<Z, false, G, true, 2 * VWG, MARK> : k_vis<Z, false, G, false, 2 * VWG, MARK>;
+    return coop ? k_vis<Z, C, G, true, VWG, MARK> : k_vis<Z, C, G, false, VWG, MARK>;
+}
+
 // t: the totals that pick the variant -- this batch's when they are known (a
 // warm, known-size or exact batch), else the last validated batch's
 template <int Z, bool C, int G>
 void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& t, const VisArgs& va, u32 grid,
                 hipStream_t s, hipEvent_t start, hipEvent_t stop) {
-    const WarmCheck wc = va.wc;
     // the flattened raster when the batch has more than COOP_PAIRS tiles per
     // triangle (large triangles), or when there is no history
     const bool coop = sc.coopMode ? sc.coopMode == 1 : (t.n == 0 || (u64)t.pairs > (u64)(COOP_PAIRS * (f64)t.n));
     // wide workgroups when the batch has few pairs (a sharded frame): its
     // dense items run at low occupancy and are latency-bound
     const bool wide = !C && t.n != 0 && t.heavy > 0 && t.heavy < WIDE_HEAVY;
-#define NR_VIS(CO, NTT, ...)                                                                                       \
-    hipExtLaunchKernelGGL((k_vis<Z, __VA_ARGS__>), dim3(grid), dim3(NTT), 0, s, start, stop, 0, fp, va.items,    \
-                          va.list, sc.kslot.p, sc.fdone.p, va.plan, wc)
+    auto kernel = vis_kernel<Z, C, G, false>(wide, coop);
     // a marking frame (fp.winMask; never a counting batch, never LESS without write)
     if constexpr (!C && Z != 2) {
-        if (fp.winMask) {
-            if (wide) {
-                if (coop) NR_VIS(1, 2 * VWG, false, G, true, 2 * VWG, true);
-                else NR_VIS(0, 2 * VWG, false, G, false, 2 * VWG, true);
-            } else if (coop) {
-                NR_VIS(1, VWG, false, G, true, VWG, true);
-            } else {
-                NR_VIS(0, VWG, false, G, false, VWG, true);
-            }
-            return;
-        }
+        if (fp.winMask) kernel = vis_kernel<Z, false, G, true>(wide, coop);
     }
-    if (wide) {
-        if (coop) NR_VIS(1, 2 * VWG, false, G, true, 2 * VWG);
-        else NR_VIS(0, 2 * VWG, false, G, false, 2 * VWG);
-    } else if (coop) {
-        NR_VIS(1, VWG, C, G, true, VWG);
-    } else {
-        NR_VIS(0, VWG, C, G, false, VWG);
-    }
-#undef NR_VIS
+    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(wide ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.items, va.list,
+                          sc.kslot.p, sc.fdone.p, va.plan, va.wc);
 }
 
 // k_vis' ZMODE of a batch: 0 no test, 1 LESS + write, 2 LESS without write
@@ -1711,8 +1699,7 @@ static void launch_vis_any(const FrameParams& fp, const TriScratch& sc, const Ba
 
 // Everything a batch needs to be re-run after an overflow (nr_settle).
 struct PendingBatch {
-    TriSrc src;
-    FrameParams fp;
+    FrameParams fp;   // (fp.src == bp.src: the batch's arrays)
     BinParams bp;
     int set;
     u32 seq;
@@ -2589,9 +2576,9 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
 
 // ordered: the batch is rasterised by the ordered raster (blending, Z test
 // without write...): the same binning, each tile's list sorted in LDS.
-void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, bool ordered,
-               const TexView* tex, const f64* q) {
-    FrameParams fp = frame_params(ctx, src, tex, q);
+void draw_free(RenderContext* ctx, const Batch& b, bool ordered) {
+    TriangleBuffer* const tb = b.tb;
+    FrameParams fp = frame_params(ctx, b);
     if (ctx->frameOutput && fp.pendColor) {
         const size_t n = (size_t)nr_frame_bytes(ctx);
         if (n <= ctx->frameU8cap) fp.frameU8 = ctx->frameU8;
@@ -2603,7 +2590,7 @@ void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool c
     // so does a batch from the caller's device arrays: a deferred overflow
     // re-run (settle, at the next call) could read them after the caller has
     // synchronised and released or rewritten them
-    const bool exact = fp.fragCounter != nullptr || callerOwned;
+    const bool exact = fp.fragCounter != nullptr || b.callerOwned;
     TriScratch& sc = ctx->tri;
     // A TriangleBuffer drawn again under the binning key of its last validated
     // draw has the same pair total: the list is sized to hold it, so the plan's
@@ -2620,7 +2607,7 @@ void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool c
                        !sc.capOverride && memcmp(&tb->knownKey, &key, sizeof key) == 0;
     if (known && !exact) {   // this batch's totals pick the k_vis variant (launch_vis)
         sc.last = tb->knownTotals;
-        sc.last.n = (u64)src.n;
+        sc.last.n = (u64)fp.src.n;
     }
     // warm: the schedule kept from this buffer's last validated binning under
     // this key, or (loose) under a key whose transform is within LOOSE_PX
@@ -2667,7 +2654,7 @@ void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool c
     if (r == ENQ_FAIL) return;
     if (r == ENQ_SORTED) {   // (exact) a tile list too long for the LDS sort
         fp.tileStamp = nullptr;   // (the ordered raster writes every tile)
-        draw_ordered_sorted(ctx, src, fp, bp);
+        draw_ordered_sorted(ctx, fp, bp);
         return;
     }
     const int ntiles = fp.tiles_x * fp.tiles_y;
@@ -2676,7 +2663,7 @@ void draw_free(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool c
     } else if (known) {
         sched_capture(ctx, F, key, tb, ntiles, sc.last);
     } else {
-        PendingBatch* pb = new PendingBatch{src, fp, bp, si, seq, tb, key, ordered};
+        PendingBatch* pb = new PendingBatch{fp, bp, si, seq, tb, key, ordered};
         ctx->pendingBatch = pb;
     }
     ctx->lastPath = ordered ? 2 : 1;
@@ -2714,7 +2701,7 @@ void settle(RenderContext* ctx) {
     }
     const int ntiles = pb->fp.tiles_x * pb->fp.tiles_y;
     const bool fits = plan_val(F, PW_FITS) != 0;
-    sc.last = plan_totals(F, pb->src.n);
+    sc.last = plan_totals(F, pb->fp.src.n);
     // exact totals, fitted or not; fitted: its offsets and items are the buffer's schedule under this key
     if (!pb->ordered) keep_binning(ctx, F, pb->key, pb->tb, ntiles, sc.last, fits);
     if (!fits) {
@@ -2729,7 +2716,7 @@ void settle(RenderContext* ctx) {
         em.ordered = pb->ordered;
         int rr = ENQ_SORTED;
         if (sorted || (rr = free_enqueue(ctx, pb->fp, pb->bp, pb->set, em, &seq)) == ENQ_SORTED)
-            rerun_ordered_sorted(ctx, pb->src, pb->fp, pb->bp);   // (the context's flags are left as they are now)
+            rerun_ordered_sorted(ctx, pb->fp, pb->bp);   // (the context's flags are left as they are now)
         else if (rr == ENQ_OK && !pb->ordered)   // the exact re-run's binning is the buffer's schedule under this key
             keep_binning(ctx, F, pb->key, pb->tb, ntiles, sc.last);
     }

@@ -609,26 +609,40 @@ void launch_ordered_binned(const FrameParams& fp, const u32* list, const u32* of
     else launch_raster_c<false, true>(fp, list, off, nullptr, ntiles, s, rec, plan, start, stop);
 }
 
-void draw_ordered(RenderContext* ctx, const TriSrc& src, TriangleBuffer* tb, bool callerOwned, const TexView* tex,
-                  const f64* q) {
+void draw_ordered(RenderContext* ctx, const Batch& b) {
     const i64 ntiles = (i64)((ctx->width + TW - 1) / TW) * ((ctx->height + TH - 1) / TH);
     if (ntiles <= ORD_BIN_TILES) {
-        draw_free(ctx, src, tb, callerOwned, true, tex, q);
+        draw_free(ctx, b, true);
         return;
     }
-    FrameParams fp = frame_params(ctx, src, tex, q);
-    draw_ordered_sorted(ctx, src, fp, bin_params(fp));
+    FrameParams fp = frame_params(ctx, b);
+    draw_ordered_sorted(ctx, fp, bin_params(fp));
 }
 
 namespace {
 
-// The global-sort ordered path for a batch with its state snapshot (fp, bp):
+// The snapshot pair (ft, bt) of the triangles of (fp, bp) from `first` on: the one place that knows which arrays a
+// batch has.  (The head of a split is the same pair with src.n cut.)
+void batch_tail(const FrameParams& fp, const BinParams& bp, i64 first, FrameParams& ft, BinParams& bt) {
+    ft = fp;
+    bt = bp;
+    TriSrc& s = ft.src;
+    s.xy += first * 6;
+    if (s.z) s.z += first * 3;
+    s.attr += first * attr_stride(s.mode);
+    s.n -= first;
+    if (ft.q) ft.q += first * 3;
+    bt.src = s;
+}
+
+// The global-sort ordered path for a batch with its state snapshot (fp, bp; fp.src == bp.src):
 // per-triangle tile counts -> scan -> (tile, triangle) pairs in triangle order
 // -> stable radix sort by tile -> tile ranges -> k_tile_raster.  Only enqueues
 // kernels: the context's flags are the caller's business (draw_ordered_sorted
 // consumes them; a deferred re-run, rerun_ordered_sorted, must leave them as
 // the calls after the batch set them).
-void ordered_sorted_kernels(RenderContext* ctx, const TriSrc& src, const FrameParams& fp, const BinParams& bp) {
+void ordered_sorted_kernels(RenderContext* ctx, const FrameParams& fp, const BinParams& bp) {
+    const TriSrc& src = fp.src;
     hipStream_t s = ctx->stream;
     TriScratch& sc = ctx->tri;
     const int ntiles = fp.tiles_x * fp.tiles_y;
@@ -659,19 +673,12 @@ void ordered_sorted_kernels(RenderContext* ctx, const TriSrc& src, const FramePa
 
     if (P > (1ull << 31) && src.n > 1) {
         // too many pairs for one pass: split the batch; submission order kept
-        TriSrc a = src, b = src;
-        a.n = src.n / 2;
-        b.n = src.n - a.n;
-        b.xy = src.xy + a.n * 6;
-        b.z = src.z ? src.z + a.n * 3 : nullptr;
-        b.attr = src.attr + a.n * attr_stride(src.mode);
-        BinParams ba = bp, bb = bp;
-        ba.src = a; bb.src = b;
-        FrameParams fa = fp, fb = fp;
-        fa.src = a; fb.src = b;
-        if (fp.q) fb.q = fp.q + a.n * 3;
+        FrameParams fa = fp, fb;
+        BinParams ba = bp, bb;
+        fa.src.n = ba.src.n = src.n / 2;
+        batch_tail(fp, bp, fa.src.n, fb, bb);
         // (fb keeps the frame output: the second half rewrites the tiles it covers)
-        ordered_sorted_kernels(ctx, a, fa, ba);
+        ordered_sorted_kernels(ctx, fa, ba);
         if (fa.fragCounter) {   // fragments of the first half, then the counter restarts for the second
             NR_CHECK(hipMemcpyAsync(&sc.h_total[2], fa.fragCounter, sizeof(u64), hipMemcpyDeviceToHost, s));
             NR_CHECK(hipStreamSynchronize(s));
@@ -680,7 +687,7 @@ void ordered_sorted_kernels(RenderContext* ctx, const TriSrc& src, const FramePa
         }
         fb.pendColor = 0;   // (the first half applied the pending clears)
         fb.pendDepth = 0;
-        ordered_sorted_kernels(ctx, b, fb, bb);
+        ordered_sorted_kernels(ctx, fb, bb);
         return;
     }
 
@@ -724,7 +731,7 @@ void ordered_sorted_kernels(RenderContext* ctx, const TriSrc& src, const FramePa
 
 }  // namespace
 
-void draw_ordered_sorted(RenderContext* ctx, const TriSrc& src, const FrameParams& fp0, const BinParams& bp) {
+void draw_ordered_sorted(RenderContext* ctx, const FrameParams& fp0, const BinParams& bp) {
     FrameParams fp = fp0;
     // with a pending clear every owned tile is rasterised and written back,
     // so the write-back also produces the frame output (as k_vis does)
@@ -732,7 +739,7 @@ void draw_ordered_sorted(RenderContext* ctx, const TriSrc& src, const FrameParam
         const size_t n = (size_t)nr_frame_bytes(ctx);
         if (n <= ctx->frameU8cap) fp.frameU8 = ctx->frameU8;
     }
-    ordered_sorted_kernels(ctx, src, fp, bp);
+    ordered_sorted_kernels(ctx, fp, bp);
     ctx->lastPath = 2;
     finish_batch(ctx, fp);
 }
@@ -743,8 +750,8 @@ void draw_ordered_sorted(RenderContext* ctx, const TriSrc& src, const FrameParam
 // nothing of the context's current state -- the calls made since (ClearDepth,
 // SetColor, ...) have already set the flags for what comes next.  Only its
 // fragments are accounted.
-void rerun_ordered_sorted(RenderContext* ctx, const TriSrc& src, const FrameParams& fp, const BinParams& bp) {
-    ordered_sorted_kernels(ctx, src, fp, bp);
+void rerun_ordered_sorted(RenderContext* ctx, const FrameParams& fp, const BinParams& bp) {
+    ordered_sorted_kernels(ctx, fp, bp);
     if (fp.fragCounter) {
         TriScratch& sc = ctx->tri;
         NR_CHECK(hipMemcpyAsync(&sc.h_total[2], fp.fragCounter, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
