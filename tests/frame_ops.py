@@ -136,6 +136,13 @@ def textured_soup(n, W, H, seed, spread, uvkind, size):
     return xy, z, np.ascontiguousarray(uv.reshape(n, 6))
 
 
+def oracle_texels(tex):
+    """The texels of an oracle texture as they are now, (h, w, 3|4) f64."""
+    out = np.empty((tex.height, tex.width, 4 if tex.enableAlpha else 3), dtype=np.float64)
+    tex.lib.OracleGetTextureBuffer(tex._ptr, scenes._vp(out))
+    return out
+
+
 def _to_space(space, p, W, H):
     """Unit-box positions p (in about [-1.2, 1.2]^3) in the mesh's space."""
     if space == "model":
@@ -313,10 +320,7 @@ class _Run:
         self.snaps[(which, bool(shared))] = t
 
     def texels(self, tex):
-        """The texels of an oracle texture as they are now, (h, w, 3|4) f64."""
-        out = np.empty((tex.height, tex.width, 4 if tex.enableAlpha else 3), dtype=np.float64)
-        tex.lib.OracleGetTextureBuffer(tex._ptr, scenes._vp(out))
-        return out
+        return oracle_texels(tex)
 
     # ---- triangle batches -----------------------------------------------------
     def _note(self, kind, xy, ctx=None):
