@@ -146,7 +146,7 @@ void DrawTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb);         /* NEW 
 i64 GetTriangleBufferCount(TriangleBuffer* tb);                          /* NEW */
 /* NEW: textured triangles.  uv: n*6 per-vertex texture coordinates in texel units (u0 v0 u1 v1 u2 v2),
    interpolated like a Gouraud channel (affine) and sampled with DrawTexture's nearest sampler (a NaN
-   coordinate samples texel 0); blended by ApplyPixel.  A NULL texture, one narrower or lower than 2
+   coordinate samples texel 0) or, by SetTriangleTextureFilter, bilinearly; blended by ApplyPixel.  A NULL texture, one narrower or lower than 2
    texels, or one on another device latches an error and draws nothing. */
 void DrawTexturedTriangles(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uv,
                            i64 n);                                        /* NEW: host arrays */
@@ -167,6 +167,16 @@ TriangleBuffer* CreateTexturedTriangleBuffer(i64 n, const f64* xy, const f64* z,
                                              const f64* uv);              /* NEW: one H2D upload; no texture bound */
 void DrawTexturedTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb, Texture* tex);   /* NEW: texture chosen per
                                  draw; a colour buffer here, or a textured one in DrawTriangleBuffer, latches an error */
+/* NEW: the texture filter of the textured triangle draws (DESIGN §3 "Bilinear texture filtering"): 0 nearest (the
+   default), 1 bilinear -- the filter in the body of the reference's sampler, restated bit for bit: (u, v) clamped
+   as the nearest sampler clamps it, the texels (iy, ix), (iy, ix+1), (iy+1, ix), (iy+1, ix+1) weighted by the
+   fractions in f64, every operation rounded in the order written; the alpha of a texture without alpha stays the
+   literal 1.  It covers DrawTexturedTriangles and its Device / Perspective variants, DrawTexturedTriangleBuffer
+   and DrawTexturedMesh; colour draws, DrawTexture, DrawSplittedTexture and ResampleTexture are untouched.  Per
+   context, not saved / restored, not recorded; read when a draw is issued (a pending batch keeps its filter).
+   Any other mode latches an error, leaves the state unchanged and returns false. */
+bool SetTriangleTextureFilter(RenderContext* ctx, i64 mode);             /* NEW */
+i64 GetTriangleTextureFilter(RenderContext* ctx);                        /* NEW */
 /* NEW: indexed 3D meshes (DESIGN §3 "Vertex stage").  nv vertices pos (px, py, pz), n triangles as u32 index
    triples, one per-vertex attribute: RGBA nv*4 (flat = the colour of a triangle's first index, or Gouraud) or
    texel-unit UVs nv*2.  Uploaded once; each draw transforms the vertices on the device by a row-major 4x4

@@ -82,6 +82,8 @@ DEVICE_ABI = {
     "DrawTexturedTrianglesPerspectiveDevice": (None, (P, P, P, P, P, P, L)),
     "CreateTexturedTriangleBuffer": (P, (L, P, P, P)),
     "DrawTexturedTriangleBuffer": (None, (P, P, P)),
+    "SetTriangleTextureFilter": (B, (P, L)),
+    "GetTriangleTextureFilter": (L, (P,)),
     "CreateMesh": (P, (L, P, L, P, P, B)),
     "CreateTexturedMesh": (P, (L, P, L, P, P)),
     "DestroyMesh": (None, (P,)),

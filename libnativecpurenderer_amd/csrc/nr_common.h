@@ -309,6 +309,7 @@ struct RenderContext {
     f64 meshNear = 0;
     int meshCull = 0;
     bool meshPersp = false;           // textured mesh draws carry 1/cw to the rasters (SetMeshPerspective); same rule
+    int texFilter = 0;                // textured triangle draws: 0 nearest, 1 bilinear (SetTriangleTextureFilter); same rule
     i64 meshLastCount = 0;
     iu8* u8buf = nullptr; size_t u8cap = 0;   // GetBufferAsUInt8 staging
     // multi-GPU: owned tile rows ty % nshards == shard (nr_dist.hip)

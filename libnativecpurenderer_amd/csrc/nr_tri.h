@@ -28,10 +28,21 @@ constexpr int TH = 32;   // tile height
 // Per-triangle attribute of a batch: one colour, a colour per vertex, or a
 // texture coordinate per vertex (texel units) sampled from FrameParams::tex --
 // interpolated affinely in screen space (ATTR_TEX), or perspective-correct
-// with a 1/w per vertex, FrameParams::q (ATTR_TEX_PERSP).
-enum AttrMode { ATTR_FLAT = 0, ATTR_GOURAUD = 1, ATTR_TEX = 2, ATTR_TEX_PERSP = 3 };
-// either textured mode: the attribute array is the uv array, the colour a texel
-__host__ __device__ constexpr bool attr_textured(int mode) { return mode == ATTR_TEX || mode == ATTR_TEX_PERSP; }
+// with a 1/w per vertex, FrameParams::q (ATTR_TEX_PERSP).  The
+// two _BIL modes are those two with the bilinear filter (SetTriangleTextureFilter,
+// tex_bilinear) in place of the nearest texel: the same batch, record and
+// coordinates, four texels per fragment.
+enum AttrMode {
+    ATTR_FLAT = 0, ATTR_GOURAUD = 1, ATTR_TEX = 2, ATTR_TEX_PERSP = 3, ATTR_TEX_BIL = 4, ATTR_TEX_PERSP_BIL = 5
+};
+// any textured mode: the attribute array is the uv array, the colour a texel (or four, filtered)
+__host__ __device__ constexpr bool attr_textured(int mode) { return mode >= ATTR_TEX && mode <= ATTR_TEX_PERSP_BIL; }
+__host__ __device__ constexpr bool attr_persp(int mode) { return mode == ATTR_TEX_PERSP || mode == ATTR_TEX_PERSP_BIL; }
+__host__ __device__ constexpr bool attr_bilinear(int mode) { return mode == ATTR_TEX_BIL || mode == ATTR_TEX_PERSP_BIL; }
+// the nearest mode whose per-triangle data (record, setup slots) a textured mode shares
+__host__ __device__ constexpr int attr_unfiltered(int mode) {
+    return mode == ATTR_TEX_BIL ? ATTR_TEX : (mode == ATTR_TEX_PERSP_BIL ? ATTR_TEX_PERSP : mode);
+}
 
 struct TriSrc {
     const f64* xy;    // n*6
@@ -45,7 +56,7 @@ struct TriSrc {
 // doubles of the attribute array per triangle
 __host__ __device__ inline int attr_stride(int mode) { return mode == ATTR_GOURAUD ? 12 : (attr_textured(mode) ? 6 : 4); }
 
-// The texture a textured batch samples (nearest, tex_index): texels as the
+// The texture a textured batch samples (tex_index, tex_bilinear): texels as the
 // framebuffer stores them, ipp doubles each, w >= 2 and h >= 2 (a side below
 // 2^29, so the pitch fits an int: check_texture).  The sampler's clamp bounds (f64)(w-2), (f64)(h-2)
 // are formed on the host -- the same values -- so that they arrive as scalar
@@ -389,7 +400,7 @@ struct FrameParams {
                       // 100 MHz clock (raster_stamp_begin / _end, nr_timing_stamp)
     TexView tex;      // textured batches: the texture (a snapshot when it aliases fb)
     u32* winMask;     // a marking frame (k_vis MARK instances only): bit t is set when triangle t wins a pixel
-    // ATTR_TEX_PERSP batches: each corner's 1/w, n*3 laid out like src.z (else null).  Only the shading reads it,
+    // perspective batches (attr_persp): each corner's 1/w, n*3 laid out like src.z (else null).  Only the shading reads it,
     // so it lives here and not in TriSrc, and last: the binning's BinParams and every offset of the snapshot
     // the existing instances read stay as they were.
     const f64* q;
@@ -408,6 +419,35 @@ __device__ __forceinline__ i64 tex_index(const TexView& tv, f64 x, f64 y) {
     const int xi = (int)fmin(fmax(x, 0.0), tv.xlast);
     const int yi = (int)fmin(fmax(y, 0.0), tv.ylast);
     return (i64)yi * tv.pitch + xi * tv.ipp;
+}
+
+// The bilinear filter's footprint of a fragment's (u, v) (the
+// filter in the reference sampler's body, cpp:576-619): the offset of texel
+// (iy, ix) -- its neighbours are tv.ipp and tv.pitch doubles further -- and the
+// fractions fu, fv.  The reference clamps x < 0 -> 0, x >= w-1 -> w-2 (so the
+// +1 neighbour exists), then ix = (i64)x, fu = x - ix.  That needs w-1, which
+// as xlast + 1.0 is one more loop-invariant vector value (see TexView); the
+// form here needs xlast and the constant 1 only: x' = fmax(x, 0) (NaN -> 0),
+// ix = (int)fmin(x', xlast), fu = x' - ix, and fu >= 1 -> 0.  For x' < w-2 both
+// forms truncate x' itself; for w-2 <= x' < w-1 the reference keeps x', ix is
+// w-2 and x' - (w-2) is exact and below 1; for x' >= w-1 (or +inf) the
+// difference is >= 1 or infinite and becomes the reference's 0.  Rows likewise.
+// All four texels are in range for every input: ix <= w-2, iy <= h-2.
+// (tests/test_bilinear_ref.py proves the two forms equal.)
+__device__ __forceinline__ i64 tex_bilinear(const TexView& tv, f64 x, f64 y, f64& fu, f64& fv) {
+    const f64 xc = fmax(x, 0.0), yc = fmax(y, 0.0);
+    const int xi = (int)fmin(xc, tv.xlast);
+    const int yi = (int)fmin(yc, tv.ylast);
+    const f64 du = xc - (f64)xi, dv = yc - (f64)yi;
+    fu = du < 1.0 ? du : 0.0;
+    fv = dv < 1.0 ? dv : 0.0;
+    return (i64)yi * tv.pitch + xi * tv.ipp;
+}
+// One channel of the filtered colour from its four texels c0 (iy, ix), c1 (iy, ix+1), c2 (iy+1, ix), c3 (iy+1,
+// ix+1), as C evaluates cpp:609: each product left to right, the sum left to right, every operation rounded (the
+// build has no FMA contraction).  gu = 1 - fu, gv = 1 - fv.
+__device__ __forceinline__ f64 bilinear_mix(f64 c0, f64 c1, f64 c2, f64 c3, f64 fu, f64 fv, f64 gu, f64 gv) {
+    return c0 * gu * gv + c1 * fu * gv + c2 * gu * fv + c3 * fu * fv;
 }
 
 // Kernel timing of the rasters by the device's constant 100 MHz clock
@@ -544,7 +584,7 @@ struct Soup {
 // context's staging, of a TriangleBuffer or of a mesh draw are not the caller's.
 struct Batch {
     TriSrc src;
-    const f64* q;                                 // ATTR_TEX_PERSP: the corners' 1/w (else null)
+    const f64* q;                                 // perspective textured batches: the corners' 1/w (else null)
     TexView tex = tex_view(nullptr, 2, 2, false); // textured modes: what draw_textured resolved
     Opacity opq;
     TriangleBuffer* tb;   // non-null: the batch is that (immutable) buffer -- its binning may overlap the previous

@@ -218,12 +218,15 @@ bool check_texture(RenderContext* ctx, const Texture* tex, const char* what) {
     return false;
 }
 
-// b.q non-null: a perspective textured batch (ATTR_TEX_PERSP).
+// b.q non-null: a perspective textured batch.  The context's filter
+// (SetTriangleTextureFilter) is read here, when the draw is issued: the mode is
+// part of the batch's snapshot, so a pending batch or its re-run keeps it.
 void draw_textured(RenderContext* ctx, Texture* tex, Batch& b) {
     settle(ctx);   // (a re-run of the pending batch comes before a snapshot of the target)
     TexSrc ts = nr_tex_source(ctx, tex);
     b.tex = tex_view(ts.ptr, tex->width, tex->height, tex->enableAlpha);
-    b.src.mode = b.q ? ATTR_TEX_PERSP : ATTR_TEX;
+    if (ctx->texFilter) b.src.mode = b.q ? ATTR_TEX_PERSP_BIL : ATTR_TEX_BIL;
+    else b.src.mode = b.q ? ATTR_TEX_PERSP : ATTR_TEX;
     b.opq = tex->enableAlpha ? OPQ_BLENDED : OPQ_OPAQUE;
     draw(ctx, b);
     if (ts.tmp) {   // (rare: the snapshot must outlive the batch and any re-run of it)
@@ -315,6 +318,23 @@ void SetDepthState(RenderContext* ctx, bool test, bool write) {
     ctx->depthTest = test;
     ctx->depthWrite = write;
 }
+
+// New: the texture filter of this context's textured triangle draws
+// (DrawTexturedTriangles and its Device / Perspective variants,
+// DrawTexturedTriangleBuffer, DrawTexturedMesh): 0 nearest (the default), 1
+// bilinear.  Any other mode latches an error, leaves the state
+// unchanged and returns false.  Per context; not part of the save / restore
+// stack, not recorded (the mesh states' rule); read when a draw is issued.
+// DrawTexture, DrawSplittedTexture and ResampleTexture stay nearest.
+bool SetTriangleTextureFilter(RenderContext* ctx, i64 mode) {
+    if (mode != 0 && mode != 1) {
+        nr_set_error_msg("SetTriangleTextureFilter: mode must be 0 (nearest) or 1 (bilinear)");
+        return false;
+    }
+    ctx->texFilter = (int)mode;
+    return true;
+}
+i64 GetTriangleTextureFilter(RenderContext* ctx) { return ctx->texFilter; }
 
 // New: clear the u32 depth buffer (deferred; consumed by the raster).
 void ClearDepth(RenderContext* ctx, u32 value) {

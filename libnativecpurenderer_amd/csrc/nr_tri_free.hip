@@ -820,6 +820,7 @@ template <int ZMODE, int MODE, int NT, int HS, bool MARK = false>
 __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0, int wlim, int hlim,
                                            const u64* key, unsigned char* lds, u32& nU) {
     using St = ShadeStage<MODE, HS>;
+    constexpr int RM = attr_unfiltered(MODE);   // the mode of the shading records (a bilinear batch: its nearest counterpart's)
     constexpr int PPT = TH * TW / NT;
     static_assert(PPT <= 32, "overflow bitmask");
     const int tid = opaque_tid();
@@ -930,29 +931,33 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
     const u32 U = nU < (u32)St::RT ? nU : (u32)St::RT;
     // two winners per thread per round, both records' loads in flight
     for (u32 u = tid; u < U; u += 2 * NT) {
-        RecordSrc<MODE> s0, s1;
+        RecordSrc<RM> s0, s1;
         const bool two = u + NT < U;
-        load_record_src<MODE>(fp, (i64)didx[u] - 1, s0);
-        if (two) load_record_src<MODE>(fp, (i64)didx[u + NT] - 1, s1);
-        build_record<MODE>(fp, s0, rec + u * St::REC);
-        if (two) build_record<MODE>(fp, s1, rec + (u + NT) * St::REC);
+        load_record_src<RM>(fp, (i64)didx[u] - 1, s0);
+        if (two) load_record_src<RM>(fp, (i64)didx[u + NT] - 1, s1);
+        build_record<RM>(fp, s0, rec + u * St::REC);
+        if (two) build_record<RM>(fp, s1, rec + (u + NT) * St::REC);
     }
     __syncthreads();
     NR_PROBE_STAMP(5);
     const TexView& tv = fp.tex;   // (textured batches)
     if constexpr (attr_textured(MODE)) {
-        // Textured (either mode; the perspective record's texel carries the
-        // divide, record_texel_persp): a pixel's colour is a dependent gather (record -> u, v ->
+        // Textured (any mode; the perspective record's coordinate carries the
+        // divide, record_uv): a pixel's colour is a dependent gather (record -> u, v ->
         // texel, 24 B), so a thread first forms the texel offsets of TQ of its
         // pixels, then issues their loads together, and only then consumes
         // them (as the flat path keeps FQ loads in flight).  Ordinary cached
-        // loads: the texture is read again by other tiles.
+        // loads: the texture is read again by other tiles.  A bilinear mode
+        // gathers four texels per pixel (24 VGPRs) and keeps the two fractions,
+        // so it has one pixel's loads in flight, not two.
         static_assert(OVF_Q > 0, "unstaged winners are shaded in pass 3b");
-        constexpr int TQ = 2;
+        constexpr bool BIL = attr_bilinear(MODE);
+        constexpr int TQ = BIL ? 1 : 2;
         static_assert(PPT % TQ == 0, "pixel groups");
 #pragma unroll 1
         for (int k0 = 0; k0 < PPT; k0 += TQ) {
             i64 ti[TQ];   // texel offset, or -1: nothing to fetch
+            f64 fu[BIL ? TQ : 1], fv[BIL ? TQ : 1];   // (bilinear: the footprint's fractions)
 #pragma unroll
             for (int j = 0; j < TQ; ++j) {
                 const int k = k0 + j;
@@ -982,14 +987,26 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                     ovf |= 1u << k;
                     continue;
                 }
-                ti[j] = record_texel_of<MODE>(tv, rec + d * St::REC, px, py);
+                if constexpr (BIL) {
+                    f64 u, v;
+                    record_uv<MODE>(rec + d * St::REC, px, py, u, v);
+                    ti[j] = tex_bilinear(tv, u, v, fu[j], fv[j]);
+                } else {
+                    ti[j] = record_texel_of<MODE>(tv, rec + d * St::REC, px, py);
+                }
             }
             f64 c[TQ][3];
 #pragma unroll
             for (int j = 0; j < TQ; ++j) {
                 if (ti[j] < 0) continue;
-                const f64* q = tv.ptr + ti[j];
-                c[j][0] = q[0]; c[j][1] = q[1]; c[j][2] = q[2];
+                if constexpr (BIL) {
+                    TexQuad t;
+                    load_tex_quad(tv, ti[j], t);
+                    mix_tex_quad(t, fu[j], fv[j], c[j][0], c[j][1], c[j][2]);
+                } else {
+                    const f64* q = tv.ptr + ti[j];
+                    c[j][0] = q[0]; c[j][1] = q[1]; c[j][2] = q[2];
+                }
             }
 #pragma unroll
             for (int j = 0; j < TQ; ++j) {
@@ -1040,7 +1057,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                 continue;
             } else {   // overflow: load this pixel's winner directly
                 f64 r[St::REC];
-                make_record<MODE>(fp, (i64)id - 1, r);
+                make_record<RM>(fp, (i64)id - 1, r);
                 record_colour<MODE>(tv, r, px, py, cr, cg, cb, ca);
             }
             apply_winner(fp, gp, cr, cg, cb, ca);
@@ -1054,7 +1071,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
         while (ovf) {
             constexpr int Q = OVF_Q > 0 ? OVF_Q : 1;
             int kq[Q];
-            RecordSrc<MODE> src[Q];
+            RecordSrc<RM> src[Q];
 #pragma unroll
             for (int j = 0; j < Q; ++j) {
                 kq[j] = -1;
@@ -1065,7 +1082,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
 #pragma unroll
                 for (int q = 0; q < PPT; ++q)
                     if (q == kq[j]) id = ids[q];
-                load_record_src<MODE>(fp, (i64)id - 1, src[j]);
+                load_record_src<RM>(fp, (i64)id - 1, src[j]);
             }
 #pragma unroll
             for (int j = 0; j < Q; ++j) {
@@ -1074,7 +1091,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                 const i64 px = x0 + lx, py = y0 + ly;
                 const i64 gp = py * fp.W + px;
                 f64 r[St::REC];
-                build_record<MODE>(fp, src[j], r);
+                build_record<RM>(fp, src[j], r);
                 f64 cr, cg, cb, ca;
                 record_colour<MODE>(tv, r, px, py, cr, cg, cb, ca);
                 apply_winner(fp, gp, cr, cg, cb, ca);
@@ -1665,8 +1682,9 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& 
     // dense items run at low occupancy and are latency-bound
     const bool wide = !C && t.n != 0 && t.heavy > 0 && t.heavy < WIDE_HEAVY;
     auto kernel = vis_kernel<Z, C, G, false>(wide, coop);
-    // a marking frame (fp.winMask; never a counting batch, never LESS without write)
-    if constexpr (!C && Z != 2) {
+    // a marking frame (fp.winMask; never a counting batch, never LESS without write -- and only a repeat
+    // TriangleBuffer draw marks, which has no q: the filtered perspective mode has no marking instance)
+    if constexpr (!C && Z != 2 && G != ATTR_TEX_PERSP_BIL) {
         if (fp.winMask) kernel = vis_kernel<Z, false, G, true>(wide, coop);
     }
     hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(wide ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.items, va.list,
@@ -1682,7 +1700,9 @@ static void launch_vis_any(const FrameParams& fp, const TriScratch& sc, const Ba
 #define NR_VG(ZM, G) (fp.fragCounter ? launch_vis<ZM, true, G>(fp, sc, t, va, grid, s, start, stop) \
                                      : launch_vis<ZM, false, G>(fp, sc, t, va, grid, s, start, stop))
 #define NR_VZ(ZM)                                            \
-    (mode == ATTR_TEX_PERSP ? NR_VG(ZM, ATTR_TEX_PERSP)      \
+    (mode == ATTR_TEX_PERSP_BIL ? NR_VG(ZM, ATTR_TEX_PERSP_BIL) \
+     : mode == ATTR_TEX_BIL ? NR_VG(ZM, ATTR_TEX_BIL)        \
+     : mode == ATTR_TEX_PERSP ? NR_VG(ZM, ATTR_TEX_PERSP)    \
      : mode == ATTR_TEX     ? NR_VG(ZM, ATTR_TEX)            \
      : mode == ATTR_GOURAUD ? NR_VG(ZM, ATTR_GOURAUD)        \
                             : NR_VG(ZM, ATTR_FLAT))

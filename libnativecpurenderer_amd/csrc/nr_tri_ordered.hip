@@ -133,12 +133,15 @@ __device__ __forceinline__ u64 window_bits(int xs, int xe) {
 // varies over the triangle, so it takes none of the flat shortcuts.  A
 // perspective textured batch (ATTR_TEX_PERSP) interpolates U = u q, V = v q and
 // Q = q in three of those slots and samples at (U / Q, V / Q) (as U * (1 / Q)).
+// A bilinear mode differs in the blend loop only: four texels (tex_bilinear)
+// filtered into R, G, B (and A from an RGBA texture) before ApplyPixel.
 // 4 waves per SIMD (6: 80 VGPRs, 85 spilled -- C5 raster 740 -> 1355 us)
 template <int MODE, bool DEPTH, bool COUNT, bool RGBA, bool BINNED>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_tile_raster(const FrameParams fp, const u32* __restrict__ list,
                                                     const u32* __restrict__ tstart, const u32* __restrict__ tend,
                                                     const f64* __restrict__ rec, const u32* __restrict__ plan) {
-    constexpr bool GOURAUD = MODE == ATTR_GOURAUD, TEX = attr_textured(MODE), PERSP = MODE == ATTR_TEX_PERSP;
+    constexpr bool GOURAUD = MODE == ATTR_GOURAUD, TEX = attr_textured(MODE), PERSP = attr_persp(MODE);
+    constexpr bool BIL = attr_bilinear(MODE);
     constexpr bool FLATC = MODE == ATTR_FLAT;   // one colour per triangle: the per-triangle blend terms apply
     const int tile = blockIdx.x;
     const int tx = tile % fp.tiles_x, ty = tile / fp.tiles_x;
@@ -460,9 +463,24 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                         u = u * rq;
                         v = v * rq;
                     }
-                    const f64* tq = fp.tex.ptr + tex_index(fp.tex, u, v);
-                    f64 R = tq[0], G = tq[1], B = tq[2];
-                    f64 A = fp.tex.ipp == 4 ? tq[3] : 1.0;
+                    f64 R, G, B, A;
+                    if (BIL) {
+                        f64 fu, fv;
+                        const f64* t0 = fp.tex.ptr + tex_bilinear(fp.tex, u, v, fu, fv);
+                        const f64* t1 = t0 + fp.tex.ipp;
+                        const f64* t2 = t0 + fp.tex.pitch;
+                        const f64* t3 = t2 + fp.tex.ipp;
+                        const f64 gu = 1 - fu, gv = 1 - fv;
+                        R = bilinear_mix(t0[0], t1[0], t2[0], t3[0], fu, fv, gu, gv);
+                        G = bilinear_mix(t0[1], t1[1], t2[1], t3[1], fu, fv, gu, gv);
+                        B = bilinear_mix(t0[2], t1[2], t2[2], t3[2], fu, fv, gu, gv);
+                        // (a texture without alpha: the literal 1, not a filtered sum of ones)
+                        A = fp.tex.ipp == 4 ? bilinear_mix(t0[3], t1[3], t2[3], t3[3], fu, fv, gu, gv) : 1.0;
+                    } else {
+                        const f64* tq = fp.tex.ptr + tex_index(fp.tex, u, v);
+                        R = tq[0]; G = tq[1]; B = tq[2];
+                        A = fp.tex.ipp == 4 ? tq[3] : 1.0;
+                    }
                     // ApplyPixel (cpp:529-547) on the register-resident pixel
                     R *= ct0; G *= ct1; B *= ct2; A *= ct3;
                     if (A != 1) {
@@ -587,7 +605,12 @@ void launch_raster_c(const FrameParams& fp, const u32* list, const u32* ts, cons
                      hipEvent_t stop = nullptr) {
     const bool g = fp.src.mode == ATTR_GOURAUD, t = fp.src.mode == ATTR_TEX, d = fp.depthTest != 0;
     const bool p = fp.src.mode == ATTR_TEX_PERSP;
-    if (p && d) launch_raster<ATTR_TEX_PERSP, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    const bool tb = fp.src.mode == ATTR_TEX_BIL, pb = fp.src.mode == ATTR_TEX_PERSP_BIL;
+    if (pb && d) launch_raster<ATTR_TEX_PERSP_BIL, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (pb) launch_raster<ATTR_TEX_PERSP_BIL, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (tb && d) launch_raster<ATTR_TEX_BIL, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (tb) launch_raster<ATTR_TEX_BIL, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (p && d) launch_raster<ATTR_TEX_PERSP, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
     else if (p) launch_raster<ATTR_TEX_PERSP, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
     else if (t && d) launch_raster<ATTR_TEX, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
     else if (t) launch_raster<ATTR_TEX, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);

@@ -31,7 +31,9 @@ namespace nrtri {
 // geometry terms | u0 v0 | (u1-u0) (v1-v0) | (u2-u0) (v2-v0): 13 doubles in
 // the Gouraud record's 16-double slot; perspective textured the 7 geometry
 // terms | a0 b0 | (a1-a0) (b1-b0) | (a2-a0) (b2-b0) | q0 (q1-q0) (q2-q0) with
-// a_k = u_k * q_k, b_k = v_k * q_k: all 16.  MODE: AttrMode.
+// a_k = u_k * q_k, b_k = v_k * q_k: all 16.  MODE: AttrMode; a bilinear mode
+// has no record code of its own -- shade_tile stages its batch with the
+// record of its nearest counterpart (attr_unfiltered).
 template <int MODE>
 struct RecLen {
     static constexpr int REC = MODE != ATTR_FLAT ? 16 : 3;
@@ -174,46 +176,70 @@ __device__ __forceinline__ void make_record(const FrameParams& fp, i64 t, f64* r
     build_record<MODE>(fp, s, r);
 }
 
-// Texel (tex_index) of pixel (px, py) from a textured record: u and v by the
-// expression of a Gouraud channel.
-__device__ __forceinline__ i64 record_texel(const TexView& tv, const f64* r, i64 px, i64 py) {
+// Texture coordinate of pixel (px, py) from a textured record: u and v by the
+// expression of a Gouraud channel; from a perspective textured record U, V, Q
+// by that expression, then the divide (IEEE) and the two products, u = U * (1 /
+// Q), v = V * (1 / Q).  Any Q (zero, negative, non-finite) gives a defined
+// texel: the samplers clamp.
+template <int MODE>
+__device__ __forceinline__ void record_uv(const f64* r, i64 px, i64 py, f64& u, f64& v) {
     const f64 dx = (f64)px - r[0], dy = (f64)py - r[1];
     const f64 w1 = (dx * r[5] - r[4] * dy) * r[6];
     const f64 w2 = (r[2] * dy - dx * r[3]) * r[6];
-    const f64 u = r[7] + r[9] * w1 + r[11] * w2;
-    const f64 v = r[8] + r[10] * w1 + r[12] * w2;
-    return tex_index(tv, u, v);
+    u = r[7] + r[9] * w1 + r[11] * w2;
+    v = r[8] + r[10] * w1 + r[12] * w2;
+    if constexpr (attr_persp(MODE)) {
+        const f64 Q = r[13] + r[14] * w1 + r[15] * w2;
+        const f64 rq = 1.0 / Q;
+        u = u * rq;
+        v = v * rq;
+    }
 }
-// ... from a perspective textured record: U, V, Q by that expression, then the
-// divide (IEEE) and the two products, u = U * (1 / Q), v = V * (1 / Q).  Any Q
-// (zero, negative, non-finite) gives a defined texel: tex_index clamps.
-__device__ __forceinline__ i64 record_texel_persp(const TexView& tv, const f64* r, i64 px, i64 py) {
-    const f64 dx = (f64)px - r[0], dy = (f64)py - r[1];
-    const f64 w1 = (dx * r[5] - r[4] * dy) * r[6];
-    const f64 w2 = (r[2] * dy - dx * r[3]) * r[6];
-    const f64 U = r[7] + r[9] * w1 + r[11] * w2;
-    const f64 V = r[8] + r[10] * w1 + r[12] * w2;
-    const f64 Q = r[13] + r[14] * w1 + r[15] * w2;
-    const f64 rq = 1.0 / Q;
-    return tex_index(tv, U * rq, V * rq);
-}
+// Nearest texel (tex_index) of that coordinate.
 template <int MODE>
 __device__ __forceinline__ i64 record_texel_of(const TexView& tv, const f64* r, i64 px, i64 py) {
-    if constexpr (MODE == ATTR_TEX_PERSP) return record_texel_persp(tv, r, px, py);
-    else return record_texel(tv, r, px, py);
+    f64 u, v;
+    record_uv<MODE>(r, px, py, u, v);
+    return tex_index(tv, u, v);
+}
+
+// The four texels of a bilinear footprint at offset ti (tex_bilinear), rgb each: texels (iy, ix) and (iy, ix + 1)
+// are adjacent, the second row tv.pitch further.  Ordinary cached loads, like the nearest texel's.
+struct TexQuad {
+    f64 c[4][3];
+};
+__device__ __forceinline__ void load_tex_quad(const TexView& tv, i64 ti, TexQuad& t) {
+    const f64* q0 = tv.ptr + ti;
+    const f64* q1 = q0 + tv.pitch;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        t.c[0][k] = q0[k]; t.c[1][k] = q0[tv.ipp + k];
+        t.c[2][k] = q1[k]; t.c[3][k] = q1[tv.ipp + k];
+    }
+}
+__device__ __forceinline__ void mix_tex_quad(const TexQuad& t, f64 fu, f64 fv, f64& cr, f64& cg, f64& cb) {
+    const f64 gu = 1 - fu, gv = 1 - fv;
+    cr = bilinear_mix(t.c[0][0], t.c[1][0], t.c[2][0], t.c[3][0], fu, fv, gu, gv);
+    cg = bilinear_mix(t.c[0][1], t.c[1][1], t.c[2][1], t.c[3][1], fu, fv, gu, gv);
+    cb = bilinear_mix(t.c[0][2], t.c[1][2], t.c[2][2], t.c[3][2], fu, fv, gu, gv);
 }
 
 // Colour of pixel (px, py) from a record.  (Textured: the texel's rgb from
-// the view tv, an ordinary cached load; alpha is 1 -- only textures without
-// alpha are routed to the order-free raster.)
+// the view tv, an ordinary cached load -- the filtered rgb of four in a
+// bilinear mode; alpha is the literal 1 -- only textures without alpha are
+// routed to the order-free raster.)
 template <int MODE>
 __device__ __forceinline__ void record_colour(const TexView& tv, const f64* r, i64 px, i64 py, f64& cr, f64& cg,
                                               f64& cb, f64& ca) {
-    if constexpr (MODE == ATTR_TEX) {
-        const f64* q = tv.ptr + record_texel(tv, r, px, py);
-        cr = q[0]; cg = q[1]; cb = q[2]; ca = 1.0;
-    } else if constexpr (MODE == ATTR_TEX_PERSP) {
-        const f64* q = tv.ptr + record_texel_persp(tv, r, px, py);
+    if constexpr (attr_bilinear(MODE)) {
+        f64 u, v, fu, fv;
+        record_uv<MODE>(r, px, py, u, v);
+        TexQuad t;
+        load_tex_quad(tv, tex_bilinear(tv, u, v, fu, fv), t);
+        mix_tex_quad(t, fu, fv, cr, cg, cb);
+        ca = 1.0;
+    } else if constexpr (attr_textured(MODE)) {
+        const f64* q = tv.ptr + record_texel_of<MODE>(tv, r, px, py);
         cr = q[0]; cg = q[1]; cb = q[2]; ca = 1.0;
     } else if (MODE == ATTR_GOURAUD) {
         const f64 dx = (f64)px - r[0], dy = (f64)py - r[1];

@@ -301,8 +301,9 @@ class RenderContext:
 
         xy: (n, 3, 2) or (n, 6) vertex positions; uv: (n, 3, 2) or (n, 6)
         per-vertex texture coordinates in texels of `tex` (interpolated like a
-        Gouraud channel, sampled with draw_texture's nearest sampler, tinted
-        by the colour transform); z: (n, 3) depths in [0, 1] or None; q: (n, 3)
+        Gouraud channel, sampled with draw_texture's nearest sampler or, after
+        set_triangle_texture_filter(1), bilinearly, tinted by the colour
+        transform); z: (n, 3) depths in [0, 1] or None; q: (n, 3)
         per-vertex 1/w for perspective-correct sampling at (U / Q, V / Q) with
         U, V, Q interpolated from u q, v q, q (None: affine, as before)."""
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 6)
@@ -409,6 +410,20 @@ class RenderContext:
             raise RuntimeError("AssembleMeshClipped failed: " + _lib.last_error())
         k = nout.value
         return xy[:k].copy(), z[:k].copy(), attr[:k].copy()
+
+    # texture filter of the textured triangle draws: per context, not saved /
+    # restored, not recorded; read when a draw is issued
+    def set_triangle_texture_filter(self, mode: int):
+        """0 nearest (the default), 1 bilinear: the filter of
+        draw_textured_triangles (with or without q), draw_textured_triangle_buffer
+        and draw_mesh of a textured Mesh.  Colour draws and draw_texture are
+        untouched.  Any other mode raises (the error stays latched) and leaves
+        the state unchanged."""
+        if not lib.SetTriangleTextureFilter(self._ptr, int(mode)):
+            raise RuntimeError("SetTriangleTextureFilter failed: " + _lib.last_error())
+
+    def get_triangle_texture_filter(self) -> int:
+        return lib.GetTriangleTextureFilter(self._ptr)
 
     # perspective-correct texture mapping of textured mesh draws: per context,
     # not saved / restored, not recorded; colour meshes ignore it

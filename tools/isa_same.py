@@ -3,7 +3,8 @@
 
 A host-only edit may reorder the functions of a listing and renumber their local labels, so the files differ
 while every function body is identical.  This compares the symbol sets and each function's text between its
-"Begin function" and "End function" markers, with the function ordinal stripped from local labels.
+"Begin function" and "End function" markers, with the function ordinal stripped from local labels (and the
+padding in front of a line's comment, which the printer sizes by the label's length, ordinal included).
 
 usage: isa_same.py PARENT.s NEW.s      exit status 1 on any difference
 """
@@ -21,6 +22,7 @@ def functions(path):
             out[name], name = "".join(body), None
         elif name:
             line = re.sub(r"BB\d+_(\d+)", r"BB_\1", line)   # (labels, and the comments that name them)
+            line = re.sub(r"[ \t]+;", " ;", line)
             body.append(re.sub(r"\.L(func_begin|func_end|tmp|JTI)\d+", r".L\1", line))
     return out
 
