@@ -250,6 +250,14 @@ i64 GetVisiblePairCount(RenderContext* ctx);                             /* NEW 
                                                                             list, 0 when there is none */
 void SetVisiblePruning(RenderContext* ctx, i64 mode);                    /* NEW: visible list of an unchanged repeat draw
                                                                             0 auto (on), 2 off (reuse the full list) */
+void SetVisibleReplan(RenderContext* ctx, i64 mode);                     /* NEW: work items of the visible list planned from
+                                                                            its kept counts, 0 auto (on), 2 off (the
+                                                                            schedule's items over the pruned list) */
+i64 GetReplannedBatchCount(RenderContext* ctx);                          /* NEW (testing): of the pruned batches, rasterised
+                                                                            under the visible plan */
+bool GetVisiblePlanTotals(RenderContext* ctx, i64* out4);                /* NEW (testing): the visible plan's kept pairs, work
+                                                                            items, split-tile slices, dense tiles; false:
+                                                                            none.  Waits for the device */
 bool GetScheduleTotals(RenderContext* ctx, i64* out4);                   /* NEW (testing): the warm schedule's pairs, work
                                                                             items, split-tile slices, dense tiles; false: none */
 void SetWarmFaultInjection(RenderContext* ctx, i64 mode);                /* NEW (testing): fault in the next warm batch

@@ -116,6 +116,9 @@ DEVICE_ABI = {
     "GetPrunedBatchCount": (L, (P,)),
     "GetVisiblePairCount": (L, (P,)),
     "SetVisiblePruning": (None, (P, L)),
+    "SetVisibleReplan": (None, (P, L)),
+    "GetReplannedBatchCount": (L, (P,)),
+    "GetVisiblePlanTotals": (B, (P, P)),
     "GetScheduleTotals": (B, (P, P)),
     "ExecuteCommands": (L, (P, P, L, P, L)),
     "SetWarmFaultInjection": (None, (P, L)),

@@ -210,10 +210,24 @@ struct TriScratch {
         int visZ = 0;                                    // depth mode (k_vis ZMODE) of the marking frame
         int markSet = -1; u32 markTag = 0;               // the list the marking frame read (pruned from the same one)
         hipEvent_t evMark = nullptr;                     // the marking frame is done (main stream)
-        void drop_visible() { visState = 0; }
+        // visible plan: the work items and plan words of the pruned list, planned
+        // from the kept counts once per pruning (k_vis_plan, right after
+        // k_prune_list) -- right-sized slices, items longest first by the
+        // visible counts, no item for work the frame no longer needs
+        DevArray<uint4> vitems;                          // its k_vis work items
+        u32* vplan = nullptr;                            // its device totals (PW_DEV words; PW_FITS always 1)
+        u64* h_vplan = nullptr;                          // pinned, device-mapped host copy, (seq << 32) | value
+        u64* d_hvplan = nullptr;                         // its device address
+        u32 vplanSeq = 0;                                // sequence number of the last visible plan
+        int replanState = 0;                             // 0 none, 1 enqueued, 2 its totals seen by the host
+        BatchTotals vtotals;                             // (state 2) pairs, items, split slices, dense tiles
+        u32 splitAt = 0, dslice = 0;                     // the split limits the schedule was planned under (0: defaults)
+        void drop_visible() { visState = 0; replanState = 0; }
         void release() {
             off.release(); items.release(); off2.release();
-            vlist.release(); vcnt.release(); vmask.release();
+            vlist.release(); vcnt.release(); vmask.release(); vitems.release();
+            if (vplan) NR_CHECK(hipFree(vplan));
+            if (h_vplan) NR_CHECK(hipHostFree(h_vplan));
             if (evMark) NR_CHECK(hipEventDestroy(evMark));
             if (dplan) NR_CHECK(hipFree(dplan));
             if (blocks) NR_CHECK(hipFree(blocks));
@@ -227,6 +241,8 @@ struct TriScratch {
     int reuseMode = 0;                      // list reuse: 0 automatic (on), 2 off (SetListReuse)
     u64 prunedBatches = 0;                  // of the reused ones, rasterised from the visible list (GetPrunedBatchCount)
     int pruneMode = 0;                      // visible list: 0 automatic (on), 2 off (SetVisiblePruning)
+    u64 replannedBatches = 0;               // of the pruned ones, rasterised under the visible plan (GetReplannedBatchCount)
+    int replanMode = 0;                     // visible plan: 0 automatic (on), 2 off (SetVisibleReplan)
     std::vector<u64> looseBanned;           // buffers whose loose binning overflowed a tile: not binned loose again
     // warm-batch checks (k_vis WarmCheck): host-mapped word a raster sets when
     // a warm batch failed them (1 binning check, 2 token timeout), read by

@@ -637,6 +637,7 @@ void launch_ordered_binned(const FrameParams& fp, const u32* list, const u32* of
 void draw_free(RenderContext* ctx, const Batch& b, bool ordered);
 void settle(RenderContext* ctx);
 i64 visible_pairs(RenderContext* ctx);   // pairs kept in the schedule's visible list (0: none)
+bool visible_plan_totals(RenderContext* ctx, i64* out4);   // the visible plan's pairs, items, split slices, dense tiles
 
 // the batch entry points behind every triangle draw call (nr_tri.hip), shared with the mesh front end
 // (nr_mesh.hip): draw picks the raster; draw_textured first completes the batch from the texture (its view, the

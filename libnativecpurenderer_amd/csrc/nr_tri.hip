@@ -543,6 +543,19 @@ i64 GetVisiblePairCount(RenderContext* ctx) {
 // (reused batches rasterise from the full list; a list already pruned is kept
 // and used again after a switch back to 0).
 void SetVisiblePruning(RenderContext* ctx, i64 mode) { ctx->tri.pruneMode = mode == 2 ? 2 : 0; }
+// New (testing / A-B measurement): the visible plan -- the pruned list's own
+// work items, planned from the kept counts -- 0 automatic (on), 2 off (pruned
+// batches run the schedule's items over the pruned list in place).
+void SetVisibleReplan(RenderContext* ctx, i64 mode) { ctx->tri.replanMode = mode == 2 ? 2 : 0; }
+// New (testing): of the pruned batches, those rasterised under the visible plan.
+i64 GetReplannedBatchCount(RenderContext* ctx) { return (i64)ctx->tri.replannedBatches; }
+// New (testing): totals of the current visible plan -- out[0..3] = kept pairs,
+// k_vis work items, slices of split tiles, dense tiles; false (and zeros) when
+// there is none.  Waits for the device.
+bool GetVisiblePlanTotals(RenderContext* ctx, i64* out) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    return nrtri::visible_plan_totals(ctx, out);
+}
 // New (testing): totals of the context's warm schedule -- out[0..3] = (tile,
 // triangle) pairs, k_vis work items, slices of split tiles, dense tiles;
 // false (and zeros) when it has none.

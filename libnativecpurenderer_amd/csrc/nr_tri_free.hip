@@ -220,14 +220,17 @@ constexpr u32 HEAVY_PAIRS = 256;   // a dense tile (for the k_vis workgroup-size
 // order within each): C3 -0.8 %, 1M tris at 1080p -1.3 %,
 // C2 -2 % per frame (profiles/r03_c3/ab_class_lin.txt).
 constexpr int PLAN_ONE = 10, PLAN_SPLIT = 3, PLAN_NB = 1 + PLAN_ONE + PLAN_SPLIT;
-__device__ __forceinline__ int size_class(u32 c, u32 lim, u32 dsl) {
+// top: the upper end of the one-slice bins -- lim for a binning's plan, the
+// largest one-slice count for the visible plan (k_vis_plan)
+__device__ __forceinline__ int size_class(u32 c, u32 lim, u32 dsl, u32 top) {
     if (c > lim) {
         const u32 ni = (c + dsl - 1) / dsl;
         return PLAN_NB - (ni >= 8 ? 1 : ni >= 4 ? 2 : 3);
     }
     if (c == 0) return 0;
-    return 1 + min((int)((float)c * ((float)PLAN_ONE / (float)(lim + 1))), PLAN_ONE - 1);
+    return 1 + min((int)((float)c * ((float)PLAN_ONE / (float)(top + 1))), PLAN_ONE - 1);
 }
+__device__ __forceinline__ int size_class(u32 c, u32 lim, u32 dsl) { return size_class(c, lim, dsl, lim); }
 
 // Tiles are taken PLAN_T at a time (thread = tile: coalesced), each round a
 // workgroup scan carried over from the previous one.
@@ -2095,6 +2098,7 @@ static void sched_capture(RenderContext* ctx, TriScratch::FreeSet& F, const BinK
     S.tbUid = tb->uid;
     S.key = key;
     S.totals = t;
+    S.splitAt = sc.splitAt; S.dslice = sc.dslice;   // (the limits the binning was planned under: visible_replan)
     static u64 g_gen = 0;
     S.gen = ++g_gen;
     S.waitReady = true;
@@ -2363,16 +2367,147 @@ __global__ __launch_bounds__(256) void k_prune_list(const uint4* __restrict__ it
     }
 }
 
-// The marking frame's set-up: room for the mask, the pruned list and the
-// counts (a regrow waits for the main stream: a queued batch of an earlier
-// generation may still read them; first use or a larger schedule), the mask
-// zeroed on the main stream, and the batch's snapshot pointed at it.
+// ---- visible plan -------------------------------------------------------------
+// The pruned list sits at the full list's offsets, and the schedule's items
+// are the full list's: a tile that held 3000 pairs is still split into three
+// slices of ~150 kept pairs (each zeroes its keys, writes a 16 KB key slot and
+// the last one merges them), and the items run longest first by the full
+// counts.  k_vis_plan plans the kept counts afresh, once per pruning, on the
+// main stream right after k_prune_list: a single workgroup, as k_free_plan,
+// but it only reads the counts (they are the raster's cursors) and the offsets.
+// Its items go to S.vitems and its totals to S.vplan; the layout is the plan
+// kernels' (split tiles' items first -- item index = key slot -- the densest
+// split tiles earliest, empty owned tiles last), so k_vis runs them unchanged:
+// under the loose-format check it slices [off[t], off[t] + vcnt[t]) by the
+// item's own slice count.
+// One-slice classes: PLAN_ONE equal bins of [1, the largest one-slice count of
+// this plan] -- bins of [1, lim] would leave the kept counts (C3: median 195
+// of a limit of 1024) in two or three of the ten classes.
+// Split limits: the visible plan's own (VIS_SPLIT_AT / VIS_DSLICE, or
+// SetSplitLimits') under the schedule's slice length (lim_p, dsl_p: never
+// coarser than the schedule's, and a small batch's short slices are kept).
+// Finer limits than the schedule's can want more items or key
+// slots than there are (icap, kcap: the real capacities): the kernel then
+// plans under the schedule's limits (lim_s, dsl_s), under which no tile has
+// more items than in the full plan, whose items and slots are allocated -- so
+// the plan always fits and the host never waits or regrows for it.
+// Measured (profiles/visible_replan/limits_table.md; ms per frame, parent ->
+// limits 1024 / 512 / 256): C3 0.0769 -> 0.0700 / 0.0707 / 0.0698, 1M triangles
+// at 1080p 0.0617 -> 0.0449 / 0.0513 / 0.0472, an 8-way C3 share 0.0271 ->
+// 0.0218 / 0.0226 / 0.0217.  An item costs 20-35 us almost whatever its pairs
+// (key set-up, shading), a slice that much again plus its slot, so the gain
+// is the work no longer scheduled, and finer slices only add some back: the
+// visible plan splits where the binning's plan does, at 1024.
+constexpr u32 VIS_SPLIT_AT = 1024, VIS_DSLICE = 1024;
+
+__global__ __launch_bounds__(PLAN_T) void k_vis_plan(const u32* __restrict__ vcnt, const u32* __restrict__ off,
+                                                     int ntiles, int tiles_x, int period, u64 mask,
+                                                     uint4* __restrict__ items, u32* __restrict__ totals,
+                                                     u64* __restrict__ host_totals, u32 icap, u32 kcap, u32 seq,
+                                                     u32 lim_p, u32 dsl_p, u32 lim_s, u32 dsl_s) {
+    __shared__ u32 sh[6][PLAN_W];
+    __shared__ u32 smx[2];   // largest one-slice count under the preferred / the schedule's limits
+    __shared__ u32 bcnt[PLAN_NB], bcur[PLAN_NB];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (tid < PLAN_NB) bcnt[tid] = 0;
+    if (tid < 2) smx[tid] = 0;
+    // pass 0: the kept total and the dense tiles
+    u32 a = 0, hv = 0;
+    for (int i = tid; i < ntiles; i += PLAN_T) {
+        const u32 c = vcnt[i];
+        a += c;
+        hv += c >= HEAVY_PAIRS ? 1u : 0u;
+    }
+    a = wave_scan(a, lane); hv = wave_scan(hv, lane);
+    if (lane == 63) { sh[0][w] = a; sh[1][w] = hv; }
+    __syncthreads();
+    u32 ta = 0, th = 0;
+#pragma unroll
+    for (int k = 0; k < PLAN_W; ++k) { ta += sh[0][k]; th += sh[1][k]; }
+    u32 lim = lim_p, dsl = dsl_p;
+    // pass 1: items and split slices under both pairs of limits
+    u32 b = 0, m = 0, b2 = 0, m2 = 0, mx = 0, mx2 = 0;
+    for (int i = tid; i < ntiles; i += PLAN_T) {
+        const u32 c = vcnt[i];
+        const bool owned = owned_row(i / tiles_x, period, mask);
+        const u32 ni = tile_items(c, owned, lim, dsl), ni2 = tile_items(c, owned, lim_s, dsl_s);
+        b += ni;
+        m += ni > 1 ? ni : 0u;
+        b2 += ni2;
+        m2 += ni2 > 1 ? ni2 : 0u;
+        if (owned && c <= lim) mx = max(mx, c);
+        if (owned && c <= lim_s) mx2 = max(mx2, c);
+    }
+    b = wave_scan(b, lane); m = wave_scan(m, lane); b2 = wave_scan(b2, lane); m2 = wave_scan(m2, lane);
+    if (lane == 63) { sh[2][w] = b; sh[3][w] = m; sh[4][w] = b2; sh[5][w] = m2; }
+    if (mx) atomicMax(&smx[0], mx);
+    if (mx2) atomicMax(&smx[1], mx2);
+    __syncthreads();
+    u32 tb = 0, tm = 0, tb2 = 0, tm2 = 0;
+#pragma unroll
+    for (int k = 0; k < PLAN_W; ++k) { tb += sh[2][k]; tm += sh[3][k]; tb2 += sh[4][k]; tm2 += sh[5][k]; }
+    const bool pref = tb <= icap && tm <= kcap;
+    if (!pref) { lim = lim_s; dsl = dsl_s; tb = tb2; tm = tm2; }
+    const u32 top = max(smx[pref ? 0 : 1], 1u);
+    const bool fits = tb <= icap && tm <= kcap;   // (always: see above)
+    // pass 2: items per size class
+    for (int i = tid; i < ntiles; i += PLAN_T) {
+        const u32 c = vcnt[i];
+        const u32 ni = tile_items(c, owned_row(i / tiles_x, period, mask), lim, dsl);
+        if (ni) atomicAdd(&bcnt[size_class(c, lim, dsl, top)], ni);
+    }
+    __syncthreads();
+    if (tid == 0) {   // item ranges of the classes, largest class first
+        u32 base = 0;
+        for (int k = PLAN_NB - 1; k >= 0; --k) { bcur[k] = base; base += bcnt[k]; }
+    }
+    __syncthreads();
+    // pass 3: the items
+    if (fits) {
+        for (int i = tid; i < ntiles; i += PLAN_T) {
+            const u32 c = vcnt[i];
+            const u32 ni = tile_items(c, owned_row(i / tiles_x, period, mask), lim, dsl);
+            if (!ni) continue;
+            const u32 eb = atomicAdd(&bcur[size_class(c, lim, dsl, top)], ni), ea = off[i];
+            for (u32 k = 0; k < ni; ++k) items[eb + k] = tile_item((u32)i, ea, c, k, ni);
+        }
+    }
+    if (tid == 0) {
+        u32 t[PW_COUNT];
+        t[PW_PAIRS] = ta; t[PW_ITEMS] = tb; t[PW_SPLIT] = tm; t[PW_FITS] = fits ? 1u : 0u;
+        t[PW_SEQ] = seq; t[PW_HEAVY] = th; t[PW_LONGEST] = 0u;
+        for (int k = 0; k < PW_DEV; ++k) totals[k] = t[k];
+        for (int k = 0; k < PW_COUNT; ++k)   // (host copy: see k_free_plan)
+            __hip_atomic_store(&host_totals[k], ((u64)seq << 32) | t[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// Items the visible plan can need at most: an item per tile and, over the
+// kept pairs (<= the schedule's), a slice per SLICE_MIN of them.
+static size_t vitems_need(const BatchTotals& t, int ntiles) {
+    return std::max<size_t>((size_t)t.items, (size_t)ntiles + (size_t)t.pairs / SLICE_MIN + 1);
+}
+
+// The marking frame's set-up: room for the mask, the pruned list, the counts
+// and the visible plan (a regrow waits for the main stream: a queued batch of
+// an earlier generation may still read them; first use or a larger schedule),
+// the mask zeroed on the main stream, and the batch's snapshot pointed at it.
 static void visible_mark_begin(RenderContext* ctx, FrameParams& fp, int ntiles) {
     auto& S = ctx->tri.sched;
     const size_t words = ((size_t)fp.src.n + 31) / 32, pairs = std::max<size_t>(S.totals.pairs, 1);
-    if (S.vmask.needs(words) || S.vlist.needs(pairs) || S.vcnt.needs((size_t)ntiles + 3)) {
+    const size_t vitems = vitems_need(S.totals, ntiles);
+    if (S.vmask.needs(words) || S.vlist.needs(pairs) || S.vcnt.needs((size_t)ntiles + 3) || S.vitems.needs(vitems) ||
+        !S.vplan) {
         NR_CHECK(hipStreamSynchronize(ctx->stream));
-        if (!S.vmask.ensure(words) || !S.vlist.ensure(pairs) || !S.vcnt.ensure((size_t)ntiles + 3)) return;
+        if (!S.vmask.ensure(words) || !S.vlist.ensure(pairs) || !S.vcnt.ensure((size_t)ntiles + 3) ||
+            !S.vitems.ensure(vitems))
+            return;
+        if (!S.vplan) NR_CHECK(hipMalloc(&S.vplan, PW_DEV * sizeof(u32)));
+        if (!S.h_vplan) {
+            NR_CHECK(hipHostMalloc((void**)&S.h_vplan, 8 * sizeof(u64), hipHostMallocMapped | hipHostMallocCoherent));
+            for (int k = 0; k < 8; ++k) S.h_vplan[k] = 0;
+            NR_CHECK(hipHostGetDevicePointer((void**)&S.d_hvplan, S.h_vplan, 0));
+        }
     }
     NR_CHECK(hipMemsetAsync(S.vmask, 0, words * sizeof(u32), ctx->stream));
     fp.winMask = S.vmask;
@@ -2409,6 +2544,57 @@ static void visible_prune(RenderContext* ctx, int ntiles) {
                        (u32)std::min<u64>(S.totals.n, 0xFFFFFFFFull), S.vlist.p, S.vcnt.p, S.vcnt.p + ntiles + 2);
     NR_CHECK(hipGetLastError());
     S.visState = 2;
+    S.replanState = 0;
+}
+
+// Visible split limits under test (A/B measurement): NR_VIS_SPLIT_AT /
+// NR_VIS_DSLICE replace VIS_SPLIT_AT / VIS_DSLICE; SetSplitLimits still wins.
+static u32 vis_limit_env(const char* name, u32 def) {
+    const char* e = getenv(name);
+    const long v = e ? atol(e) : 0;
+    return v > 0 ? (u32)v : def;
+}
+
+// The visible plan of the list just pruned (main stream, in stream order after
+// k_prune_list and before the first k_vis that reads it).  The schedule's own
+// limits, the fall-back on the device, are formed as its plan kernel formed
+// them: the slice length from its pair total, the split limits it was binned
+// under.
+static void visible_replan(RenderContext* ctx, const FrameParams& fp, int ntiles) {
+    TriScratch& sc = ctx->tri;
+    auto& S = sc.sched;
+    if (!S.vplan || !S.h_vplan || S.vitems.cap < vitems_need(S.totals, ntiles)) return;
+    static const u32 envAt = vis_limit_env("NR_VIS_SPLIT_AT", VIS_SPLIT_AT);
+    static const u32 envDs = vis_limit_env("NR_VIS_DSLICE", VIS_DSLICE);
+    const u32 sat = sc.splitAt ? sc.splitAt : envAt, dsl = sc.dslice ? sc.dslice : envDs;
+    u32 slice = SLICE_MIN;
+    while (slice < SLICE && (u64)slice * SLICE_TARGET < S.totals.pairs) slice <<= 1;
+    const u32 lim_s = std::min(slice, S.splitAt ? S.splitAt : SPLIT_AT);
+    const u32 dsl_s = std::max<u32>(SLICE_MIN, std::min(lim_s, S.dslice ? S.dslice : DSLICE));
+    const u32 lim_p = std::min(slice, sat), dsl_p = std::max<u32>(SLICE_MIN, std::min(lim_p, dsl));
+    const u32 icap = (u32)std::min<size_t>(S.vitems.cap, 0xFFFFFFF0ull);
+    const u32 kcap = (u32)std::min<size_t>(sc.kslot.cap / (TH * TW), 0xFFFFFFF0ull);
+    if (++S.vplanSeq == 0) S.vplanSeq = 1;   // (the host words start at 0)
+    hipLaunchKernelGGL(k_vis_plan, dim3(1), dim3(PLAN_T), 0, ctx->stream, (const u32*)S.vcnt, (const u32*)S.off, ntiles,
+                       fp.tiles_x, fp.period, fp.mask, S.vitems.p, S.vplan, S.d_hvplan, icap, kcap, S.vplanSeq,
+                       lim_p, dsl_p, lim_s, dsl_s);
+    NR_CHECK(hipGetLastError());
+    S.replanState = 1;
+}
+
+// The visible plan's totals once the host has seen every word of them (no wait).
+static bool vplan_seen(TriScratch::Schedule& S) {
+    if (S.replanState == 2) return true;
+    if (S.replanState != 1) return false;
+    u32 v[PW_COUNT];
+    for (int k = 0; k < PW_COUNT; ++k) {
+        const u64 x = __atomic_load_n(&S.h_vplan[k], __ATOMIC_ACQUIRE);
+        if ((u32)(x >> 32) != S.vplanSeq) return false;
+        v[k] = (u32)x;
+    }
+    S.vtotals = BatchTotals{S.totals.n, v[PW_PAIRS], v[PW_ITEMS], v[PW_SPLIT], v[PW_HEAVY]};
+    S.replanState = 2;
+    return true;
 }
 
 // loose: the batch's transform differs from the schedule's (loose_matches):
@@ -2449,7 +2635,40 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
         if (pruning && S.visState == 1) visible_prune(ctx, ntiles);
         if (pruning && S.visState == 2 && S.visZ == zm) {
             const WarmCheck wv{S.vcnt + ntiles, S.vcnt, S.off, 1u, 1u, sc.dfail, 1u};
-            vis_tail(ctx, F, fp, VisArgs{S.items, S.vlist, S.dplan, wv}, std::min<u32>(T.items, 8192));
+            // The visible plan (above), unless SetVisibleReplan(2): planned
+            // once per pruning, here when the list was pruned with the switch
+            // off.  Its items and plan words are in stream order before this
+            // raster.  The grid is the schedule's until the host has seen the
+            // plan's totals (k_vis strides over plan[PW_ITEMS] items, whatever
+            // the grid), then the visible item count.
+            // NR_VIS_WIDE=1 (A/B): the workgroup-size choice follows the visible
+            // dense-tile count; by default it keeps the schedule's (an 8-way C3
+            // share measured no gain, profiles/visible_replan/limits_table.md).
+            // Only a schedule with split tiles is planned again: the measured
+            // gain is the slices and merges no longer scheduled.  Without any,
+            // the plan could only reorder the items, and C2 (no split tile, as
+            // many items as workgroup slots) measured 2.7 % slower with it than
+            // under the schedule's order (profiles/visible_replan/ab_bench.json).
+            VisArgs va{S.items, S.vlist, S.dplan, wv};
+            u32 grid = std::min<u32>(T.items, 8192);
+            if (sc.replanMode != 2 && T.split > 0) {
+                if (S.replanState == 0) visible_replan(ctx, fp, ntiles);
+                if (S.replanState != 0) {
+                    va.items = S.vitems;
+                    va.plan = S.vplan;
+                    if (vplan_seen(S)) {
+                        grid = std::min<u32>(std::max<u32>(S.vtotals.items, 1), 8192);
+                        static const bool visWide = [] {
+                            const char* e = getenv("NR_VIS_WIDE");
+                            return e && atoi(e) == 1;
+                        }();
+                        if (visWide) sc.last.heavy = S.vtotals.heavy;
+                    }
+                    ++sc.replannedBatches;
+                }
+            }
+            vis_tail(ctx, F, fp, va, grid);
+            sc.last = T;
             ++sc.reusedBatches;
             ++sc.prunedBatches;
             return true;
@@ -2753,6 +2972,18 @@ i64 visible_pairs(RenderContext* ctx) {
     NR_CHECK(hipStreamSynchronize(ctx->stream));
     NR_CHECK(hipMemcpy(&v, S.vcnt.p + ntiles + 2, sizeof v, hipMemcpyDeviceToHost));
     return (i64)v;
+}
+
+// Totals of the context's visible plan -- pairs, work items, slices of split
+// tiles, dense tiles -- false when it has none (waits for the main stream).
+bool visible_plan_totals(RenderContext* ctx, i64* out) {
+    auto& S = ctx->tri.sched;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!S.valid || S.visState != 2 || S.replanState == 0) return false;
+    NR_CHECK(hipStreamSynchronize(ctx->stream));
+    if (!vplan_seen(S)) return false;
+    out[0] = S.vtotals.pairs; out[1] = S.vtotals.items; out[2] = S.vtotals.split; out[3] = S.vtotals.heavy;
+    return true;
 }
 
 }  // namespace nrtri

@@ -650,6 +650,25 @@ class RenderContext:
         off (reused batches rasterise from the full pair list)."""
         lib.SetVisiblePruning(self._ptr, int(mode))
 
+    def set_visible_replan(self, mode: int):
+        """The visible plan -- work items of the visible list planned from its
+        kept counts: 0 automatic (on), 2 off (pruned batches run the
+        schedule's items over the pruned list in place)."""
+        lib.SetVisibleReplan(self._ptr, int(mode))
+
+    def replanned_batch_count(self) -> int:
+        """Of the pruned batches, those rasterised under the visible plan."""
+        return lib.GetReplannedBatchCount(self._ptr)
+
+    def visible_plan_totals(self) -> typing.Optional[dict]:
+        """Testing: totals of the current visible plan -- kept pairs, k_vis
+        work items, slices of split tiles, dense tiles -- or None when there
+        is none.  Waits for the device."""
+        out = (ctypes.c_long * 4)()
+        if not lib.GetVisiblePlanTotals(self._ptr, out):
+            return None
+        return {"pairs": out[0], "items": out[1], "split": out[2], "heavy": out[3]}
+
     def schedule_totals(self) -> typing.Optional[dict]:
         """Testing: totals of the context's warm schedule -- (tile, triangle)
         pairs, k_vis work items, slices of split tiles, dense tiles -- or None
