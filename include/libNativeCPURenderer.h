@@ -230,6 +230,28 @@ bool AssembleMeshPerspective(RenderContext* ctx, Mesh* m, const f64* matrix16, i
                                  kernels): the full count in *n_out, the first min(cap, *n_out) triangles copied to the
                                  host (xy x6, z x3, uv x6, q x3; q is 1.0 with the state off); a sync point; a textured
                                  mesh only */
+/* NEW: instanced mesh draws (DESIGN §3 "Instanced mesh draws"): one mesh under K row-major 4x4 matrices (K*16) as
+   ONE batch -- by definition the frame of K DrawMesh / DrawTexturedMesh calls in instance order (triangle t of
+   instance k is triangle k*n + t of the batch), from one vertex and assembly pass and one binning.  Every state
+   of DrawMesh applies unchanged (transform, depth, colour transform, near plane, cull, perspective, filter,
+   sharding); GetMeshLastTriangleCount is the batch's total.  tint: K*4 (r, g, b, a) or NULL -- every vertex colour
+   of instance k times tint[k] (one rounded product, before anything else); NULL: no product.  A textured mesh
+   takes no tint.  K == 0 draws nothing; K < 0, NULL matrices with K > 0, a tint on a textured mesh, or more than
+   2^31 - 1 triangles (K*n) or vertices (K*nv): error latched, nothing drawn, the last count 0. */
+void DrawMeshInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* tint, i64 K);   /* NEW: host
+                                 arrays, the caller's again on return */
+void DrawTexturedMeshInstanced(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrices, i64 K);   /* NEW */
+void DrawMeshInstancedDevice(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* tint, i64 K);   /* NEW:
+                                 device pointers, valid and unchanged until the draw has executed (as
+                                 DrawTrianglesDevice); read only by kernels launched inside the call */
+void DrawTexturedMeshInstancedDevice(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrices, i64 K);   /* NEW */
+bool AssembleMeshInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* tint, i64 K, i64 cap,
+                           f64* xy_out, f64* z_out, f64* attr_out, f64* q_out, i64* n_out);   /* NEW: the soup an
+                                 instanced draw of m rasterises under ctx's near plane, cull mode and perspective
+                                 state (the draw's own kernels; host matrices and tint): the full count in *n_out, the
+                                 first min(cap, *n_out) triangles copied to the host (xy x6, z x3, attr x12 / x4 / x6;
+                                 q x3 only for a perspective textured draw, q_out may be NULL otherwise); a sync
+                                 point; either mesh kind */
 void SetFragmentCounting(RenderContext* ctx, bool on);                   /* NEW: covered-fragment counter */
 i64 GetFragmentCount(RenderContext* ctx);                                /* NEW */
 i64 GetLastRasterPath(RenderContext* ctx);                               /* NEW: 1 order-free tiled, 2 ordered */

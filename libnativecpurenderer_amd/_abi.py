@@ -102,6 +102,11 @@ DEVICE_ABI = {
     "SetMeshPerspective": (B, (P, B)),
     "GetMeshPerspective": (B, (P,)),
     "AssembleMeshPerspective": (B, (P, P, P, L, P, P, P, P, P)),
+    "DrawMeshInstanced": (None, (P, P, P, P, L)),
+    "DrawTexturedMeshInstanced": (None, (P, P, P, P, L)),
+    "DrawMeshInstancedDevice": (None, (P, P, P, P, L)),
+    "DrawTexturedMeshInstancedDevice": (None, (P, P, P, P, L)),
+    "AssembleMeshInstanced": (B, (P, P, P, P, L, L, P, P, P, P, P)),
     "SetFragmentCounting": (None, (P, B)),
     "GetFragmentCount": (L, (P,)),
     "GetLastRasterPath": (L, (P,)),

@@ -330,7 +330,10 @@ static const char* kKernelNames[NRK_COUNT_] = {"tri_count", "tri_scan",    "tri_
                                                "resolve",   "vis_init",    "output",   "gather",
                                                "mesh_vertex", "mesh_assemble",
                                                "mesh_clip_vertex", "mesh_clip_count", "mesh_clip_scan",
-                                               "mesh_clip_emit"};
+                                               "mesh_clip_emit",
+                                               "mesh_inst_vertex", "mesh_inst_assemble",
+                                               "mesh_inst_clip_vertex", "mesh_inst_clip_count",
+                                               "mesh_inst_clip_scan", "mesh_inst_clip_emit"};
 
 extern "C" {
 

@@ -161,6 +161,14 @@ struct TriScratch {
     // n_out*attr_stride, and a perspective textured draw's q n_out*3 -- is then what mstage holds
     DevArray<f64> mclip;
     DevArray<u32> mscan;
+    // instanced mesh draws (nr_mesh.hip, DrawMeshInstanced): the draw's K matrices (K*16) and, behind them, its
+    // tints (K*4) on the device, overwritten only after settle like mstage; a host call's arrays reach it through
+    // one of the two pinned h_minst, in turn, by an asynchronous copy (evMinst: that copy is done, the buffer
+    // may be rewritten)
+    DevArray<f64> minst;
+    f64* h_minst[2] = {nullptr, nullptr}; size_t h_minst_cap[2] = {0, 0};
+    hipEvent_t evMinst[2] = {nullptr, nullptr};
+    int minstNext = 0;
     // warm binning (nr_tri_free.hip): the tile offsets, k_vis work items and
     // plan totals of the last validated binning of one TriangleBuffer under
     // one binning key -- a later draw of the same buffer under the same key
@@ -261,6 +269,11 @@ struct TriScratch {
         cnt.release(); off.release(); orec.release(); tile_start.release(); tile_end.release();
         for (int k = 0; k < 2; ++k) { keys[k].release(); vals[k].release(); }
         fdone.release(); kslot.release(); stage.release(); mstage.release(); mclip.release(); mscan.release();
+        minst.release();
+        for (int k = 0; k < 2; ++k) {
+            if (h_minst[k]) NR_CHECK(hipHostFree(h_minst[k]));
+            if (evMinst[k]) NR_CHECK(hipEventDestroy(evMinst[k]));
+        }
         if (temp) NR_CHECK(hipFree(temp));
         if (d_frag) NR_CHECK(hipFree(d_frag));
         if (d_flag) NR_CHECK(hipFree(d_flag));
@@ -275,7 +288,8 @@ struct TriScratch {
 enum NRKernelId { NRK_TRI_COUNT = 0, NRK_TRI_SCAN, NRK_TRI_EMIT, NRK_TRI_SORT, NRK_TILE_RANGES,
                   NRK_TILE_RASTER, NRK_PRIM, NRK_FILL, NRK_RESOLVE, NRK_VIS_INIT, NRK_OUTPUT, NRK_GATHER,
                   NRK_MESH_VERTEX, NRK_MESH_ASSEMBLE, NRK_MESH_CLIP_VERTEX, NRK_MESH_CLIP_COUNT, NRK_MESH_CLIP_SCAN,
-                  NRK_MESH_CLIP_EMIT, NRK_COUNT_ };
+                  NRK_MESH_CLIP_EMIT, NRK_MESH_INST_VERTEX, NRK_MESH_INST_ASSEMBLE, NRK_MESH_INST_CLIP_VERTEX,
+                  NRK_MESH_INST_CLIP_COUNT, NRK_MESH_INST_CLIP_SCAN, NRK_MESH_INST_CLIP_EMIT, NRK_COUNT_ };
 
 struct RenderContext {
     i64 width = 0, height = 0;

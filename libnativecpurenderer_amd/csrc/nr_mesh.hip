@@ -33,12 +33,20 @@
 // offsets (a stable compaction: submission order is kept).  The draw reads the
 // total back before it bins, so such a draw -- and only such a draw -- waits
 // for the device once.  With both off nothing here runs.
+//
+// Instanced draws (DrawMeshInstanced and its kin, DESIGN.md §3 "Instanced mesh
+// draws"): one mesh under K matrices as ONE batch whose frame is, by definition,
+// that of K DrawMesh calls in instance order.  The same passes run once over
+// K*nv vertices and K*n triangles (k_minst_*), the assembly also copying -- or
+// tinting -- the mesh's attributes to each instance's place in the batch; the
+// single-draw kernels and host path are untouched.
 #include "nr_tri.h"
 
 #include <hipcub/hipcub.hpp>
 
 #include <climits>
 #include <cmath>
+#include <cstring>
 #include <initializer_list>
 #include <string>
 
@@ -219,11 +227,9 @@ __device__ __forceinline__ bool clip_culled(const ClipPos& p0, const ClipPos& p1
 // Pass C2: one thread per source triangle: which of its output triangles survive
 // the clip and the cull (keep: bit 0 the first, bit 1 the second half of a
 // quad) and how many (cnt, the scan's input).  Without a cull no vertex is formed.
-__global__ __launch_bounds__(256) void k_mesh_clip_count(const u32* __restrict__ idx, i64 n,
-                                                         const double2* __restrict__ clip, f64 wNear, int cull,
-                                                         u32* __restrict__ keep, u32* __restrict__ cnt) {
-    const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
+// (clip_keep: the same decision for one triangle, shared with the instanced count pass)
+__device__ __forceinline__ u32 clip_keep(const u32* __restrict__ idx, const double2* __restrict__ clip, i64 t, f64 wNear,
+                                         int cull) {
     ClipTri c;
     load_clip_tri(idx, clip, t, c);
     const int code = inside_code(c, wNear);
@@ -238,6 +244,14 @@ __global__ __launch_bounds__(256) void k_mesh_clip_count(const u32* __restrict__
             if (clip_culled(q0, q2, q3, cull)) k &= ~2u;
         }
     }
+    return k;
+}
+__global__ __launch_bounds__(256) void k_mesh_clip_count(const u32* __restrict__ idx, i64 n,
+                                                         const double2* __restrict__ clip, f64 wNear, int cull,
+                                                         u32* __restrict__ keep, u32* __restrict__ cnt) {
+    const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const u32 k = clip_keep(idx, clip, t, wNear, cull);
     keep[t] = k;
     cnt[t] = (k & 1u) + (k >> 1);
 }
@@ -269,18 +283,14 @@ __device__ __forceinline__ void clip_store_pos(i64 o, const ClipPos& p0, const C
 // word j in, the polygon's word j out -- so nothing is held in an array.
 // Q (a perspective textured draw): also each output corner's 1/w (clip_slot_q)
 // into oq, laid out like z.
-template <int H, bool Q = false>
-__global__ __launch_bounds__(256) void k_mesh_clip_emit(const u32* __restrict__ idx, i64 n,
-                                                        const double2* __restrict__ clip,
-                                                        const double2* __restrict__ attr, f64 wNear,
-                                                        const u32* __restrict__ keep, const u32* __restrict__ off,
-                                                        double2* __restrict__ xy, f64* __restrict__ z,
-                                                        double2* __restrict__ oattr, f64* __restrict__ oq) {
-    const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
-    const u32 k = keep[t];
-    if (k == 0) return;
-    const i64 o0 = (i64)off[t];         // the first kept triangle
+// (clip_emit_tri: source triangle t with keep mask k != 0, its first kept triangle at o0; shared with the
+// instanced emit pass, whose TINT instances multiply each colour word by the instance's tint (r, g | b, a) as
+// it is loaded, before any interpolation.)
+template <int H, bool Q, bool TINT>
+__device__ __forceinline__ void clip_emit_tri(const u32* __restrict__ idx, const double2* __restrict__ clip,
+                                              const double2* __restrict__ attr, const f64* __restrict__ tint, f64 wNear,
+                                              i64 t, u32 k, i64 o0, double2* __restrict__ xy, f64* __restrict__ z,
+                                              double2* __restrict__ oattr, f64* __restrict__ oq) {
     const i64 o1 = o0 + (i64)(k & 1u);  // the second half of a quad, when kept
     ClipTri c;
     load_clip_tri(idx, clip, t, c);
@@ -314,13 +324,23 @@ __global__ __launch_bounds__(256) void k_mesh_clip_emit(const u32* __restrict__ 
         }
     }
     if constexpr (H == 0) {
-        const double2 c0 = attr[t * 2], c1 = attr[t * 2 + 1];
+        double2 c0 = attr[t * 2], c1 = attr[t * 2 + 1];
+        if constexpr (TINT) {
+            c0 = make_double2(c0.x * tint[0], c0.y * tint[1]);
+            c1 = make_double2(c1.x * tint[2], c1.y * tint[3]);
+        }
         if (k & 1u) { oattr[o0 * 2] = c0; oattr[o0 * 2 + 1] = c1; }
         if (k & 2u) { oattr[o1 * 2] = c0; oattr[o1 * 2 + 1] = c1; }
     } else {
 #pragma unroll
         for (int j = 0; j < H; ++j) {
-            const double2 w0 = attr[t * (3 * H) + j], w1 = attr[t * (3 * H) + H + j], w2 = attr[t * (3 * H) + 2 * H + j];
+            double2 w0 = attr[t * (3 * H) + j], w1 = attr[t * (3 * H) + H + j], w2 = attr[t * (3 * H) + 2 * H + j];
+            if constexpr (TINT) {   // (H == 2: word j of a corner is (r, g) or (b, a))
+                const f64 ta = tint[2 * j], tb = tint[2 * j + 1];
+                w0 = make_double2(w0.x * ta, w0.y * tb);
+                w1 = make_double2(w1.x * ta, w1.y * tb);
+                w2 = make_double2(w2.x * ta, w2.y * tb);
+            }
             const double2 e0 = make_double2(clip_attr(a0, b0, q0.t, w0.x, w1.x, w2.x),
                                             clip_attr(a0, b0, q0.t, w0.y, w1.y, w2.y));
             const double2 e2 = make_double2(clip_attr(a2, b2, q2.t, w0.x, w1.x, w2.x),
@@ -339,6 +359,156 @@ __global__ __launch_bounds__(256) void k_mesh_clip_emit(const u32* __restrict__ 
             }
         }
     }
+}
+template <int H, bool Q = false>
+__global__ __launch_bounds__(256) void k_mesh_clip_emit(const u32* __restrict__ idx, i64 n,
+                                                        const double2* __restrict__ clip,
+                                                        const double2* __restrict__ attr, f64 wNear,
+                                                        const u32* __restrict__ keep, const u32* __restrict__ off,
+                                                        double2* __restrict__ xy, f64* __restrict__ z,
+                                                        double2* __restrict__ oattr, f64* __restrict__ oq) {
+    const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const u32 k = keep[t];
+    if (k == 0) return;
+    const i64 o0 = (i64)off[t];         // the first kept triangle
+    clip_emit_tri<H, Q, false>(idx, clip, attr, nullptr, wNear, t, k, o0, xy, z, oattr, oq);
+}
+
+// ---- instanced draws (DESIGN.md §3 "Instanced mesh draws") ----------------------
+// One mesh under K matrices as one soup: instance k's vertices are vertices k*nv ..
+// of the batch's vertex table, its triangles k*n .. of the soup.  Every pass runs
+// on a flat thread index over all instances (K*nv, 3*K*n or K*n threads, each
+// below 2^31), so that waves stay full however small the mesh; the instance of a
+// thread is one 32-bit division, and its matrix is loaded per lane from the
+// device array (lanes of one instance read the same 128 bytes: a wave of a large
+// mesh fetches one matrix, a wave of tiny meshes a few neighbouring ones).
+struct InstOf { u32 k, r; };   // instance and the index inside it
+__device__ __forceinline__ InstOf inst_of(u32 g, u32 per) {
+    const u32 k = g / per;
+    return InstOf{k, g - k * per};
+}
+
+__device__ __forceinline__ Mat4 inst_matrix(const f64* __restrict__ mats, u32 k) {
+    Mat4 M;
+    const f64* p = mats + (size_t)k * 16;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) M.m[j] = p[j];
+    return M;
+}
+
+// the clip coordinates of k_mesh_vertex / k_mesh_clip_vertex: the same expressions
+__device__ __forceinline__ void clip_rows(const Mat4& M, f64 px, f64 py, f64 pz, f64& cx, f64& cy, f64& cz, f64& cw) {
+    cx = ((M.m[0] * px + M.m[1] * py) + M.m[2] * pz) + M.m[3];
+    cy = ((M.m[4] * px + M.m[5] * py) + M.m[6] * pz) + M.m[7];
+    cz = ((M.m[8] * px + M.m[9] * py) + M.m[10] * pz) + M.m[11];
+    cw = ((M.m[12] * px + M.m[13] * py) + M.m[14] * pz) + M.m[15];
+}
+
+// Pass 1 of an instanced draw: one thread per (instance, vertex), g = k * nv + v.
+template <bool Q>
+__global__ __launch_bounds__(256) void k_minst_vertex(const f64* __restrict__ pos, u32 nv, u32 total,
+                                                      const f64* __restrict__ mats, double2* __restrict__ vxy,
+                                                      f64* __restrict__ vz, f64* __restrict__ vq) {
+    const u32 g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= total) return;
+    const InstOf in = inst_of(g, nv);
+    const Mat4 M = inst_matrix(mats, in.k);
+    const f64 px = pos[(size_t)in.r * 3], py = pos[(size_t)in.r * 3 + 1], pz = pos[(size_t)in.r * 3 + 2];
+    f64 cx, cy, cz, cw;
+    clip_rows(M, px, py, pz, cx, cy, cz, cw);
+    f64 x = NAN, y = NAN, z = NAN;
+    if (cw > 0) {
+        x = cx / cw;
+        y = cy / cw;
+        z = cz / cw;
+    }
+    vxy[g] = make_double2(x, y);
+    vz[g] = z;
+    if constexpr (Q) vq[g] = cw > 0 ? 1.0 / cw : NAN;
+}
+
+// Pass 2: one thread per corner of the batch, c = k * 3n + (the mesh's corner):
+// the gather of k_mesh_assemble from instance k's part of the vertex table, and
+// the batch's attributes -- the rasters index them by batch triangle -- from the
+// mesh's expanded ones: H 16-byte words per corner (2 Gouraud, 1 textured), or
+// for a flat mesh (H == 0) the triangle's two words, written by its corners 0 and
+// 1.  TINT: each colour word times the instance's tint, else a plain copy.
+template <int H, bool Q, bool TINT>
+__global__ __launch_bounds__(256) void k_minst_assemble(const u32* __restrict__ idx, u32 per, u32 total, u32 nv,
+                                                        const double2* __restrict__ vxy, const f64* __restrict__ vz,
+                                                        const f64* __restrict__ vq, const double2* __restrict__ attr,
+                                                        const f64* __restrict__ tint, double2* __restrict__ xy,
+                                                        f64* __restrict__ z, f64* __restrict__ q,
+                                                        double2* __restrict__ oattr) {
+    const u32 c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= total) return;
+    const InstOf in = inst_of(c, per);
+    const size_t i = (size_t)in.k * nv + idx[in.r];
+    xy[c] = vxy[i];
+    z[c] = vz[i];
+    if constexpr (Q) q[c] = vq[i];
+    const f64* tk = tint + (size_t)in.k * 4;   // (TINT only)
+    if constexpr (H == 0) {
+        const u32 t = in.r / 3u, w = in.r - t * 3u;   // (c / 3 is the batch triangle: 3n divides k * 3n)
+        if (w < 2u) {
+            double2 a = attr[(size_t)t * 2 + w];
+            if constexpr (TINT) a = make_double2(a.x * tk[2 * w], a.y * tk[2 * w + 1]);
+            oattr[(size_t)(c / 3u) * 2 + w] = a;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            double2 a = attr[(size_t)in.r * H + j];
+            if constexpr (TINT) a = make_double2(a.x * tk[2 * j], a.y * tk[2 * j + 1]);
+            oattr[(size_t)c * H + j] = a;
+        }
+    }
+}
+
+// Pass C1 of an instanced draw: k_mesh_clip_vertex per (instance, vertex).
+__global__ __launch_bounds__(256) void k_minst_clip_vertex(const f64* __restrict__ pos, u32 nv, u32 total,
+                                                           const f64* __restrict__ mats, double2* __restrict__ clip) {
+    const u32 g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= total) return;
+    const InstOf in = inst_of(g, nv);
+    const Mat4 M = inst_matrix(mats, in.k);
+    const f64 px = pos[(size_t)in.r * 3], py = pos[(size_t)in.r * 3 + 1], pz = pos[(size_t)in.r * 3 + 2];
+    f64 cx, cy, cz, cw;
+    clip_rows(M, px, py, pz, cx, cy, cz, cw);
+    clip[(size_t)g * 2] = make_double2(cx, cy);
+    clip[(size_t)g * 2 + 1] = make_double2(cz, cw);
+}
+
+// Pass C2: k_mesh_clip_count per (instance, triangle), g = k * n + t: the keep
+// masks and counts of the whole batch, scanned at once.
+__global__ __launch_bounds__(256) void k_minst_clip_count(const u32* __restrict__ idx, u32 n, u32 total, u32 nv,
+                                                          const double2* __restrict__ clip, f64 wNear, int cull,
+                                                          u32* __restrict__ keep, u32* __restrict__ cnt) {
+    const u32 g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= total) return;
+    const InstOf in = inst_of(g, n);
+    const u32 k = clip_keep(idx, clip + (size_t)in.k * nv * 2, (i64)in.r, wNear, cull);
+    keep[g] = k;
+    cnt[g] = (k & 1u) + (k >> 1);
+}
+
+// Pass C3: k_mesh_clip_emit per (instance, triangle) at the batch's scanned offsets.
+template <int H, bool Q, bool TINT>
+__global__ __launch_bounds__(256) void k_minst_clip_emit(const u32* __restrict__ idx, u32 n, u32 total, u32 nv,
+                                                         const double2* __restrict__ clip,
+                                                         const double2* __restrict__ attr, const f64* __restrict__ tint,
+                                                         f64 wNear, const u32* __restrict__ keep,
+                                                         const u32* __restrict__ off, double2* __restrict__ xy,
+                                                         f64* __restrict__ z, double2* __restrict__ oattr,
+                                                         f64* __restrict__ oq) {
+    const u32 g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= total) return;
+    const u32 k = keep[g];
+    if (k == 0) return;
+    const InstOf in = inst_of(g, n);
+    clip_emit_tri<H, Q, TINT>(idx, clip + (size_t)in.k * nv * 2, attr, tint + (size_t)in.k * 4, wNear, (i64)in.r, k,
+                              (i64)off[g], xy, z, oattr, oq);
 }
 
 unsigned blocks_for(i64 threads) { return (unsigned)((threads + 255) / 256); }
@@ -526,6 +696,202 @@ bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup
 bool draw_soup(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out) {
     const bool persp = persp_draw(ctx, m);
     return clip_stage_on(ctx) ? assemble_clipped(ctx, m, matrix, out, persp) : assemble(ctx, m, matrix, out, persp);
+}
+
+// ---- instanced draws: host side ---------------------------------------------------
+// The K matrices (K*16) and tints (K*4, or null) of an instanced draw, on the device.
+struct Instances { const f64* mats; const f64* tint; i64 K; };
+bool check_mesh(RenderContext* ctx, const Mesh* m, bool textured, const char* what);
+
+// The argument checks every instanced entry point shares, after the mesh's own: false with an error latched under
+// `what`, or *empty when there is nothing to draw (no error).  Nothing is allocated or read before them.
+// frame: an empty context counts as nothing to draw (the draws; AssembleMeshInstanced needs no frame).
+bool check_instances(const RenderContext* ctx, const Mesh* m, const f64* matrices, const f64* tint, i64 K, bool frame,
+                     bool* empty, const char* what) {
+    *empty = true;
+    if (K < 0) return fail(what, "negative instance count");
+    if (tint && m->mode == nrtri::ATTR_TEX) return fail(what, "a textured mesh takes no tint");
+    if (K == 0 || m->n <= 0 || (frame && (ctx->width <= 0 || ctx->height <= 0))) return true;
+    if (!matrices) return fail(what, "NULL matrices");
+    if (K > (i64)INT_MAX / m->n) return fail(what, "more than 2^31 - 1 triangles");
+    if (K > (i64)INT_MAX / m->nv) return fail(what, "more than 2^31 - 1 vertices");
+    *empty = false;
+    return true;
+}
+
+// A host call's matrices and tints onto the device (TriScratch::minst), through the context's pinned buffer by
+// one asynchronous copy: the caller's arrays are free when this returns and the host waits for nothing but an
+// earlier such copy (of the draw before last), long done.  (The copy-and-wait of DrawTriangles' staging would add a host wait to every
+// draw, which is what an instanced draw is there to avoid.)  Settles first: minst follows mstage's rule.
+bool upload_instances(RenderContext* ctx, const f64* matrices, const f64* tint, i64 K, Instances* out) {
+    nrtri::settle(ctx);
+    TriScratch& sc = ctx->tri;
+    const size_t k = (size_t)K, need = k * (tint ? 20 : 16);
+    if (!sc.minst.ensure(need)) return false;
+    const int slot = sc.minstNext;   // two pinned buffers in turn: the wait is for the copy of the draw before last
+    sc.minstNext ^= 1;
+    if (sc.evMinst[slot]) NR_CHECK(hipEventSynchronize(sc.evMinst[slot]));
+    else NR_CHECK(hipEventCreateWithFlags(&sc.evMinst[slot], hipEventDisableTiming));
+    if (sc.h_minst_cap[slot] < need) {
+        if (sc.h_minst[slot]) NR_CHECK(hipHostFree(sc.h_minst[slot]));
+        sc.h_minst[slot] = nullptr;
+        sc.h_minst_cap[slot] = 0;
+        if (hipHostMalloc((void**)&sc.h_minst[slot], need * sizeof(f64)) != hipSuccess) {
+            (void)hipGetLastError();
+            sc.h_minst[slot] = nullptr;
+            return fail("instanced mesh draw", "hipHostMalloc failed");
+        }
+        sc.h_minst_cap[slot] = need;
+    }
+    f64* h = sc.h_minst[slot];
+    std::memcpy(h, matrices, k * 16 * sizeof(f64));
+    if (tint) std::memcpy(h + k * 16, tint, k * 4 * sizeof(f64));
+    NR_CHECK(hipMemcpyAsync(sc.minst.p, h, need * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
+    NR_CHECK(hipEventRecord(sc.evMinst[slot], ctx->stream));
+    *out = Instances{sc.minst.p, tint ? sc.minst.p + k * 16 : nullptr, K};
+    return true;
+}
+
+// assemble() for K instances (m->n > 0, K > 0, K*n and K*nv below 2^31): the vertex table of all instances, then
+// the soup and its attributes -- xy N*6 | z N*3 (padded to an even count) | attributes N*stride | q N*3, the
+// clipped soup's layout -- in ctx's mesh staging, N = K*n.
+bool assemble_instanced(RenderContext* ctx, const Mesh* m, const Instances& in, Soup* out, bool persp) {
+    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
+    TriScratch& sc = ctx->tri;
+    const size_t NV = (size_t)in.K * (size_t)m->nv, N = (size_t)in.K * (size_t)m->n;
+    const size_t vzn = (NV + 1) & ~(size_t)1, zn = (N * 3 + 1) & ~(size_t)1;   // keep xy and the attributes 16-byte aligned
+    const size_t stride = (size_t)nrtri::attr_stride(m->mode);
+    if (!sc.mstage.ensure(NV * 2 + vzn + (persp ? vzn : 0) + N * 6 + zn + N * stride + (persp ? N * 3 : 0))) return false;
+    f64* vxy = sc.mstage;
+    f64* vz = vxy + NV * 2;
+    f64* vq = persp ? vz + vzn : nullptr;
+    f64* xy = vz + vzn + (persp ? vzn : 0);
+    f64* z = xy + N * 6;
+    f64* attr = z + zn;
+    f64* q = persp ? attr + N * stride : nullptr;
+    const bool tint = in.tint != nullptr;
+    const auto vertex = persp ? k_minst_vertex<true> : k_minst_vertex<false>;
+    const auto gather = m->mode == nrtri::ATTR_GOURAUD ? (tint ? k_minst_assemble<2, false, true> : k_minst_assemble<2, false, false>)
+                        : m->mode != nrtri::ATTR_TEX   ? (tint ? k_minst_assemble<0, false, true> : k_minst_assemble<0, false, false>)
+                        : persp                        ? k_minst_assemble<1, true, false>
+                                                       : k_minst_assemble<1, false, false>;
+    hipEvent_t a, b;
+    nr_timing_begin(ctx, NRK_MESH_INST_VERTEX, &a, &b);
+    hipLaunchKernelGGL(vertex, dim3(blocks_for((i64)NV)), dim3(256), 0, ctx->stream, m->pos, (u32)m->nv, (u32)NV, in.mats,
+                       reinterpret_cast<double2*>(vxy), vz, vq);
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_INST_VERTEX, a, b);
+    nr_timing_begin(ctx, NRK_MESH_INST_ASSEMBLE, &a, &b);
+    hipLaunchKernelGGL(gather, dim3(blocks_for((i64)N * 3)), dim3(256), 0, ctx->stream, m->idx, (u32)(m->n * 3),
+                       (u32)(N * 3), (u32)m->nv, reinterpret_cast<const double2*>(vxy), vz, vq,
+                       reinterpret_cast<const double2*>(m->attr), in.tint, reinterpret_cast<double2*>(xy), z, q,
+                       reinterpret_cast<double2*>(attr));
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_INST_ASSEMBLE, a, b);
+    *out = Soup{xy, z, attr, q, (i64)N};
+    return true;
+}
+
+// assemble_clipped() for K instances: the count, the scan and the emit run once over all K*n triangles, with one
+// read-back of the total, so the instances' clipped soups follow each other in instance order.
+bool assemble_instanced_clipped(RenderContext* ctx, const Mesh* m, const Instances& in, Soup* out, bool persp) {
+    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
+    TriScratch& sc = ctx->tri;
+    const size_t NV = (size_t)in.K * (size_t)m->nv, N = (size_t)in.K * (size_t)m->n;
+    if (!sc.mclip.ensure(NV * 4) || !sc.mscan.ensure(N * 3)) return false;
+    u32* keep = sc.mscan;
+    u32* cnt = keep + N;
+    u32* off = cnt + N;
+    size_t need = 0;
+    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, cnt, off, (int)N, ctx->stream));
+    if (!grow_temp(sc, need > 0 ? need : 1)) return false;
+    u32* h = reinterpret_cast<u32*>(sc.totals());
+    if (!h) return fail("mesh clip stage", "hipHostMalloc failed");
+    const f64 wNear = ctx->meshNear;
+    const double2* clip = reinterpret_cast<const double2*>(sc.mclip.p);
+    const u32 nv = (u32)m->nv, n = (u32)m->n;
+    hipEvent_t a, b;
+    nr_timing_begin(ctx, NRK_MESH_INST_CLIP_VERTEX, &a, &b);
+    hipLaunchKernelGGL(k_minst_clip_vertex, dim3(blocks_for((i64)NV)), dim3(256), 0, ctx->stream, m->pos, nv, (u32)NV,
+                       in.mats, reinterpret_cast<double2*>(sc.mclip.p));
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_INST_CLIP_VERTEX, a, b);
+    nr_timing_begin(ctx, NRK_MESH_INST_CLIP_COUNT, &a, &b);
+    hipLaunchKernelGGL(k_minst_clip_count, dim3(blocks_for((i64)N)), dim3(256), 0, ctx->stream, m->idx, n, (u32)N, nv,
+                       clip, wNear, ctx->meshCull, keep, cnt);
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_INST_CLIP_COUNT, a, b);
+    nr_timing_begin(ctx, NRK_MESH_INST_CLIP_SCAN, &a, &b);
+    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(sc.temp, need, cnt, off, (int)N, ctx->stream));
+    nr_timing_end(ctx, NRK_MESH_INST_CLIP_SCAN, a, b);
+    // n_out = the last offset + the last count (at most 2N < 2^32): the one sync point of the draw
+    NR_CHECK(hipMemcpyAsync(&h[0], off + (N - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    NR_CHECK(hipMemcpyAsync(&h[1], cnt + (N - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("mesh clip stage", "the count could not be read back");
+    const size_t nout = (size_t)h[0] + (size_t)h[1];
+    *out = Soup{nullptr, nullptr, nullptr, nullptr, (i64)nout};
+    if (nout == 0) return true;
+    if (nout > 2 * N) return fail("mesh clip stage", "inconsistent triangle count");   // (never: the counts are 0, 1 or 2)
+    const size_t stride = (size_t)nrtri::attr_stride(m->mode);
+    const size_t zn = (nout * 3 + 1) & ~(size_t)1;   // keeps the attributes 16-byte aligned
+    if (!sc.mstage.ensure(nout * 6 + zn + nout * stride + (persp ? nout * 3 : 0))) return false;
+    f64* xy = sc.mstage;
+    f64* z = xy + nout * 6;
+    f64* attr = z + zn;
+    f64* q = persp ? attr + nout * stride : nullptr;
+    const bool tint = in.tint != nullptr;
+    const auto emit = m->mode == nrtri::ATTR_GOURAUD ? (tint ? k_minst_clip_emit<2, false, true> : k_minst_clip_emit<2, false, false>)
+                      : m->mode != nrtri::ATTR_TEX   ? (tint ? k_minst_clip_emit<0, false, true> : k_minst_clip_emit<0, false, false>)
+                      : persp                        ? k_minst_clip_emit<1, true, false>
+                                                     : k_minst_clip_emit<1, false, false>;
+    nr_timing_begin(ctx, NRK_MESH_INST_CLIP_EMIT, &a, &b);
+    hipLaunchKernelGGL(emit, dim3(blocks_for((i64)N)), dim3(256), 0, ctx->stream, m->idx, n, (u32)N, nv, clip,
+                       reinterpret_cast<const double2*>(m->attr), in.tint, wNear, keep, off,
+                       reinterpret_cast<double2*>(xy), z, reinterpret_cast<double2*>(attr), q);
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_INST_CLIP_EMIT, a, b);
+    *out = Soup{xy, z, attr, q, (i64)nout};
+    return true;
+}
+
+// The soup an instanced draw rasterises under the context's clip and perspective state.
+bool instanced_soup(RenderContext* ctx, const Mesh* m, const Instances& in, Soup* out) {
+    const bool persp = persp_draw(ctx, m);
+    return clip_stage_on(ctx) ? assemble_instanced_clipped(ctx, m, in, out, persp)
+                              : assemble_instanced(ctx, m, in, out, persp);
+}
+
+// The four instanced draw entry points under the caller's name `what`.  onDevice: matrices and tint are device
+// arrays, read only by the vertex and assembly kernels launched here; the batch reads the context's staging.
+void draw_instanced(RenderContext* ctx, Mesh* m, Texture* tex, bool textured, const f64* matrices, const f64* tint,
+                    i64 K, bool onDevice, const char* what) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    ctx->meshLastCount = 0;
+    if (!check_mesh(ctx, m, textured, what)) return;
+    if (ctx->recording) nr_settle(ctx);   // recorded draws come first
+    if (textured && !nrtri::check_texture(ctx, tex, what)) return;
+    bool empty;
+    if (!check_instances(ctx, m, matrices, tint, K, true, &empty, what) || empty) return;
+    Instances in{matrices, tint, K};
+    if (!onDevice && !upload_instances(ctx, matrices, tint, K, &in)) return;
+    Soup s;
+    if (!instanced_soup(ctx, m, in, &s)) return;
+    ctx->meshLastCount = s.n;
+    if (s.n <= 0) return;   // (clipped or culled away)
+    if (textured) {
+        Batch b = soup_batch(s, nrtri::ATTR_TEX, nrtri::OPQ_UNKNOWN, nullptr, false);   // (s.q: the perspective state)
+        nrtri::draw_textured(ctx, tex, b);
+        return;
+    }
+    // opaque: an opaque mesh under no tint or tints of alpha 1 (a device tint: the batch's own device scan)
+    nrtri::Opacity opq = m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED;
+    if (tint && m->opaque) {
+        if (onDevice) opq = nrtri::OPQ_UNKNOWN;
+        else
+            for (i64 k = 0; k < K; ++k)
+                if (tint[k * 4 + 3] != 1) { opq = nrtri::OPQ_BLENDED; break; }
+    }
+    nrtri::draw(ctx, soup_batch(s, m->mode, opq, nullptr, false));
 }
 
 // Copy-out of the Assemble* entry points: the first k triangles of each part (`per` doubles a triangle; a null
@@ -745,6 +1111,54 @@ bool AssembleMeshClipped(RenderContext* ctx, Mesh* m, const f64* matrix16, i64 c
     *n_out = s.n;
     const size_t k = (size_t)(s.n < cap ? s.n : cap);
     copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {attr_out, s.attr, (size_t)nrtri::attr_stride(m->mode)}});
+    return true;
+}
+
+// New: an instanced draw (DESIGN.md §3 "Instanced mesh draws"): the colour mesh `m` under each of the K row-major
+// 4x4 `matrices` (K*16) as one batch -- the frame of DrawMesh(ctx, m, matrices + 16 k) for k = 0 .. K-1 in that
+// order, from one vertex and assembly pass and one binning.  tint (K*4: r, g, b, a) or NULL: every vertex colour
+// of instance k times tint[k], as if the mesh had been created with those colours; NULL is no product at all.
+// Host arrays, free again on return.  K == 0 draws nothing; K < 0, NULL matrices with K > 0, or more than
+// 2^31 - 1 triangles or vertices in all latch an error and draw nothing.
+void DrawMeshInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* tint, i64 K) {
+    draw_instanced(ctx, m, nullptr, false, matrices, tint, K, false, "DrawMeshInstanced");
+}
+
+// New: the same for a textured mesh sampled from `tex` (no tint).
+void DrawTexturedMeshInstanced(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrices, i64 K) {
+    draw_instanced(ctx, m, tex, true, matrices, nullptr, K, false, "DrawTexturedMeshInstanced");
+}
+
+// New: the same from device-resident matrices and tint (as DrawTrianglesDevice: valid and unchanged until the
+// draw has executed).  Only the vertex and assembly kernels launched in the call read them.
+void DrawMeshInstancedDevice(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* tint, i64 K) {
+    draw_instanced(ctx, m, nullptr, false, matrices, tint, K, true, "DrawMeshInstancedDevice");
+}
+void DrawTexturedMeshInstancedDevice(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrices, i64 K) {
+    draw_instanced(ctx, m, tex, true, matrices, nullptr, K, true, "DrawTexturedMeshInstancedDevice");
+}
+
+// New: the soup an instanced draw of `m` rasterises under the context's near plane, cull mode and perspective
+// state -- the draw's own kernels, host matrices and tint -- copied to the host: *n_out = the full count, the
+// first min(cap, *n_out) triangles in xy_out (x6), z_out (x3), attr_out (x12 Gouraud, x4 flat, x6 textured) and,
+// for a perspective textured draw only, q_out (x3; may be NULL otherwise).  A sync point; either mesh kind.
+bool AssembleMeshInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* tint, i64 K, i64 cap,
+                           f64* xy_out, f64* z_out, f64* attr_out, f64* q_out, i64* n_out) {
+    const char* what = "AssembleMeshInstanced";
+    NR_CHECK(hipSetDevice(ctx->device));
+    const bool persp = m && persp_draw(ctx, m);
+    const bool outputs = xy_out && z_out && attr_out && (q_out || !persp);
+    if (!check_assemble(ctx, m, false, cap, outputs, n_out, what)) return false;
+    bool empty;
+    if (!check_instances(ctx, m, matrices, tint, K, false, &empty, what)) return false;
+    if (empty) return true;
+    Instances in;
+    Soup s;
+    if (!upload_instances(ctx, matrices, tint, K, &in) || !instanced_soup(ctx, m, in, &s)) return false;
+    *n_out = s.n;
+    const size_t k = (size_t)(s.n < cap ? s.n : cap);
+    copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {attr_out, s.attr, (size_t)nrtri::attr_stride(m->mode)},
+                      {q_out, s.q, 3}});
     return true;
 }
 

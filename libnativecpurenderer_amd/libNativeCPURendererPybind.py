@@ -454,6 +454,87 @@ class RenderContext:
         k = nout.value
         return xy[:k].copy(), z[:k].copy(), uv[:k].copy(), q[:k].copy()
 
+    # instanced mesh draws: one mesh under K matrices as one batch -- the frame
+    # of K draw_mesh calls in instance order
+    @staticmethod
+    def _instances(mesh, matrices, texture, tint):
+        """(matrices (K, 16), tint (K, 4) or None) of an instanced call, checked."""
+        matrices = np.ascontiguousarray(matrices, dtype=np.float64).reshape(-1, 16)
+        if mesh.textured:
+            if texture is None:
+                raise ValueError("a textured Mesh is drawn with a texture")
+            if tint is not None:
+                raise ValueError("a textured Mesh takes no tint")
+        elif texture is not None:
+            raise ValueError("a colour Mesh takes no texture")
+        if tint is not None:
+            tint = np.ascontiguousarray(tint, dtype=np.float64).reshape(-1, 4)
+            if tint.shape[0] != matrices.shape[0]:
+                raise ValueError("tint must hold one (r, g, b, a) per matrix")
+        return matrices, tint
+
+    def draw_mesh_instanced(self, mesh: "Mesh", matrices, texture: typing.Optional["Texture"] = None, tint=None):
+        """Draws `mesh` under each of the K row-major 4x4 `matrices` ((K, 16)
+        or (K, 4, 4)) as ONE batch: the frame of K draw_mesh calls in instance
+        order, from one vertex / assembly pass and one binning.  tint ((K, 4),
+        colour meshes only): instance k's vertex colours times tint[k]; None:
+        the mesh's own colours.  Every state of draw_mesh applies; the arrays
+        are the caller's again on return."""
+        matrices, tint = self._instances(mesh, matrices, texture, tint)
+        k = matrices.shape[0]
+        mp = _f64_ptr(matrices) if k else None
+        if mesh.textured:
+            lib.DrawTexturedMeshInstanced(self._ptr, mesh._ptr, texture._ptr, mp, k)
+        else:
+            lib.DrawMeshInstanced(self._ptr, mesh._ptr, mp, None if tint is None else _f64_ptr(tint), k)
+
+    def draw_mesh_instanced_device(self, mesh: "Mesh", matrices, k: int,
+                                   texture: typing.Optional["Texture"] = None, tint=None):
+        """draw_mesh_instanced with matrices (k*16 f64) and tint (k*4) already
+        in HBM: device addresses or objects with .data_ptr(), as for
+        draw_triangles_device -- keep them alive and unchanged until the draw
+        has executed."""
+        def addr(a):
+            if a is None:
+                return None
+            return a.data_ptr() if hasattr(a, "data_ptr") else int(a)
+        if mesh.textured:
+            if texture is None:
+                raise ValueError("a textured Mesh is drawn with a texture")
+            if tint is not None:
+                raise ValueError("a textured Mesh takes no tint")
+            lib.DrawTexturedMeshInstancedDevice(self._ptr, mesh._ptr, texture._ptr, addr(matrices), int(k))
+        else:
+            if texture is not None:
+                raise ValueError("a colour Mesh takes no texture")
+            lib.DrawMeshInstancedDevice(self._ptr, mesh._ptr, addr(matrices), addr(tint), int(k))
+
+    def assemble_mesh_instanced(self, mesh: "Mesh", matrices, tint=None):
+        """(xy (n_out, 6), z (n_out, 3), attr (n_out, 12 | 4 | 6), q (n_out, 3)
+        or None): the soup draw_mesh_instanced would rasterise under this
+        context's near plane, cull mode and perspective state -- the draw's own
+        kernels (a sync point).  q only for a perspective textured draw."""
+        matrices = np.ascontiguousarray(matrices, dtype=np.float64).reshape(-1, 16)
+        if tint is not None:
+            tint = np.ascontiguousarray(tint, dtype=np.float64).reshape(-1, 4)
+            if tint.shape[0] != matrices.shape[0]:
+                raise ValueError("tint must hold one (r, g, b, a) per matrix")
+        k = matrices.shape[0]
+        cap = 2 * k * mesh.triangle_count
+        stride = 6 if mesh.textured else (12 if mesh.gouraud else 4)
+        persp = mesh.textured and self.mesh_perspective()
+        xy = np.empty((cap, 6), dtype=np.float64)
+        z = np.empty((cap, 3), dtype=np.float64)
+        attr = np.empty((cap, stride), dtype=np.float64)
+        q = np.empty((cap, 3), dtype=np.float64) if persp else None
+        nout = ctypes.c_long(0)
+        if not lib.AssembleMeshInstanced(self._ptr, mesh._ptr, _f64_ptr(matrices) if k else None,
+                                         None if tint is None else _f64_ptr(tint), k, cap, _f64_ptr(xy), _f64_ptr(z),
+                                         _f64_ptr(attr), None if q is None else _f64_ptr(q), ctypes.byref(nout)):
+            raise RuntimeError("AssembleMeshInstanced failed: " + _lib.last_error())
+        no = nout.value
+        return xy[:no].copy(), z[:no].copy(), attr[:no].copy(), (None if q is None else q[:no].copy())
+
     # ---- additions: sync, device interop, measurement ------------------
     def flush(self):
         lib.Flush(self._ptr)
