@@ -280,6 +280,14 @@ i64 GetReplannedBatchCount(RenderContext* ctx);                          /* NEW 
 bool GetVisiblePlanTotals(RenderContext* ctx, i64* out4);                /* NEW (testing): the visible plan's kept pairs, work
                                                                             items, split-tile slices, dense tiles; false:
                                                                             none.  Waits for the device */
+void SetKeyCache(RenderContext* ctx, i64 mode);                          /* NEW: an unchanged repeat draw shaded from its cached
+                                                                            visibility keys, 0 auto (on), 2 off (the visible
+                                                                            list; the cached keys are kept) */
+i64 GetKeyCachedBatchCount(RenderContext* ctx);                          /* NEW (testing): of the pruned batches, shaded from
+                                                                            the key cache (no raster) */
+bool GetKeyCacheTotals(RenderContext* ctx, i64* out3);                   /* NEW (testing): the key cache's cached tiles, key
+                                                                            items, bytes of keys; false: none.  Waits for
+                                                                            the device */
 bool GetScheduleTotals(RenderContext* ctx, i64* out4);                   /* NEW (testing): the warm schedule's pairs, work
                                                                             items, split-tile slices, dense tiles; false: none */
 void SetWarmFaultInjection(RenderContext* ctx, i64 mode);                /* NEW (testing): fault in the next warm batch

@@ -124,6 +124,9 @@ DEVICE_ABI = {
     "SetVisibleReplan": (None, (P, L)),
     "GetReplannedBatchCount": (L, (P,)),
     "GetVisiblePlanTotals": (B, (P, P)),
+    "SetKeyCache": (None, (P, L)),
+    "GetKeyCachedBatchCount": (L, (P,)),
+    "GetKeyCacheTotals": (B, (P, P)),
     "GetScheduleTotals": (B, (P, P)),
     "ExecuteCommands": (L, (P, P, L, P, L)),
     "SetWarmFaultInjection": (None, (P, L)),

@@ -230,10 +230,31 @@ struct TriScratch {
         int replanState = 0;                             // 0 none, 1 enqueued, 2 its totals seen by the host
         BatchTotals vtotals;                             // (state 2) pairs, items, split slices, dense tiles
         u32 splitAt = 0, dslice = 0;                     // the split limits the schedule was planned under (0: defaults)
-        void drop_visible() { visState = 0; replanState = 0; }
+        // key cache: the final keys (zq << 32) | id of every owned tile with a kept
+        // pair, as one capture frame's k_vis left them in LDS right before it shaded
+        // -- a function of the buffer, the binning key and the initial depth only,
+        // so later batches of the capturing mode over the same initial depth shade
+        // from them (k_keys) and rasterise nothing
+        DevArray<u64> kkeys;                             // TH*TW keys per cached tile, slot = the tile's item index
+        DevArray<uint4> kitems;                          // an item per owned tile {tile, slot, kept pairs, 0}: cached first
+        DevArray<u32> ktile;                             // the capture frame's table (KeyCaptureTable): kkeys' address, then
+                                                         // per tile its slot, or ~0 (not cached)
+        u32* kplan = nullptr;                            // device totals {cached tiles, items}
+        u64* h_kplan = nullptr;                          // pinned, device-mapped host copy, (seq << 32) | value
+        u64* d_hkplan = nullptr;                         // its device address
+        u32 kplanSeq = 0;                                // sequence number of the last key plan
+        int keyState = 0;                                // 0 none, 1 item list enqueued, 2 totals seen and slots allocated,
+                                                         // 3 capture frame enqueued, 4 cached, -1 no memory (this generation)
+        u32 ktiles = 0, knitems = 0;                     // (state >= 2) cached tiles, items
+        hipEvent_t evKey = nullptr;                      // the capture frame is done (main stream)
+        void drop_visible() { visState = 0; replanState = 0; keyState = 0; }
         void release() {
             off.release(); items.release(); off2.release();
             vlist.release(); vcnt.release(); vmask.release(); vitems.release();
+            kkeys.release(); kitems.release(); ktile.release();
+            if (kplan) NR_CHECK(hipFree(kplan));
+            if (h_kplan) NR_CHECK(hipHostFree(h_kplan));
+            if (evKey) NR_CHECK(hipEventDestroy(evKey));
             if (vplan) NR_CHECK(hipFree(vplan));
             if (h_vplan) NR_CHECK(hipHostFree(h_vplan));
             if (evMark) NR_CHECK(hipEventDestroy(evMark));
@@ -251,6 +272,8 @@ struct TriScratch {
     int pruneMode = 0;                      // visible list: 0 automatic (on), 2 off (SetVisiblePruning)
     u64 replannedBatches = 0;               // of the pruned ones, rasterised under the visible plan (GetReplannedBatchCount)
     int replanMode = 0;                     // visible plan: 0 automatic (on), 2 off (SetVisibleReplan)
+    u64 keyCachedBatches = 0;               // of the pruned ones, shaded from the key cache (GetKeyCachedBatchCount)
+    int keyMode = 0;                        // key cache: 0 automatic (on), 2 off (SetKeyCache)
     std::vector<u64> looseBanned;           // buffers whose loose binning overflowed a tile: not binned loose again
     // warm-batch checks (k_vis WarmCheck): host-mapped word a raster sets when
     // a warm batch failed them (1 binning check, 2 token timeout), read by

@@ -373,6 +373,13 @@ __device__ __forceinline__ bool row_span32(const Span32& S, int r, f64 y, float 
     return ok;
 }
 
+// The key cache's capture table, in device memory (nr_tri_free.hip, capture_keys): the address of the slots (TH * TW
+// keys each) and every tile's slot, ~0 for a tile that is not cached (no kept pair, or another rank's).
+struct KeyCaptureTable {
+    u64* keys;
+    u32 slot[2];   // (one per tile: the table is allocated to the frame's tiles)
+};
+
 // State snapshot of one draw call (passed by value to the kernels).
 struct FrameParams {
     TriSrc src;
@@ -399,7 +406,10 @@ struct FrameParams {
     u64* tstamp;      // non-null (kernel timing): {~first start, last end} of the raster on the device's
                       // 100 MHz clock (raster_stamp_begin / _end, nr_timing_stamp)
     TexView tex;      // textured batches: the texture (a snapshot when it aliases fb)
-    u32* winMask;     // a marking frame (k_vis MARK instances only): bit t is set when triangle t wins a pixel
+    union {           // (one place in the snapshot: a batch is never both, and the other instances read neither)
+        u32* winMask;                  // a marking frame (k_vis MARK instances only): bit t is set when triangle t wins a pixel
+        const KeyCaptureTable* kcap;   // the key cache's capture frame (k_vis KCAP instances only): where its keys go
+    };
     // perspective batches (attr_persp): each corner's 1/w, n*3 laid out like src.z (else null).  Only the shading reads it,
     // so it lives here and not in TriSrc, and last: the binning's BinParams and every offset of the snapshot
     // the existing instances read stay as they were.
@@ -638,6 +648,7 @@ void draw_free(RenderContext* ctx, const Batch& b, bool ordered);
 void settle(RenderContext* ctx);
 i64 visible_pairs(RenderContext* ctx);   // pairs kept in the schedule's visible list (0: none)
 bool visible_plan_totals(RenderContext* ctx, i64* out4);   // the visible plan's pairs, items, split slices, dense tiles
+bool key_cache_totals(RenderContext* ctx, i64* out3);      // the key cache's cached tiles, key items, bytes of keys
 
 // the batch entry points behind every triangle draw call (nr_tri.hip), shared with the mesh front end
 // (nr_mesh.hip): draw picks the raster; draw_textured first completes the batch from the texture (its view, the

@@ -556,6 +556,20 @@ bool GetVisiblePlanTotals(RenderContext* ctx, i64* out) {
     NR_CHECK(hipSetDevice(ctx->device));
     return nrtri::visible_plan_totals(ctx, out);
 }
+// New (testing / A-B measurement): the key cache -- an unchanged draw shaded
+// from the final visibility keys one capture frame stored, no raster -- 0
+// automatic (on), 2 off (such draws run from the visible list; the cached keys
+// are kept and used again after a switch back to 0).
+void SetKeyCache(RenderContext* ctx, i64 mode) { ctx->tri.keyMode = mode == 2 ? 2 : 0; }
+// New (testing): of the pruned batches, those shaded from the key cache.
+i64 GetKeyCachedBatchCount(RenderContext* ctx) { return (i64)ctx->tri.keyCachedBatches; }
+// New (testing): totals of the current key cache -- out[0..2] = cached tiles,
+// key items (one per owned tile), bytes of cached keys; false (and zeros) when
+// there is none.  Waits for the device.
+bool GetKeyCacheTotals(RenderContext* ctx, i64* out) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    return nrtri::key_cache_totals(ctx, out);
+}
 // New (testing): totals of the context's warm schedule -- out[0..3] = (tile,
 // triangle) pairs, k_vis work items, slices of split tiles, dense tiles;
 // false (and zeros) when it has none.

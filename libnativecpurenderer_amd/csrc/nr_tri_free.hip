@@ -27,6 +27,9 @@
 //                    dense tiles, e.g. mesh poles) merges its keys into `vis`
 //                    with global atomics and the last slice to finish shades
 //                    it and resets those keys.
+//   5 k_keys         an unchanged repeat draw only (key cache): each tile's
+//                    final keys, stored by one capture frame's k_vis, are loaded
+//                    back into LDS and the tile is shaded as in 4 -- no raster.
 #include "nr_tri.h"
 #include "nr_tri_shade.h"
 
@@ -1206,8 +1209,25 @@ __device__ __forceinline__ void warm_report(const WarmCheck& wc, u32 why, u32 a,
     __hip_atomic_store(&wc.hfail[0], why, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// The key cache's capture frame (KCAP instances; warm_enqueue): right before a
+// workgroup shades a tile it copies the tile's final LDS keys to the tile's slot
+// (tile-contiguous, rows unpadded: a wave's store is 512 contiguous bytes).
+// The slots' address and the tiles' slots come from the capture table in device
+// memory (fp.kcap, nr_tri.h): k_vis's arguments, and so every other instance's
+// code, stay as they were.
+template <int NT>
+__device__ __forceinline__ void capture_keys(const KeyCaptureTable* kc, int tile, const u64* key) {
+    const u32 slot = kc->slot[tile];
+    if (slot == ~0u) return;
+    u64* const dst = kc->keys + (size_t)slot * (TH * TW);
+    const int tid = opaque_tid();
+    for (int p = tid; p < TH * TW; p += NT)   // (every key: pixels past the frame edge are never shaded)
+        dst[p] = key[(p / TW) * KS + (p & (TW - 1))];
+}
+
 // MARK: a marking frame's instance (shade_tile MARK; the visible list, warm_enqueue).
-template <int ZMODE, bool COUNT, int MODE, bool FLAT, int NT, bool MARK = false>   // ZMODE 0: no test, 1: LESS+write, 2: LESS no write
+// KCAP: the key cache's capture frame (capture_keys at the two shade_tile calls).
+template <int ZMODE, bool COUNT, int MODE, bool FLAT, int NT, bool MARK = false, bool KCAP = false>   // ZMODE 0: no test, 1: LESS+write, 2: LESS no write
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) void k_vis(const FrameParams fp, const uint4* __restrict__ items,
                                              const u32* __restrict__ list,
                                              u64* __restrict__ kslot, u32* __restrict__ done,
@@ -1554,6 +1574,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         __syncthreads();
         NR_PROBE_STAMP(2);
         if (!multi) {   // the whole list was in this slice: shade now
+            if constexpr (KCAP) capture_keys<NT>(fp.kcap, tile, key);
             if (rlo < rcap)
                 shade_tile<ZMODE, MODE, NT, HS, MARK>(fp, x0, y0 + rlo, wlim, rcap - rlo, key + rlo * KS, lds, nU);
             continue;
@@ -1624,6 +1645,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         }
         __syncthreads();
         NR_PROBE_STAMP(3);
+        if constexpr (KCAP) capture_keys<NT>(fp.kcap, tile, key);
         shade_tile<ZMODE, MODE, NT, HS, MARK>(fp, x0, y0, wlim, hlim, key, lds, nU);
     }   // work items
 #if NR_PROBE
@@ -1638,6 +1660,144 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         atomicAdd(&sFrag, myFrags);
         __syncthreads();
         if (tid == 0) atomicAdd(fp.fragCounter, sFrag);
+    }
+}
+
+// ---- key cache: the steady kernel ---------------------------------------------
+// An unchanged draw's final keys are the same every frame (same buffer, same
+// binning key, same initial depth: the conditions of a marking frame), so once
+// a capture frame has stored them (k_vis KCAP) a batch needs none of k_vis's key
+// pass -- no key set-up, no list or vertex loads, no f64 triangle set-up, no LDS
+// atomics.  One workgroup per owned tile (grid-strided over the key items,
+// k_key_plan): an empty item takes k_vis's empty-tile path; a cached one loads
+// its 2048 keys (every load of a thread in flight together, a wave's load 512
+// contiguous bytes), stores them to the LDS keys at stride KS and shades the
+// tile with shade_tile unchanged -- everything colour-side is read live from fp.
+// kplan: {cached tiles, items}.
+template <int ZMODE, int MODE, int NT>
+__global__ __launch_bounds__(NT) void k_keys(const FrameParams fp, const uint4* __restrict__ items,
+                                             const u64* __restrict__ kkeys, const u32* __restrict__ kplan) {
+    constexpr int HS = NT > VWG ? HTS_WIDE : HTS;
+    constexpr int PPT = TH * TW / NT;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[ShadeStage<MODE, HS>::BYTES];
+    u64* const key = reinterpret_cast<u64*>(lds + ShadeStage<MODE, HS>::KEY_OFF);
+    __shared__ u32 nU;
+    raster_stamp_begin(fp);
+    const u32 nitems = kplan[1];
+    uint4 dnext = blockIdx.x < nitems ? items[blockIdx.x] : make_uint4(0, 0, 0, 0);
+#if NR_PROBE
+    const int tid = threadIdx.x;
+    u64 pr_t0 = 0;
+    u32 pr_item = ~0u;
+    uint4 pr_d = make_uint4(0, 0, 0, 0);
+#endif
+    for (u32 item = blockIdx.x; item < nitems; item += gridDim.x) {
+        const uint4 d = dnext;
+        if (item + gridDim.x < nitems) dnext = items[item + gridDim.x];
+#if NR_PROBE
+        if (tid == 0) {   // (the record's list range: [0, kept pairs))
+            const u64 now = __builtin_amdgcn_s_memrealtime();
+            if (pr_item != ~0u) probe_item(pr_item, pr_d, pr_t0, now, NT);
+            pr_t0 = now; pr_item = item; pr_d = make_uint4(d.x, 0u, d.z, 1u);
+        }
+#endif
+        __syncthreads();   // (the last item's records lie over the keys)
+        const int itid = opaque_tid();
+        const int tile = (int)d.x;
+        const int tx = tile % fp.tiles_x, ty = tile / fp.tiles_x;
+        const i64 x0 = (i64)tx * TW, y0 = (i64)ty * TH;
+        const int wlim = (int)(fp.W - x0 < TW ? fp.W - x0 : TW);
+        const int hlim = (int)(fp.H - y0 < TH ? fp.H - y0 : TH);
+        if (d.y == ~0u) {   // no kept pair: only the pending clears (as k_vis)
+            if (fp.tileStamp) {
+                if (fp.frameU8 && fp.pendColor) {
+                    const f64 v = fp.pendColorValue;
+                    for (int p = itid; p < TH * TW; p += NT) {
+                        const int lx = p & (TW - 1), ly = p / TW;
+                        if (lx < wlim && ly < hlim)
+                            store_frame_out(fp, (y0 + ly) * fp.W + x0 + lx, x0 + lx, y0 + ly, v, v, v, v);
+                    }
+                }
+                if (itid == 0) fp.tileStamp[tile] = fp.tileEpoch;
+                continue;
+            }
+            for (int p = itid; p < TH * TW; p += NT) {
+                const int lx = p & (TW - 1), ly = p / TW;
+                if (lx < wlim && ly < hlim)
+                    store_clear<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, x0 + lx, y0 + ly);
+            }
+            continue;
+        }
+        const u64* const src = kkeys + (size_t)d.y * (TH * TW);
+        u64 kv[PPT];
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) kv[k] = src[itid + k * NT];
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) {
+            const int p = itid + k * NT;
+            key[(p / TW) * KS + (p & (TW - 1))] = kv[k];
+        }
+        __syncthreads();
+        NR_PROBE_STAMP(1);
+        NR_PROBE_STAMP(2);
+        shade_tile<ZMODE, MODE, NT, HS>(fp, x0, y0, wlim, hlim, key, lds, nU);
+    }
+#if NR_PROBE
+    if (tid == 0 && pr_item != ~0u) probe_item(pr_item, pr_d, pr_t0, __builtin_amdgcn_s_memrealtime(), NT);
+#endif
+    raster_stamp_end(fp);
+}
+
+// The key items of a pruned list (one workgroup, once per pruning, main stream
+// right after k_prune_list): one item per owned tile {tile, slot, kept pairs, 0}
+// -- the tiles with a kept pair first, densest first by KEY_NB equal bins of
+// [1, the largest kept count], each one's slot its item index; then the owned
+// tiles without one (slot ~0) -- no slices, whatever the split limits.
+// ktile[t]: tile t's slot, ~0 when it has none (the capture frame's table).
+// totals / host_totals (seq-tagged words, as the plan kernels'): {cached tiles, items}.
+constexpr int KEY_NB = 16;
+__global__ __launch_bounds__(PLAN_T) void k_key_plan(const u32* __restrict__ vcnt, int ntiles, int tiles_x, int period,
+                                                     u64 mask, uint4* __restrict__ items, u32* __restrict__ ktile,
+                                                     u32* __restrict__ totals, u64* __restrict__ host_totals, u32 seq) {
+    __shared__ u32 bcnt[KEY_NB + 1], bcur[KEY_NB + 1];   // [0]: the empty owned tiles
+    __shared__ u32 smx;
+    const int tid = threadIdx.x;
+    if (tid <= KEY_NB) bcnt[tid] = 0;
+    if (tid == 0) smx = 0;
+    __syncthreads();
+    u32 mx = 0;
+    for (int i = tid; i < ntiles; i += PLAN_T)
+        if (owned_row(i / tiles_x, period, mask)) mx = max(mx, vcnt[i]);
+    if (mx) atomicMax(&smx, mx);
+    __syncthreads();
+    const u32 top = smx;
+    auto cls = [&](u32 c) -> int {
+        return c == 0 ? 0 : 1 + min((int)((float)c * ((float)KEY_NB / (float)(top + 1))), KEY_NB - 1);
+    };
+    for (int i = tid; i < ntiles; i += PLAN_T)
+        if (owned_row(i / tiles_x, period, mask)) atomicAdd(&bcnt[cls(vcnt[i])], 1u);
+    __syncthreads();
+    if (tid == 0) {   // densest class first, the empty tiles last
+        u32 base = 0;
+        for (int k = KEY_NB; k >= 0; --k) { bcur[k] = base; base += bcnt[k]; }
+    }
+    __syncthreads();
+    for (int i = tid; i < ntiles; i += PLAN_T) {
+        u32 slot = ~0u;
+        if (owned_row(i / tiles_x, period, mask)) {
+            const u32 c = vcnt[i];
+            const u32 e = atomicAdd(&bcur[cls(c)], 1u);
+            if (c) slot = e;
+            items[e] = make_uint4((u32)i, slot, c, 0u);
+        }
+        ktile[i] = slot;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const u32 nit = bcur[0], nc = nit - bcnt[0];   // (bcur[0] has run to the end of the items)
+        totals[0] = nc; totals[1] = nit;
+        __hip_atomic_store(&host_totals[0], ((u64)seq << 32) | nc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&host_totals[1], ((u64)seq << 32) | nit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -1663,6 +1823,12 @@ struct VisArgs {
     const u32* list;
     const u32* plan;
     WarmCheck wc;   // (a warm batch's checks; zero: a cold batch)
+    // key cache (warm_enqueue): capture, the batch is the capture frame (its snapshot's kcap is set); kkeys
+    // non-null, it is shaded from the cache by k_keys (kitems, kplan) and reads nothing of the above
+    bool capture = false;
+    const u64* kkeys = nullptr;
+    const uint4* kitems = nullptr;
+    const u32* kplan = nullptr;
 };
 
 // The instance of a batch among its four shapes -- wide workgroups (never a counting batch) or not, the flattened
@@ -1671,6 +1837,15 @@ template <int Z, bool C, int G, bool MARK>
 auto vis_kernel(bool wide, bool coop) {
     if (wide) return coop ? k_vis<Z, false, G, true, 2 * VWG, MARK> : k_vis<Z, false, G, false, 2 * VWG, MARK>;
     return coop ? k_vis<Z, C, G, true, VWG, MARK> : k_vis<Z, C, G, false, VWG, MARK>;
+}
+
+// NR_KEYS_WIDE=1 (tests, A/B): every batch shaded from the key cache runs k_keys' 512-thread instance.
+static bool keys_wide_forced() {
+    static const bool v = [] {
+        const char* e = getenv("NR_KEYS_WIDE");
+        return e && atoi(e) == 1;
+    }();
+    return v;
 }
 
 // t: the totals that pick the variant -- this batch's when they are known (a
@@ -1687,11 +1862,26 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& 
     auto kernel = vis_kernel<Z, C, G, false>(wide, coop);
     // a marking frame (fp.winMask; never a counting batch, never LESS without write -- and only a repeat
     // TriangleBuffer draw marks, which has no q: the filtered perspective mode has no marking instance)
+    // The key cache's batches are those of a pruned list, so they too exist only where a marking frame does.  A
+    // cached batch runs k_keys at the workgroup size k_vis would take; the capture frame (one per generation) the
+    // narrow capturing instance of its raster shape.
+    bool narrow = false;
     if constexpr (!C && Z != 2 && G != ATTR_TEX_PERSP_BIL) {
-        if (fp.winMask) kernel = vis_kernel<Z, false, G, true>(wide, coop);
+        if (va.kkeys) {
+            const bool w = wide || keys_wide_forced();
+            hipExtLaunchKernelGGL(w ? k_keys<Z, G, 2 * VWG> : k_keys<Z, G, VWG>, dim3(grid), dim3(w ? 2 * VWG : VWG), 0, s,
+                                  start, stop, 0, fp, va.kitems, va.kkeys, va.kplan);
+            return;
+        }
+        if (va.capture) {   // (fp.kcap shares fp.winMask's place: asked first)
+            kernel = coop ? k_vis<Z, false, G, true, VWG, false, true> : k_vis<Z, false, G, false, VWG, false, true>;
+            narrow = true;
+        } else if (fp.winMask) {
+            kernel = vis_kernel<Z, false, G, true>(wide, coop);
+        }
     }
-    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(wide ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.items, va.list,
-                          sc.kslot.p, sc.fdone.p, va.plan, va.wc);
+    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(wide && !narrow ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.items,
+                          va.list, sc.kslot.p, sc.fdone.p, va.plan, va.wc);
 }
 
 // k_vis' ZMODE of a batch: 0 no test, 1 LESS + write, 2 LESS without write
@@ -2545,6 +2735,7 @@ static void visible_prune(RenderContext* ctx, int ntiles) {
     NR_CHECK(hipGetLastError());
     S.visState = 2;
     S.replanState = 0;
+    S.keyState = 0;
 }
 
 // Visible split limits under test (A/B measurement): NR_VIS_SPLIT_AT /
@@ -2595,6 +2786,109 @@ static bool vplan_seen(TriScratch::Schedule& S) {
     S.vtotals = BatchTotals{S.totals.n, v[PW_PAIRS], v[PW_ITEMS], v[PW_SPLIT], v[PW_HEAVY]};
     S.replanState = 2;
     return true;
+}
+
+// ---- key cache: host side -------------------------------------------------------
+// The fourth stage of a schedule generation, after "pruned" (and "re-planned"):
+//   1 the key items, planned on the device from the kept counts (k_key_plan), in
+//     stream order after k_prune_list, on the first batch of the pruned list;
+//   2 once the host has seen their totals (no wait), compact slots for the tiles
+//     with a kept pair (TH * TW keys each; no memory: the generation stays on the
+//     visible list);
+//   3 one batch of the pruned list whose draw could also have marked
+//     (visible_capture_ok) is the capture frame: an exact frame like any other
+//     whose k_vis also stores every shaded tile's final keys;
+//   4 once the host has seen that frame complete (an event query, never a wait)
+//     and no check failed, such draws are shaded from the cache (k_keys).
+// Exact, because the keys are k_vis's own, taken where shade_tile reads them,
+// and depend on the buffer (immutable), the binning key (the generation's) and
+// the initial depth only: none for the no-test mode (the highest covering id),
+// a pending clear to 0xFFFFFFFF for LESS + write -- the one the capture frame had.
+// Dropped with the visible list (Schedule::drop_visible).
+static bool key_totals_seen(const TriScratch::Schedule& S, u32* tiles, u32* items) {
+    const u64 a = __atomic_load_n(&S.h_kplan[0], __ATOMIC_ACQUIRE), b = __atomic_load_n(&S.h_kplan[1], __ATOMIC_ACQUIRE);
+    if ((u32)(a >> 32) != S.kplanSeq || (u32)(b >> 32) != S.kplanSeq) return false;
+    *tiles = (u32)a; *items = (u32)b;
+    return true;
+}
+
+static void key_plan(RenderContext* ctx, const FrameParams& fp, int ntiles) {
+    auto& S = ctx->tri.sched;
+    const size_t tn = std::max<size_t>((size_t)ntiles, 1);
+    // (the capture table: the slots' address in the first two words, then a slot per tile -- KeyCaptureTable)
+    if (S.kitems.needs(tn) || S.ktile.needs(tn + 2) || !S.kplan || !S.h_kplan) {
+        NR_CHECK(hipStreamSynchronize(ctx->stream));   // (a queued batch of an earlier generation may still read them)
+        if (!S.kitems.ensure(tn) || !S.ktile.ensure(tn + 2)) { S.keyState = -1; return; }
+        if (!S.kplan) NR_CHECK(hipMalloc(&S.kplan, 2 * sizeof(u32)));
+        if (!S.h_kplan) {
+            NR_CHECK(hipHostMalloc((void**)&S.h_kplan, 8 * sizeof(u64), hipHostMallocMapped | hipHostMallocCoherent));
+            if (S.h_kplan) {
+                for (int k = 0; k < 8; ++k) S.h_kplan[k] = 0;
+                NR_CHECK(hipHostGetDevicePointer((void**)&S.d_hkplan, S.h_kplan, 0));
+            }
+        }
+        if (!S.kplan || !S.h_kplan || !S.d_hkplan) { S.keyState = -1; return; }
+    }
+    if (++S.kplanSeq == 0) S.kplanSeq = 1;   // (the host words start at 0)
+    hipLaunchKernelGGL(k_key_plan, dim3(1), dim3(PLAN_T), 0, ctx->stream, (const u32*)S.vcnt, ntiles, fp.tiles_x, fp.period,
+                       fp.mask, S.kitems.p, S.ktile.p + 2, S.kplan, S.d_hkplan, S.kplanSeq);
+    NR_CHECK(hipGetLastError());
+    S.keyState = 1;
+}
+
+// One step of the stages above for a batch of the pruned list in depth mode zm;
+// fills in va's key-cache fields.  Returns 1 when the batch is the capture frame
+// (the caller records S.evKey after it), 2 when it is shaded from the cache.
+static int key_cache_step(RenderContext* ctx, const FrameParams& fp, int zm, int ntiles, VisArgs& va) {
+    TriScratch& sc = ctx->tri;
+    auto& S = sc.sched;
+    if (sc.keyMode == 2 || S.keyState < 0) return 0;
+    if (S.keyState == 0) {
+        key_plan(ctx, fp, ntiles);
+        return 0;
+    }
+    if (S.keyState == 1) {
+        if (!key_totals_seen(S, &S.ktiles, &S.knitems)) return 0;
+        const size_t need = std::max<size_t>(S.ktiles, 1) * (size_t)(TH * TW);
+        if (S.kkeys.needs(need)) {
+            NR_CHECK(hipStreamSynchronize(ctx->stream));   // (as key_plan)
+            S.kkeys.release();
+            if (hipMalloc((void**)&S.kkeys.p, need * sizeof(u64)) != hipSuccess) {
+                (void)hipGetLastError();   // no room: not an error, the generation stays on the visible list
+                S.kkeys.p = nullptr;
+                S.keyState = -1;
+                return 0;
+            }
+            S.kkeys.cap = need;
+        }
+        // the slots' address into the capture table, in stream order before the capture frame (an 8-byte copy
+        // from pageable memory is staged before the call returns)
+        NR_CHECK(hipMemcpyAsync(S.ktile.p, &S.kkeys.p, sizeof(u64*), hipMemcpyHostToDevice, ctx->stream));
+        S.keyState = 2;
+    }
+    if (S.keyState == 3) {
+        const hipError_t q = hipEventQuery(S.evKey);
+        if (q == hipErrorNotReady) {
+            (void)hipGetLastError();   // an answer, not a failure
+            return 0;
+        }
+        if (q != hipSuccess) {
+            NR_CHECK(q);
+            S.keyState = -1;
+            return 0;
+        }
+        if (sc.hfail && __atomic_load_n(sc.hfail, __ATOMIC_ACQUIRE)) return 0;   // (warm_poll drops the schedule)
+        S.keyState = 4;
+    }
+    if (!visible_capture_ok(fp, zm)) return 0;
+    if (S.keyState == 2) {
+        va.capture = true;
+        return 1;
+    }
+    va.kkeys = S.kkeys;
+    va.kitems = S.kitems;
+    va.kplan = S.kplan;
+    return 2;
 }
 
 // loose: the batch's transform differs from the schedule's (loose_matches):
@@ -2667,10 +2961,23 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
                     ++sc.replannedBatches;
                 }
             }
-            vis_tail(ctx, F, fp, va, grid);
+            // The key cache (above), unless SetKeyCache(2): a cached batch is
+            // launched like the pruned batch it replaces (vis_tail: the set's
+            // event, the raster's timing slot), with a workgroup per key item.
+            const int kstep = key_cache_step(ctx, fp, zm, ntiles, va);
+            if (kstep == 2) grid = std::min<u32>(std::max<u32>(S.knitems, 1), 8192);
+            FrameParams fpk = fp;
+            if (kstep == 1) fpk.kcap = reinterpret_cast<const KeyCaptureTable*>(S.ktile.p);
+            vis_tail(ctx, F, fpk, va, grid);
+            if (kstep == 1) {   // the capture frame: its end, for key_cache_step
+                if (!S.evKey) S.evKey = sync_event();
+                NR_CHECK(hipEventRecord(S.evKey, sa));
+                S.keyState = 3;
+            }
             sc.last = T;
             ++sc.reusedBatches;
             ++sc.prunedBatches;
+            if (kstep == 2) ++sc.keyCachedBatches;
             return true;
         }
         FrameParams fpm = fp;
@@ -2983,6 +3290,20 @@ bool visible_plan_totals(RenderContext* ctx, i64* out) {
     NR_CHECK(hipStreamSynchronize(ctx->stream));
     if (!vplan_seen(S)) return false;
     out[0] = S.vtotals.pairs; out[1] = S.vtotals.items; out[2] = S.vtotals.split; out[3] = S.vtotals.heavy;
+    return true;
+}
+
+// Totals of the context's key cache -- cached tiles, key items, bytes of the
+// cached keys -- false when its items have not been planned (waits for the main
+// stream).
+bool key_cache_totals(RenderContext* ctx, i64* out) {
+    auto& S = ctx->tri.sched;
+    out[0] = out[1] = out[2] = 0;
+    if (!S.valid || S.visState != 2 || S.keyState < 1) return false;
+    NR_CHECK(hipStreamSynchronize(ctx->stream));
+    u32 tiles = 0, items = 0;
+    if (!key_totals_seen(S, &tiles, &items)) return false;
+    out[0] = tiles; out[1] = items; out[2] = (i64)tiles * (TH * TW) * (i64)sizeof(u64);
     return true;
 }
 

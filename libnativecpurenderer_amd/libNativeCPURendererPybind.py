@@ -750,6 +750,25 @@ class RenderContext:
             return None
         return {"pairs": out[0], "items": out[1], "split": out[2], "heavy": out[3]}
 
+    def set_key_cache(self, mode: int):
+        """The key cache -- an unchanged repeat draw shaded from the final
+        visibility keys one capture frame stored: 0 automatic (on), 2 off
+        (such draws run from the visible list; the cached keys are kept)."""
+        lib.SetKeyCache(self._ptr, int(mode))
+
+    def key_cached_batch_count(self) -> int:
+        """Of the pruned batches, those shaded from the key cache."""
+        return lib.GetKeyCachedBatchCount(self._ptr)
+
+    def key_cache_totals(self) -> typing.Optional[dict]:
+        """Testing: totals of the current key cache -- cached tiles, key items
+        (one per owned tile), bytes of cached keys -- or None when there is
+        none.  Waits for the device."""
+        out = (ctypes.c_long * 3)()
+        if not lib.GetKeyCacheTotals(self._ptr, out):
+            return None
+        return {"tiles": out[0], "items": out[1], "bytes": out[2]}
+
     def schedule_totals(self) -> typing.Optional[dict]:
         """Testing: totals of the context's warm schedule -- (tile, triangle)
         pairs, k_vis work items, slices of split tiles, dense tiles -- or None
