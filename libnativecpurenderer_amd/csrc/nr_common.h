@@ -86,7 +86,49 @@ inline bool DevArray<T>::ensure(size_t n, bool* grew) {
     return nr_ensure_together(one, n, grew);
 }
 
-// Totals of one binned triangle batch (the plan kernel's, nr_tri_free.hip).
+// Tagged host words: 8 pinned, coherent, device-mapped u64 words (one 64-byte
+// line) in which a plan kernel leaves its totals for the host, word k =
+// (seq << 32) | value.  The device stores each word on its own (8-byte stores
+// are single-copy atomic), so a set of totals is complete once every word
+// carries the sequence number the host expects.  The words start at 0, so 0 is
+// never a sequence number.
+struct SeqWords {
+    u64* h = nullptr;   // host address (null: not allocated)
+    u64* d = nullptr;   // its device address
+    u32 seq = 0;        // the number the host expects: its own (next), or one handed in (expect)
+    // allocated and zeroed on first use; false: no memory (the error is latched)
+    bool ensure() {
+        if (!h) {
+            NR_CHECK(hipHostMalloc((void**)&h, 8 * sizeof(u64), hipHostMallocMapped | hipHostMallocCoherent));
+            if (!h) return false;
+            for (int k = 0; k < 8; ++k) h[k] = 0;
+        }
+        if (!d) NR_CHECK(hipHostGetDevicePointer((void**)&d, h, 0));
+        return d != nullptr;
+    }
+    u64* dev() const { return d; }
+    u32 next() {
+        if (++seq == 0) seq = 1;
+        return seq;
+    }
+    void expect(u32 s) { seq = s; }   // (a numbering kept outside: TriScratch::planSeq, shared by the binning sets)
+    // the low halves of the first n words; true only if every one carries seq (out is whole only then)
+    bool read(u32* out, int n) const {
+        if (!h) return false;
+        for (int k = 0; k < n; ++k) {
+            const u64 x = __atomic_load_n(&h[k], __ATOMIC_ACQUIRE);
+            if ((u32)(x >> 32) != seq) return false;
+            out[k] = (u32)x;
+        }
+        return true;
+    }
+    void release() {
+        if (h) NR_CHECK(hipHostFree(h));
+        h = d = nullptr;
+    }
+};
+
+// Totals of one binned triangle batch (the plan kernel's, nr_free_bin.hip).
 struct BatchTotals {
     u64 n = 0;       // triangles (0: no batch yet)
     u32 pairs = 0;   // (tile, triangle) pairs
@@ -120,8 +162,7 @@ struct TriScratch {
         DevArray<f64> frec;                 // ordered batches: per-triangle setup records (ORec doubles each)
         DevArray<u32> flist;
         u32* dplan = nullptr;
-        u64* h_plan = nullptr;              // pinned, device-mapped copy of the plan totals, (seq << 32) | value
-        u64* d_hplan = nullptr;             // its device address
+        SeqWords hplan;                     // host copy of the plan totals (PW_COUNT words), numbered by planSeq
         hipEvent_t evBin = nullptr;         // binning done (binning stream)
         hipEvent_t evVis = nullptr;         // k_vis done reading the set (main stream)
         bool visRecorded = false;
@@ -136,7 +177,7 @@ struct TriScratch {
             if (dplan) NR_CHECK(hipFree(dplan));
             if (gate) NR_CHECK(hipFree(gate));
             if (gplan) NR_CHECK(hipFree(gplan));
-            if (h_plan) NR_CHECK(hipHostFree(h_plan));
+            hplan.release();
             if (evBin) NR_CHECK(hipEventDestroy(evBin));
             if (evVis) NR_CHECK(hipEventDestroy(evVis));
         }
@@ -214,7 +255,8 @@ struct TriScratch {
         DevArray<u32> vlist;                             // pruned pairs, tile t's vcnt[t] of them from off[t]
         DevArray<u32> vcnt;                              // ntiles kept counts | 2 check words (always 0) | the kept total
         DevArray<u32> vmask;                             // one bit per triangle: it won a pixel
-        int visState = 0;                                // 0 none, 1 marking frame enqueued, 2 pruned
+        enum class VisStage { None, Marking /* marking frame enqueued */, Pruned };
+        VisStage visState = VisStage::None;
         int visZ = 0;                                    // depth mode (k_vis ZMODE) of the marking frame
         int markSet = -1; u32 markTag = 0;               // the list the marking frame read (pruned from the same one)
         hipEvent_t evMark = nullptr;                     // the marking frame is done (main stream)
@@ -224,11 +266,10 @@ struct TriScratch {
         // visible counts, no item for work the frame no longer needs
         DevArray<uint4> vitems;                          // its k_vis work items
         u32* vplan = nullptr;                            // its device totals (PW_DEV words; PW_FITS always 1)
-        u64* h_vplan = nullptr;                          // pinned, device-mapped host copy, (seq << 32) | value
-        u64* d_hvplan = nullptr;                         // its device address
-        u32 vplanSeq = 0;                                // sequence number of the last visible plan
-        int replanState = 0;                             // 0 none, 1 enqueued, 2 its totals seen by the host
-        BatchTotals vtotals;                             // (state 2) pairs, items, split slices, dense tiles
+        SeqWords hvplan;                                 // their host copy, numbered by itself (the last visible plan's)
+        enum class ReplanStage { None, Enqueued, Seen /* its totals seen by the host */ };
+        ReplanStage replanState = ReplanStage::None;
+        BatchTotals vtotals;                             // (Seen) pairs, items, split slices, dense tiles
         u32 splitAt = 0, dslice = 0;                     // the split limits the schedule was planned under (0: defaults)
         // key cache: the final keys (zq << 32) | id of every owned tile with a kept
         // pair, as one capture frame's k_vis left them in LDS right before it shaded
@@ -240,23 +281,28 @@ struct TriScratch {
         DevArray<u32> ktile;                             // the capture frame's table (KeyCaptureTable): kkeys' address, then
                                                          // per tile its slot, or ~0 (not cached)
         u32* kplan = nullptr;                            // device totals {cached tiles, items}
-        u64* h_kplan = nullptr;                          // pinned, device-mapped host copy, (seq << 32) | value
-        u64* d_hkplan = nullptr;                         // its device address
-        u32 kplanSeq = 0;                                // sequence number of the last key plan
-        int keyState = 0;                                // 0 none, 1 item list enqueued, 2 totals seen and slots allocated,
-                                                         // 3 capture frame enqueued, 4 cached, -1 no memory (this generation)
-        u32 ktiles = 0, knitems = 0;                     // (state >= 2) cached tiles, items
+        SeqWords hkplan;                                 // their host copy (2 words), numbered by itself (the last key plan's)
+        enum class KeyStage {
+            NoMemory = -1,   // or the capture frame failed (for this generation: it stays on the visible list)
+            None,
+            Planned,         // item list enqueued
+            Slotted,         // totals seen and slots allocated
+            Capturing,       // capture frame enqueued
+            Cached
+        };
+        KeyStage keyState = KeyStage::None;
+        u32 ktiles = 0, knitems = 0;                     // (Slotted and later) cached tiles, items
         hipEvent_t evKey = nullptr;                      // the capture frame is done (main stream)
-        void drop_visible() { visState = 0; replanState = 0; keyState = 0; }
+        void drop_visible() { visState = VisStage::None; replanState = ReplanStage::None; keyState = KeyStage::None; }
         void release() {
             off.release(); items.release(); off2.release();
             vlist.release(); vcnt.release(); vmask.release(); vitems.release();
             kkeys.release(); kitems.release(); ktile.release();
             if (kplan) NR_CHECK(hipFree(kplan));
-            if (h_kplan) NR_CHECK(hipHostFree(h_kplan));
+            hkplan.release();
             if (evKey) NR_CHECK(hipEventDestroy(evKey));
             if (vplan) NR_CHECK(hipFree(vplan));
-            if (h_vplan) NR_CHECK(hipHostFree(h_vplan));
+            hvplan.release();
             if (evMark) NR_CHECK(hipEventDestroy(evMark));
             if (dplan) NR_CHECK(hipFree(dplan));
             if (blocks) NR_CHECK(hipFree(blocks));

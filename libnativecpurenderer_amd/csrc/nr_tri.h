@@ -15,7 +15,8 @@
 //   nr_tri_ordered.hip  in-order tile raster (any batch: blending, Z w/o write)
 //   nr_tri_free.hip     visibility-buffer raster (opaque batches: every
 //                       fragment overwrites, so per-pixel results are an
-//                       order-independent min/max over packed keys)
+//                       order-independent min/max over packed keys); its
+//                       kernels are in nr_free_bin.hip and nr_free_vis.hip
 #pragma once
 
 #include "nr_common.h"
@@ -373,7 +374,7 @@ __device__ __forceinline__ bool row_span32(const Span32& S, int r, f64 y, float 
     return ok;
 }
 
-// The key cache's capture table, in device memory (nr_tri_free.hip, capture_keys): the address of the slots (TH * TW
+// The key cache's capture table, in device memory (nr_free_vis.hip, capture_keys): the address of the slots (TH * TW
 // keys each) and every tile's slot, ~0 for a tile that is not cached (no kept pair, or another rank's).
 struct KeyCaptureTable {
     u64* keys;
@@ -561,7 +562,7 @@ enum Opacity { OPQ_UNKNOWN = 0, OPQ_OPAQUE, OPQ_BLENDED };
 
 // Words of a binned batch's plan (k_free_plan*): the device copy (a set's
 // dplan, the schedule's, a gate's gplan) holds the first PW_DEV, read by the
-// kernels after the plan; the host copy (FreeSet::h_plan) all PW_COUNT.
+// kernels after the plan; the host copy (FreeSet::hplan) all PW_COUNT.
 enum PlanWord {
     PW_PAIRS = 0,   // (tile, triangle) pairs
     PW_ITEMS,       // k_vis work items

@@ -1,4 +1,4 @@
-// nr_tri_shade.h — per-pixel pieces of the order-free raster (nr_tri_free.hip,
+// nr_tri_shade.h — per-pixel pieces of the order-free raster (nr_free_vis.hip,
 // k_vis): the depth of one fragment as a packed visibility key, and the
 // deferred shading of a pixel from its winning triangle (record ->
 // barycentrics -> colour -> ApplyPixel, cpp:515-549 -> framebuffer, depth and

@@ -1,4 +1,4 @@
-"""A numpy restatement of the key cache's totals (nr_tri_free.hip, k_key_plan):
+"""A numpy restatement of the key cache's totals (nr_free_bin.hip, k_key_plan):
 one key item per owned tile, a cached slot of TH * TW keys for every owned tile
 with a kept pair.
 

@@ -1,4 +1,4 @@
-"""A numpy restatement of the visible plan (nr_tri_free.hip, k_vis_plan): the
+"""A numpy restatement of the visible plan (nr_free_bin.hip, k_vis_plan): the
 work items of a pruned pair list, planned from the tiles' kept counts.
 
 The kept counts come from the CPU alone: the binning's tile rectangle rule
@@ -8,7 +8,7 @@ and the pruning's padding rule keeps at least one pair per slice of a tile the
 schedule had split.  From them: the split limits, every tile's items, the
 totals (pairs, items, split slices, dense tiles) and the items' size classes.
 
-The constants restate the library's (nr_tri_free.hip)."""
+The constants restate the library's (nr_free.h, nr_free_bin.hip)."""
 import numpy as np
 
 import visible_ref as V

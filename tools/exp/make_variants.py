@@ -195,7 +195,7 @@ def parse(n):
 def main(names):
     specs = [parse(n) for n in names]
     used = {d for _, _, ds in specs for d in ds}
-    src = open(os.path.join(SRC, "nr_tri_free.hip")).read()
+    src = open(os.path.join(SRC, "nr_free_vis.hip")).read()   # (the raster kernels: where the anchors are)
     for d in sorted(used):
         for a, b in PATCHES[d]:
             if src.count(a) != 1:
@@ -206,7 +206,7 @@ def main(names):
     tmp = os.path.join(SRC, "_exp_tri_free.hip")
     open(tmp, "w").write(src)
     objs = [os.path.join(ROOT, "build", "obj", f) for f in sorted(os.listdir(os.path.join(ROOT, "build", "obj")))
-            if f.endswith(".o") and f != "nr_tri_free.o"]
+            if f.endswith(".o") and f != "nr_free_vis.o"]
     procs = []
     try:
         for n, defs, _ in specs:
