@@ -8,9 +8,9 @@ helpers this file uses.
 
 A repeat draw of a TriangleBuffer takes a shortcut that depends on host state
 earlier frames left behind (the warm schedule, its kept pair list, the visible
-list), so here the context -- its framebuffer, depth, transform and every knob
--- lives for the whole sequence, and nothing is cleared unless an operation
-says so.
+list, the visible plan, the key cache), so here the context -- its
+framebuffer, depth, transform and every knob -- lives for the whole sequence,
+and nothing is cleared unless an operation says so.
 
 A sequence is (W, H, alpha, knobs, buffers, frames).
 
@@ -18,9 +18,11 @@ knobs       dict, GPU only, applied to every context when it is created: warm
             (set_warm_binning), reuse (set_list_reuse), prune
             (set_visible_pruning), coop (set_coop_raster), split
             (set_split_limits arguments or None), paircap
-            (set_pair_capacity_override), ordered (set_force_ordered_raster).
+            (set_pair_capacity_override), ordered (set_force_ordered_raster),
+            replan (set_visible_replan, 0 | 2), keys (set_key_cache, 0 | 2).
 buffers     TriangleBuffers made before the first frame, over the W x H frame:
             ("flat" | "gouraud" | "blend", n, seed, spread)  colour soups (frame_ops.colour_soup), blend: translucent
+            ("patch", n, seed, spread)   a Gouraud soup over the left 55 % of the frame: the tiles right of it keep no pair
             ("tex", n, seed, spread)     one (u, v) per triangle (frame_ops.textured_soup, "const"); texture per draw
             ("hidden", seed)             400 slivers inside tile 0 behind two covering triangles
             ("sphere", rows, cols)       scenes.sphere_mesh
@@ -48,7 +50,8 @@ stated:
                         -> the u8 image / scenes.yuv420p of it.  None changes nothing in the library, which
                         cannot switch its frame output off once a gather has switched it on: the interpreter
                         only stops gathering and records the u8 image again
-("warm", m) ("reuse", m) ("prune", m) ("coop", m) ("split", v) ("paircap", v) ("ordered", v) ("begin",) ("end",)
+("warm", m) ("reuse", m) ("prune", m) ("coop", m) ("split", v) ("paircap", v) ("ordered", v) ("replan", m) ("keys", m)
+("begin",) ("end",)
                         GPU only: the knobs flipped mid-sequence, command recording -> nothing
 ("fragcount", on)       set_fragment_counting; while on (and unsharded) the count after each frame is recorded
                         -> the sum of last_fragment_count() over the triangle draws since
@@ -70,20 +73,22 @@ from hypothesis import HealthCheck, given, settings, strategies as st
 import frame_ops as F
 import scenes
 import textured_ref as T
+import visible_ref as V
 
 BG = (0.25, 0.5, 0.75, 1.0)
 FULL = 0xFFFFFFFF
 MOVES = {"none": None, "sub": ("t", 0.4, 0.3), "edge": ("t", 2.0, -2.0), "over": ("t", 2.0000001, 0.0),
          "far": ("t", 9.0, 5.0), "scale": ("s", 1.001)}
-KNOBS_DEFAULT = dict(warm=1, reuse=0, prune=0, coop=0, split=None, paircap=0, ordered=False)
-KNOB_OPS = ("warm", "reuse", "prune", "coop", "split", "paircap", "ordered")
+KNOBS_DEFAULT = dict(warm=1, reuse=0, prune=0, coop=0, split=None, paircap=0, ordered=False, replan=0, keys=0)
+KNOB_OPS = ("warm", "reuse", "prune", "coop", "split", "paircap", "ordered", "replan", "keys")
 TEXTURES = {"rgb": (F.NOMINAL_UV[0], F.NOMINAL_UV[1], 3, "f64", 5, None),
             "rgba": (F.NOMINAL_UV[0], F.NOMINAL_UV[1], 4, "u8", 6, None)}
 ALL_OPS = ("clear", "cleardepth", "depthstate", "ct", "buf", "host", "soup", "rect", "circle", "tex", "resize", "shard",
            "fmt") + KNOB_OPS + ("begin", "end", "fragcount", "recreate", "ctx")
-BUFFER_KINDS = ("flat", "gouraud", "blend", "tex", "hidden")
+BUFFER_KINDS = ("flat", "gouraud", "blend", "tex", "hidden", "patch")
 ARRAYS = ("frame", "f64", "depth", "u8")
-COUNTERS = ("warm", "loose", "reused", "pruned")
+COUNTERS = ("warm", "loose", "reused", "pruned", "replanned", "cached")
+KEY_TILE_BYTES = V.TW * V.TH * 8              # a cached tile: a key of 8 bytes per pixel of the rasters' tile
 
 
 # ---------------------------------------------------------------------------
@@ -119,6 +124,8 @@ def buffer_arrays(spec, W, H):
             a = scenes.sphere_mesh(W, H, spec[1], spec[2])
         elif kind == "tex":
             a = F.textured_soup(spec[1], W, H, spec[2], spec[3], "const", F.NOMINAL_UV)
+        elif kind == "patch":                 # (of the 4 tile columns at 200 x 140, the right one or two keep no pair)
+            a = F.colour_soup(spec[1], 0.55 * W, H, spec[2], spec[3], True, False)
         else:
             a = F.colour_soup(spec[1], W, H, spec[2], spec[3], kind != "flat", kind == "blend")
         _ARRAYS[key] = a
@@ -137,6 +144,26 @@ def recreated(spec, seed):
 # ---------------------------------------------------------------------------
 # the interpreter
 # ---------------------------------------------------------------------------
+def owned_tile_count(W, H, shard):
+    """Tiles of a W x H frame in the tile rows rank shard[1] of shard[0] owns."""
+    tx, ty = (W + V.TW - 1) // V.TW, (H + V.TH - 1) // V.TH
+    return tx * (ty if shard is None else len(range(shard[1], ty, shard[0])))
+
+
+def check_key_totals(t, c, made_for):
+    """What holds of key_cache_totals() without a reference: a key item per
+    tile the context's shard owns, a cached slot for some of them.  For none
+    only where a shard may own no tile with a kept pair: it owns no tile at
+    all (1 x 58 is two tiles), or the frame is not of the size `made_for` its
+    buffers were made to cover (64 x 32 resized to 200 x 140: the tile rows
+    of rank 1 of 3 lie below every triangle)."""
+    size = (c.ctx.width, c.ctx.height)
+    items = owned_tile_count(size[0], size[1], c.shard)
+    some = items > 0 and (c.shard is None or size == made_for)
+    assert t["items"] == items and some <= t["tiles"] <= items, (t, items, c.shard)
+    assert t["bytes"] == t["tiles"] * KEY_TILE_BYTES, t
+
+
 class _Context:
     def __init__(self, ctx):
         self.ctx = ctx
@@ -146,6 +173,8 @@ class _Context:
         self.counting = False
         self.frags = 0
         self.uniform = False                  # a uniform colour clear that nothing has drawn over yet
+        self.written = False                  # any other colour clear (written at once) that nothing has drawn over yet
+        self.pruned_at = -1                   # GPU: the last frame with a pruned batch
 
 
 class _Run:
@@ -167,7 +196,8 @@ class _Run:
         else:
             {"warm": ctx.set_warm_binning, "reuse": ctx.set_list_reuse, "prune": ctx.set_visible_pruning,
              "coop": ctx.set_coop_raster, "paircap": ctx.set_pair_capacity_override,
-             "ordered": ctx.set_force_ordered_raster}[name](v)
+             "ordered": ctx.set_force_ordered_raster, "replan": ctx.set_visible_replan,
+             "keys": ctx.set_key_cache}[name](v)
 
     def context(self, c):
         if c not in self.ctxs:
@@ -201,21 +231,27 @@ class _Run:
 
     # ---- triangle batches -----------------------------------------------------
     def _counts(self, ctx):
-        return (ctx.warm_batch_count(), ctx.loose_batch_count(), ctx.reused_batch_count(), ctx.pruned_batch_count())
+        return (ctx.warm_batch_count(), ctx.loose_batch_count(), ctx.reused_batch_count(), ctx.pruned_batch_count(),
+                ctx.replanned_batch_count(), ctx.key_cached_batch_count())
 
     def batch(self, what, i, draw):
         """Runs draw() and notes what became of the batch: GPU "ordered" |
-        "pruned" | "reused" | "loose" | "warm" | "cold"."""
+        "pruned" | "reused" | "loose" | "warm" | "cold"; a batch shaded from the
+        key cache is a pruned batch too, here as in the library's counters
+        ("pruned" with cached=True), and so is one under the visible plan
+        (replanned=True)."""
         c = self.cur
         before = self._counts(c.ctx) if self.gpu else None
-        uniform, c.uniform = c.uniform, False
+        uniform, written, c.uniform, c.written = c.uniform, c.written, False, False
         draw()
         if self.gpu:
             d = [a - b for a, b in zip(self._counts(c.ctx), before)]
             how = ("ordered" if c.ctx.last_raster_path() == "ordered" else
                    "pruned" if d[3] else "reused" if d[2] else "loose" if d[1] else "warm" if d[0] else "cold")
+            if how == "pruned":
+                c.pruned_at = self.k
             self.draws.append(dict(frame=self.k, ctx=self.cid, op=what, buf=i, how=how, depth=c.depth, shard=c.shard,
-                                   counting=c.counting, uniform=uniform))
+                                   counting=c.counting, fmt=c.fmt, uniform=uniform, written=written, replanned=bool(d[4]), cached=bool(d[5])))
         elif c.counting:
             c.frags += c.ctx.last_fragment_count()
 
@@ -250,10 +286,11 @@ class _Run:
         c = self.cur
         ctx = c.ctx
         if k in ("rect", "circle", "tex", "resize", "shard"):
-            c.uniform = False
+            c.uniform = c.written = False
         if k == "clear":
             ctx.set_color(*op[1])
             c.uniform = len(set(op[1])) == 1
+            c.written = not c.uniform
         elif k == "cleardepth":
             ctx.clear_depth(op[1])
         elif k == "depthstate":
@@ -335,10 +372,17 @@ class _Run:
             cs = [c.ctx for _, c in sorted(self.ctxs.items())]
             n = dict(zip(COUNTERS, (sum(v) for v in zip(*[self._counts(x) for x in cs]))))
             n["path"] = self.cur.ctx.last_raster_path()
-            if read:                          # (these two wait for the device: only where the frame is read anyway)
+            if read:                          # (these wait for the device: only where the frame is read anyway)
                 n["visible"] = self.cur.ctx.visible_pair_count()
                 n["totals"] = self.cur.ctx.schedule_totals()
                 n["failures"] = sum(x.warm_failure_count() for x in cs)
+                n["keytotals"] = self.cur.ctx.key_cache_totals()
+                n["vplan"] = self.cur.ctx.visible_plan_totals()
+                # (the exact totals: tests/key_cache_ref.py.  A shard change leaves the schedule of the shard before
+                # in place until a batch bins under the new one: only after a frame with a pruned batch are the
+                # totals those of the context's shard and size.)
+                if n["keytotals"] and self.cur.pruned_at == self.k:
+                    check_key_totals(n["keytotals"], self.cur, (self.W, self.H))
             out["counters"].append(n)
 
     def run(self):
@@ -361,12 +405,15 @@ class _Run:
 def run(fac, seq):
     """Executes `seq` on `fac`: dict records [dict k (the frame's number), ctx,
     shard, f64, depth, u8 | frame], frags [(frame, ctx, count)], and on the GPU counters
-    (per frame: warm, loose, reused, pruned summed over the contexts, path;
-    only after a recorded frame also visible, totals, failures:
-    visible_pair_count and warm_failure_count wait for the device, and an
-    unread frame is there so that the host runs ahead of it), draws (per
-    triangle batch: frame, ctx, op, buf, how, depth, shard, counting, uniform: drawn
-    over a pending uniform colour clear), failures, error."""
+    (per frame: warm, loose, reused, pruned, replanned, cached summed over the
+    contexts, path; only after a recorded frame also visible, totals, failures,
+    keytotals, vplan of the current context: visible_pair_count,
+    warm_failure_count, key_cache_totals and visible_plan_totals wait for the
+    device, and an unread frame is there so that the host runs ahead of it),
+    draws (per triangle batch: frame, ctx, op, buf, how, depth, shard, counting,
+    fmt, uniform: drawn over a pending uniform colour clear, written: over any
+    other colour clear, replanned, cached),
+    failures, error."""
     return _Run(fac, seq).run()
 
 
@@ -405,6 +452,21 @@ def _longest(flags):
         run_ = run_ + 1 if f else 0
         best = max(best, run_)
     return best
+
+
+def quiet_runs(frames):
+    """[(first frame, length)] of the maximal runs of read frames with the same
+    operations: six of them reach the key cache (cold, warm, marking, pruned,
+    capture, cached)."""
+    runs, k = [], 0
+    while k < len(frames):
+        j = k + 1
+        if frames[k][1]:
+            while j < len(frames) and frames[j] == frames[k]:
+                j += 1
+            runs.append((k, j - k))
+        k = j
+    return runs
 
 
 def describe(seq):
@@ -451,28 +513,31 @@ def describe(seq):
 # sequence is runs of unchanged repeats of one frame template (clears, then the
 # template's buffer draws with its other batches between them), at least five
 # frames long more often than not -- cold, warm, marking frame, pruned,
-# pruned -- with one or two disturbances between two runs; what a disturbance switches
+# pruned -- and seven or more in a third of the small sequences and every large
+# one (capture, cached), with one or two disturbances between two runs; what a disturbance switches
 # off (a knob, an ordered colour transform, fragment counting) is mostly
 # switched back on a frame or two later.
 SIZES = [(200, 140)] * 7 + [(64, 32)] * 2 + [(1, 58)]     # 4 x 5 tiles with partial right and bottom tiles; one tile; one column
 DEPTHS = [(True, True)] * 4 + [(False, False)] * 3 + [(True, False), (False, True)]
 SHARDS = [(2, 0), (2, 1), (2, 1), (3, 1), (8, 3)]
-_DISTURB = (["move"] * 5 + ["depth"] * 5 + ["colour"] * 4 + ["zval"] * 2 + ["noclear"] * 3 + ["ct"] * 2 + ["shard"] * 2 + ["resize"] * 2 +
-            ["fmt"] * 2 + ["knob"] * 7 + ["fragcount"] + ["recreate"] + ["ctx"] + ["batch"] * 5 + ["template"] * 2 +
+_DISTURB = (["move"] * 5 + ["depth"] * 5 + ["colour"] * 4 + ["zval"] * 3 + ["noclear"] * 5 + ["ct"] * 2 + ["shard"] * 2 + ["resize"] * 2 +
+            ["fmt"] * 2 + ["knob"] * 12 + ["fragcount"] + ["recreate"] + ["ctx"] * 3 + ["batch"] * 5 + ["template"] * 2 +
             ["unread"] * 3)
 _DISTURB_LARGE = ["move"] * 2 + ["depth", "depth", "zval", "colour", "noclear", "resize", "resize", "unread"]
-_OFF = {"warm": (2, 1), "reuse": (2, 0), "prune": (2, 0), "paircap": (50, 0), "ordered": (True, False)}   # (off, on)
+_OFF = {"warm": (2, 1), "reuse": (2, 0), "prune": (2, 0), "paircap": (50, 0), "ordered": (True, False), "replan": (2, 0),
+        "keys": (2, 0)}   # (off, on)
 
 
 class _Gen:
-    def __init__(self, r, W, H, large=False):
-        self.r, self.W, self.H, self.large = r, W, H, large
+    def __init__(self, r, W, H, large=False, long=False):
+        self.r, self.W, self.H, self.large, self.long = r, W, H, large, long
         self.cur = 0
         self.S = {c: dict(depth=(True, True), shard=None, fmt=None, size=(W, H)) for c in (0, 1)}
         self.cc = self.cd = True
         self.zval = FULL
         self.colour = self.clear_colour(r.random() < 0.5)
         self.extras = []
+        self.coop = None
         # a large sequence holds, whatever else is drawn: a loose move, and a depth-mode switch or a resize and back
         self.must = r.sample(["loose", r.choice(["depth", "resize"])], 2) if large else []
         self.pending = []                     # (frame, context, op): what is switched back later
@@ -494,7 +559,7 @@ class _Gen:
         r = self.r
         specs = []
         for k in range(r.choice([1, 2, 2, 3])):
-            kind = (r.choice(["flat", "gouraud", "gouraud", "tex", "hidden"]) if k == 0 else
+            kind = (r.choice(["flat", "gouraud", "gouraud", "tex", "hidden", "patch"]) if k == 0 else
                     r.choice(["blend", "blend", "blend", "tex", "tex", "flat", "gouraud"]))
             if kind == "hidden" and (self.W < 64 or any(s[0] == "hidden" for s in specs)):
                 kind = "gouraud"
@@ -547,13 +612,17 @@ class _Gen:
             other = {(True, True): (False, False), (False, False): (True, True)}.get(s["depth"])
             s["depth"] = other if other and r.random() < 0.6 else r.choice([d for d in DEPTHS if d != s["depth"]])
             return [("depthstate",) + s["depth"]]
-        elif name == "colour":               # uniform <-> non-uniform
-            self.colour, self.cc = self.clear_colour(len(set(self.colour)) != 1), True
-        elif name == "zval":
+        elif name == "colour":               # uniform <-> non-uniform, or (a tile nothing is drawn in shows it) another uniform one
+            uniform = len(set(self.colour)) == 1
+            self.colour, self.cc = self.clear_colour(not uniform or r.random() < 0.4), True
+        elif name == "zval":                 # (mostly back to 0xFFFFFFFF later: the depth clear the shortcuts capture over)
             self.zval, self.cd = r.choice(F.DEPTH_VALUES), True
+            if self.zval != FULL:
+                self.later(k, ("_clears",), p=0.7, after=(1, 2, 3))
         elif name == "noclear":
             if self.cc and self.cd:
                 self.cc, self.cd = r.choice([(False, False), (False, False), (True, False)])
+                self.later(k, ("_clears",), p=0.7, after=(1, 2, 3))
             else:
                 self.cc = self.cd = True
         elif name == "ct":
@@ -577,11 +646,14 @@ class _Gen:
             s["fmt"] = r.choice([f for f in (None, "rgb", "yuv420p") if f != s["fmt"] and (even or f != "yuv420p")])
             return [("fmt", s["fmt"])]
         elif name == "knob":
-            knob = r.choice(["warm", "reuse", "prune", "coop", "split", "paircap", "ordered"])
+            knob = r.choice(KNOB_OPS + ("keys", "keys", "replan"))
             if knob in _OFF:
                 self.later(k, (knob, _OFF[knob][1]), p=0.9)
                 return [(knob, _OFF[knob][0])]
-            return [(knob, r.choice([0, 1, 2]) if knob == "coop" else r.choice([None, (64, 64)]))]
+            if knob == "coop":                # (never the value the last flip left)
+                self.coop = r.choice([m for m in (0, 1, 2) if m != self.coop])
+                return [("coop", self.coop)]
+            return [("split", r.choice([None, (64, 64)]))]
         elif name == "fragcount":
             self.later(k, ("fragcount", False), p=1.0, after=(1, 2, 2))
             return [("fragcount", True)]
@@ -589,7 +661,7 @@ class _Gen:
             return [("recreate", r.choice(self.draws)[0], self.seed())]
         elif name == "ctx":
             self.cur = 1 - self.cur
-            self.later(k, ("ctx", 1 - self.cur), p=0.7, after=(1, 1, 2, 6))
+            self.later(k, ("ctx", 1 - self.cur), p=0.7, after=(1, 2, 7, 8))
             return [("ctx", self.cur)]
         elif name == "batch":
             if self.extras and r.random() < 0.5:
@@ -618,18 +690,43 @@ class _Gen:
                 pre += self.disturb(0, "depth")
             if r.random() < 0.2:
                 pre += self.disturb(0, "shard")
-            if r.random() < 0.2:
+            # (tiles without a kept pair: the rasters write their share of a frame output themselves under a pending
+            # uniform colour clear, so a patch mostly starts with both)
+            patch = self.specs[0][0] == "patch"
+            if patch and r.random() < 0.7:
+                self.colour = self.clear_colour(True)
+            if r.random() < (0.7 if patch else 0.2):
                 pre += self.disturb(0, "fmt")
             if len(self.specs) > 1 and r.random() < 0.6:
                 self.draws.append((1, self.texref(1)))
-        quiet = 4 if self.large else r.choice([4, 5, 5, 6]) if r.random() < 0.85 else 0
+        # (the key cache: six unchanged read frames reach it -- cold, warm, marking, pruned, capture, cached; frame 0
+        # differs from the ones after it by what `pre` holds)
+        if self.large:
+            quiet = r.choice([6, 7])
+        elif self.long:
+            quiet = r.choice([7, 8]) + bool(pre)
+        else:
+            quiet = r.choice([4, 5, 5, 6]) if r.random() < 0.85 else 0
+            if self.specs[0][0] == "patch":   # (its empty tiles are there for the cached frames)
+                quiet = max(quiet, 6)
         unread = 0
+        opening = quiet
+        # (a long sequence now and then goes on in the second context at once: room to be cached there too)
+        first = "ctx" if self.long and r.random() < 0.3 else None
         out = []
         for k in range(n):
             self.move, self.once = None, []
+            # (a patch after its opening run: a uniform clear mostly to another colour than the frame before, which is
+            # what shows in a tile without a kept pair; the colour is live state and ends no shortcut)
+            patch = not self.large and self.specs[0][0] == "patch"
+            if patch and k >= opening and len(set(self.colour)) == 1 and r.random() < 0.5:
+                self.colour = self.clear_colour(True)
             due = [p for p in self.pending if p[0] <= k and p[1] == self.cur]
             for p in sorted(due, key=lambda p: p[2][0] == "ctx"):   # (the context switch last)
                 self.pending.remove(p)
+                if p[2][0] == "_clears":      # (not an operation: the template clears colour and depth again, to 0xFFFFFFFF)
+                    self.cc, self.cd, self.zval = True, True, FULL
+                    continue
                 pre.append(p[2])
                 if p[2][0] == "ctx":
                     self.cur = p[2][1]
@@ -643,7 +740,7 @@ class _Gen:
                 quiet -= 1
             else:
                 kinds = _DISTURB_LARGE if self.large else _DISTURB
-                name = self.must.pop(0) if self.must else r.choice(kinds)
+                name = self.must.pop(0) if self.must else first or r.choice(kinds)
                 if name == "unread":
                     unread = r.choice([2, 3]) if self.large else r.choice([3, 4, 5])
                     read = False
@@ -651,7 +748,11 @@ class _Gen:
                     pre += self.disturb(k, name)
                     if r.random() < 0.35:     # (now and then two at once)
                         pre += self.disturb(k, r.choice([d for d in kinds if d not in (name, "unread", "ctx")]))
-                    quiet = r.choice([1, 2]) if self.must else r.choice([0, 0, 1, 1, 2, 5, 6])
+                    quiet = (r.choice([1, 2]) if self.must else r.choice([0, 1, 2, 6, 7, 7, 8]) if self.long else
+                             r.choice([0, 0, 1, 1, 2, 5, 6]))
+                    if name == "ctx" and (first or r.random() < 0.6):   # (long enough in the other context to be cached there)
+                        quiet = max(quiet, 6)
+                    first = None
             ops = pre
             if self.cc:
                 ops.append(("clear", self.colour))
@@ -669,32 +770,36 @@ class _Gen:
 def make_small_seq(seed, salt, alpha):
     r = random.Random(f"seq/{seed}/{salt}/{alpha}")
     W, H = r.choice(SIZES)
-    g = _Gen(r, W, H)
+    long = r.random() < 1 / 3                 # long enough to be cached, disturbed and cached again
+    g = _Gen(r, W, H, long=long)
     specs = g.buffers()
     knobs = dict(KNOBS_DEFAULT, warm=r.choice([0, 1, 1]), coop=r.choice([0, 0, 1, 2]))
     if r.random() < (0.8 if specs[0][0] == "hidden" else 0.15):
         knobs["split"] = (64, 64)
-    return (W, H, alpha, knobs, specs, g.frames(r.randint(10, 16)))
+    return (W, H, alpha, knobs, specs, g.frames(r.randint(18, 24) if long else r.randint(10, 16)))
 
 
 def make_large_seq(seed, salt, alpha):
     r = random.Random(f"large/{seed}/{salt}/{alpha}")
     g = _Gen(r, 640, 400, large=True)
     g.specs = [("sphere", 250, 700)]
-    return (640, 400, alpha, dict(KNOBS_DEFAULT), g.specs, g.frames(r.randint(10, 12)))
+    return (640, 400, alpha, dict(KNOBS_DEFAULT), g.specs, g.frames(r.randint(12, 14)))
 
 
 _seed = st.integers(0, 2**31 - 1)
 
 
 def small_seqs():
-    """200 x 140, 64 x 32 or 1 x 58; 10-16 frames; 1-3 buffers of 200-3000 triangles."""
+    """200 x 140, 64 x 32 or 1 x 58; 10-16 frames, a third of them 18-24 with an
+    opening run of 7-8 unchanged frames; 1-3 buffers of 200-3000 triangles."""
     return st.builds(make_small_seq, _seed, _seed, st.booleans())
 
 
 def large_seqs():
     """640 x 400, one buffer of 350 000 triangles (the inline warm binning);
-    10-12 frames of clears, depth modes, moves, resize and back, unread frames."""
+    12-14 frames, the first 6-7 unchanged (the visible plan -- the schedule has
+    split tiles -- and the key cache), then clears, depth modes, moves, resize
+    and back, unread frames."""
     return st.builds(make_large_seq, _seed, _seed, st.booleans())
 
 

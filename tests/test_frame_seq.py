@@ -35,7 +35,7 @@ def test_small_sequences_hold_every_operation_and_hand_off(small):
     assert len(small) >= 40 and sum(len(s[5]) for s in small) >= 400
     held = [S.describe(s) for s in small]
     for W, H, alpha, knobs, specs, frames in small:
-        assert (W, H) in ((200, 140), (64, 32), (1, 58)) and 8 <= len(frames) <= 16 and 1 <= len(specs) <= 3
+        assert (W, H) in ((200, 140), (64, 32), (1, 58)) and 8 <= len(frames) <= 24 and 1 <= len(specs) <= 3
         assert all(200 <= S.triangle_count(spec) <= 3000 for spec in specs)
     assert {(s[0], s[1]) for s in small} == {(200, 140), (64, 32), (1, 58)}
     ops = set().union(*[d["ops"] for d in held])
@@ -58,6 +58,13 @@ def test_small_sequences_hold_every_operation_and_hand_off(small):
     # runs of unchanged repeats, long enough for the visible list: 5 frames in a row with the same operations
     runs = [S._longest([a[0] == b[0] for a, b in zip(s[5], s[5][1:])]) + 1 for s in small]
     assert sum(n >= 5 for n in runs) >= len(small) // 2, runs
+    # ... and for the key cache: six unchanged read frames reach it (cold, warm, marking, pruned, capture, cached),
+    # a seventh is shaded from it once more; cached, then disturbed, then room to be cached again
+    quiet = [S.quiet_runs(s[5]) for s in small]
+    assert sum(any(n >= 7 for _, n in q) for q in quiet) >= (len(small) + 3) // 4, quiet
+    again = [any(n >= 6 and len(s[5]) - (k + n + 1) >= 6 for k, n in q) for s, q in zip(small, quiet)]
+    assert sum(again) >= 8, again
+    assert sum(len(s[5]) >= 18 for s in small) >= len(small) // 5, "the long flavour"
 
 
 def test_large_sequences_reach_the_inline_binning_size(large):
@@ -68,6 +75,8 @@ def test_large_sequences_reach_the_inline_binning_size(large):
         assert S.triangle_count(specs[0]) >= 300000 and len(S.buffer_arrays(specs[0], W, H)[0]) == S.triangle_count(specs[0])
         assert {op[0] for ops, _ in frames for op in ops} <= allowed
         assert knobs == S.KNOBS_DEFAULT
+        # the visible plan (the schedule has split tiles) and the key cache: six unchanged read frames first
+        assert S.quiet_runs(frames)[0][0] == 0 and S.quiet_runs(frames)[0][1] >= 6, S.quiet_runs(frames)
         # after a repeat: a loose move, and a depth-mode switch or a resize and back to the first size
         held = S.describe((W, H, alpha, knobs, specs, frames))
         assert held["moves"] & {"sub", "edge"}, held["moves"]
