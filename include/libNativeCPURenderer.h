@@ -252,6 +252,46 @@ bool AssembleMeshInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, con
                                  first min(cap, *n_out) triangles copied to the host (xy x6, z x3, attr x12 / x4 / x6;
                                  q x3 only for a perspective textured draw, q_out may be NULL otherwise); a sync
                                  point; either mesh kind */
+/* NEW: lit meshes (DESIGN §3 "Vertex lighting"): per-vertex normals under an ambient colour and up to 8
+   directional lights, computed on the device by one pass over the vertices of each *Lit draw.  Per vertex, in
+   f64, every product and sum rounded in the order written (no sqrt, no division, no renormalisation: unit normals
+   and rotation-only normal matrices are the caller's business), with N the row-major 3x3 normal matrix:
+     wx = (N[0]*nx + N[1]*ny) + N[2]*nz   (wy: row 1, wz: row 2);   acc_c = ambient_c;
+     per light (dx, dy, dz, cr, cg, cb) in order, d towards the light:
+       dot = (wx*dx + wy*dy) + wz*dz;  d = dot > 0 ? dot : 0.0 (a NaN dot: 0);  acc_c = acc_c + d * c_c;
+     lit_c = clamp(base_c * acc_c) to [0, 1] (a NaN stays NaN);  alpha is untouched.
+   The lit colours replace the mesh's own before anything else reads them: a flat mesh takes the lit colour of a
+   triangle's first index, the clip stage interpolates lit colours, an instance's tint multiplies them.  Every
+   state of DrawMesh applies, and with the default lights (ambient (1, 1, 1), none) a lit draw is DrawMesh's frame
+   bit for bit.  The light state is per context, copied at the call, not part of the save / restore stack, not
+   recorded in command lists, and read when a draw is issued.  A *Lit call with a mesh that has no normals, or a
+   textured mesh: error latched, nothing drawn, the last count 0. */
+Mesh* CreateLitMesh(i64 nv, const f64* pos, const f64* normal, i64 n, const uint32_t* idx, const f64* rgba,
+                    bool gouraud);                                       /* NEW: CreateMesh with normals (nv*3); NULL
+                                 normals with nv > 0: NULL, error latched.  DrawMesh / DrawMeshInstanced draw it unlit */
+bool UpdateMeshNormals(Mesh* m, const f64* normal);                      /* NEW: as UpdateMeshPositions; a mesh without
+                                 normals: false, error latched */
+bool GetMeshLit(Mesh* m);                                                /* NEW: created with normals */
+bool SetMeshLights(RenderContext* ctx, const f64* ambient3, const f64* lights, i64 nl);   /* NEW: ambient3 NULL:
+                                 (1, 1, 1); lights nl*6, 0 <= nl <= 8; nl out of range or NULL lights with nl > 0:
+                                 false, error latched, state unchanged; the values are not validated */
+i64 GetMeshLightCount(RenderContext* ctx);                               /* NEW */
+void DrawMeshLit(RenderContext* ctx, Mesh* m, const f64* matrix16, const f64* normal9);   /* NEW: normal9 NULL: the
+                                 identity */
+void DrawMeshLitInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* normals, const f64* tint,
+                          i64 K);                                        /* NEW: normals K*9 or NULL (the identity for
+                                 every instance), tint K*4 or NULL; DrawMeshInstanced's checks and limits; host
+                                 arrays, the caller's again on return */
+void DrawMeshLitInstancedDevice(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* normals,
+                                const f64* tint, i64 K);                 /* NEW: device pointers, valid and unchanged
+                                 until the draw has executed; read only by kernels launched inside the call */
+bool AssembleMeshLit(RenderContext* ctx, Mesh* m, const f64* matrix16, const f64* normal9, i64 cap, f64* xy_out,
+                     f64* z_out, f64* attr_out, i64* n_out);             /* NEW: the soup a DrawMeshLit rasterises under
+                                 ctx's lights, near plane and cull mode (the draw's own kernels), in
+                                 AssembleMeshClipped's conventions (attr x12 Gouraud / x4 flat); a sync point */
+bool AssembleMeshLitInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* normals, const f64* tint,
+                              i64 K, i64 cap, f64* xy_out, f64* z_out, f64* attr_out, i64* n_out);   /* NEW: the same
+                                 for a DrawMeshLitInstanced, in AssembleMeshInstanced's conventions without q */
 void SetFragmentCounting(RenderContext* ctx, bool on);                   /* NEW: covered-fragment counter */
 i64 GetFragmentCount(RenderContext* ctx);                                /* NEW */
 i64 GetLastRasterPath(RenderContext* ctx);                               /* NEW: 1 order-free tiled, 2 ordered */

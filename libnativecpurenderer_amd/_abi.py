@@ -107,6 +107,16 @@ DEVICE_ABI = {
     "DrawMeshInstancedDevice": (None, (P, P, P, P, L)),
     "DrawTexturedMeshInstancedDevice": (None, (P, P, P, P, L)),
     "AssembleMeshInstanced": (B, (P, P, P, P, L, L, P, P, P, P, P)),
+    "CreateLitMesh": (P, (L, P, P, L, P, P, B)),
+    "UpdateMeshNormals": (B, (P, P)),
+    "GetMeshLit": (B, (P,)),
+    "SetMeshLights": (B, (P, P, P, L)),
+    "GetMeshLightCount": (L, (P,)),
+    "DrawMeshLit": (None, (P, P, P, P)),
+    "DrawMeshLitInstanced": (None, (P, P, P, P, P, L)),
+    "DrawMeshLitInstancedDevice": (None, (P, P, P, P, P, L)),
+    "AssembleMeshLit": (B, (P, P, P, P, L, P, P, P, P)),
+    "AssembleMeshLitInstanced": (B, (P, P, P, P, P, L, L, P, P, P, P)),
     "SetFragmentCounting": (None, (P, B)),
     "GetFragmentCount": (L, (P,)),
     "GetLastRasterPath": (L, (P,)),

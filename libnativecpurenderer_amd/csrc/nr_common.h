@@ -194,7 +194,8 @@ struct TriScratch {
     // DrawMesh (nr_mesh.hip): the draw's transformed vertices and assembled soup -- (x, y) nv*2, z nv (padded
     // to an even count), xy n*6, z n*3; read by the batch until it is settled, like `stage`.  A perspective
     // textured draw (SetMeshPerspective) adds the vertices' 1/w, nv padded like z, before the soup and the
-    // soup's q n*3 after its z
+    // soup's q n*3 after its z.  A lit draw (DrawMeshLit, DESIGN.md §3 "Vertex lighting") also keeps its
+    // per-vertex lit colours here (nv*4, K*nv*4 instanced) and the soup's attributes gathered from them
     DevArray<f64> mstage;
     // clipped / culled mesh draws (nr_mesh.hip, SetMeshNearPlane / SetMeshCull): the draw's clip coordinates
     // (cx, cy, cz, cw) nv*4, and per source triangle its keep mask | output count | scanned offset, n each
@@ -203,7 +204,7 @@ struct TriScratch {
     DevArray<f64> mclip;
     DevArray<u32> mscan;
     // instanced mesh draws (nr_mesh.hip, DrawMeshInstanced): the draw's K matrices (K*16) and, behind them, its
-    // tints (K*4) on the device, overwritten only after settle like mstage; a host call's arrays reach it through
+    // tints (K*4) and a lit draw's normal matrices (K*9) on the device, overwritten only after settle like mstage; a host call's arrays reach it through
     // one of the two pinned h_minst, in turn, by an asynchronous copy (evMinst: that copy is done, the buffer
     // may be rewritten)
     DevArray<f64> minst;
@@ -358,7 +359,18 @@ enum NRKernelId { NRK_TRI_COUNT = 0, NRK_TRI_SCAN, NRK_TRI_EMIT, NRK_TRI_SORT, N
                   NRK_TILE_RASTER, NRK_PRIM, NRK_FILL, NRK_RESOLVE, NRK_VIS_INIT, NRK_OUTPUT, NRK_GATHER,
                   NRK_MESH_VERTEX, NRK_MESH_ASSEMBLE, NRK_MESH_CLIP_VERTEX, NRK_MESH_CLIP_COUNT, NRK_MESH_CLIP_SCAN,
                   NRK_MESH_CLIP_EMIT, NRK_MESH_INST_VERTEX, NRK_MESH_INST_ASSEMBLE, NRK_MESH_INST_CLIP_VERTEX,
-                  NRK_MESH_INST_CLIP_COUNT, NRK_MESH_INST_CLIP_SCAN, NRK_MESH_INST_CLIP_EMIT, NRK_COUNT_ };
+                  NRK_MESH_INST_CLIP_COUNT, NRK_MESH_INST_CLIP_SCAN, NRK_MESH_INST_CLIP_EMIT,
+                  NRK_MESH_LIGHT, NRK_MESH_LIT_ATTR, NRK_MESH_INST_LIGHT, NRK_MESH_INST_LIT_ATTR, NRK_COUNT_ };
+
+// The light state of a context's lit mesh draws (SetMeshLights; DESIGN.md §3 "Vertex lighting"): the ambient
+// colour and up to MESH_MAX_LIGHTS directional lights (dx, dy, dz, cr, cg, cb), d towards the light.  51 doubles
+// and a count: handed to the light kernels by value, so a draw keeps the state it was issued under.
+constexpr int MESH_MAX_LIGHTS = 8;
+struct MeshLights {
+    f64 ambient[3] = {1, 1, 1};
+    f64 light[MESH_MAX_LIGHTS][6] = {};
+    int nl = 0;
+};
 
 struct RenderContext {
     i64 width = 0, height = 0;
@@ -410,6 +422,7 @@ struct RenderContext {
     bool meshPersp = false;           // textured mesh draws carry 1/cw to the rasters (SetMeshPerspective); same rule
     int texFilter = 0;                // textured triangle draws: 0 nearest, 1 bilinear (SetTriangleTextureFilter); same rule
     i64 meshLastCount = 0;
+    MeshLights meshLights;            // lit mesh draws (SetMeshLights): ambient (1, 1, 1), no lights; same rule
     iu8* u8buf = nullptr; size_t u8cap = 0;   // GetBufferAsUInt8 staging
     // multi-GPU: owned tile rows ty % nshards == shard (nr_dist.hip)
     int nshards = 1, shard = 0;

@@ -40,6 +40,13 @@
 // K*nv vertices and K*n triangles (k_minst_*), the assembly also copying -- or
 // tinting -- the mesh's attributes to each instance's place in the batch; the
 // single-draw kernels and host path are untouched.
+//
+// Lit draws (DrawMeshLit and its kin, DESIGN.md §3 "Vertex lighting"): a mesh
+// created with normals is lit per vertex under the context's ambient colour and
+// directional lights by one more pass over the vertices (k_mesh_light,
+// k_minst_light), whose output -- a per-draw vertex-colour table in the staging,
+// never in the mesh -- feeds the assembly, clip and instancing passes in place
+// of the mesh's own colours.  Unlit draws run none of it.
 #include "nr_tri.h"
 
 #include <hipcub/hipcub.hpp>
@@ -58,6 +65,10 @@ struct Mesh {
     f64* pos = nullptr;            // nv*3
     u32* idx = nullptr;            // n*3, every entry < nv (checked on the host at creation)
     f64* attr = nullptr;           // expanded: n*12 Gouraud, n*4 flat (the colour of i0), n*6 textured
+    // a lit mesh (CreateLitMesh) also keeps what the light pass reads: the per-vertex colours and normals
+    bool lit = false;
+    f64* rgba = nullptr;           // nv*4 (with n > 0)
+    f64* normal = nullptr;         // nv*3
 };
 
 namespace nrtri {
@@ -511,6 +522,161 @@ __global__ __launch_bounds__(256) void k_minst_clip_emit(const u32* __restrict__
                               (i64)off[g], xy, z, oattr, oq);
 }
 
+// ---- vertex lighting (DESIGN.md §3 "Vertex lighting") ---------------------------
+// A lit draw's first pass: per vertex, the normal under the row-major 3x3 normal
+// matrix, the ambient plus every light's clamped dot product times its colour,
+// and the base colour times that sum, clamped to [0, 1]; alpha is copied.  f64,
+// every product and sum rounded in the order written; no sqrt, no division:
+//   wx = (N[0]*nx + N[1]*ny) + N[2]*nz                      wy: row 1, wz: row 2
+//   acc_c = A_c;  per light in order:  dot = (wx*dx + wy*dy) + wz*dz
+//                                      d = dot > 0 ? dot : 0.0    (a NaN dot: 0)
+//                                      acc_c = acc_c + d * c_c
+//   p_c = base_c * acc_c;  lit_c = p_c < 0 ? 0.0 : (p_c > 1 ? 1.0 : p_c)   (a NaN p stays NaN)
+// The output is the draw's vertex-colour table (two 16-byte words per vertex) in
+// the context's staging; the assembly and clip passes read it through the indices
+// where an unlit draw reads the mesh's expanded attributes.
+struct Mat3 { f64 m[9]; };
+
+__device__ __forceinline__ f64 clamp01(f64 p) { return p < 0 ? 0.0 : (p > 1 ? 1.0 : p); }
+
+// The lights are uniform kernel arguments: the loop is unrolled to its bound, so
+// every light is read at a constant offset and a draw with nl lights leaves after nl.
+__device__ __forceinline__ void light_vertex(const Mat3& N, const MeshLights& L, f64 nx, f64 ny, f64 nz, double2 rg,
+                                             double2 ba, double2* __restrict__ out) {
+    const f64 wx = (N.m[0] * nx + N.m[1] * ny) + N.m[2] * nz;
+    const f64 wy = (N.m[3] * nx + N.m[4] * ny) + N.m[5] * nz;
+    const f64 wz = (N.m[6] * nx + N.m[7] * ny) + N.m[8] * nz;
+    f64 ar = L.ambient[0], ag = L.ambient[1], ab = L.ambient[2];
+#pragma unroll
+    for (int l = 0; l < MESH_MAX_LIGHTS; ++l) {
+        if (l >= L.nl) break;
+        const f64 dot = (wx * L.light[l][0] + wy * L.light[l][1]) + wz * L.light[l][2];
+        const f64 d = dot > 0 ? dot : 0.0;
+        ar = ar + d * L.light[l][3];
+        ag = ag + d * L.light[l][4];
+        ab = ab + d * L.light[l][5];
+    }
+    out[0] = make_double2(clamp01(rg.x * ar), clamp01(rg.y * ag));
+    out[1] = make_double2(clamp01(ba.x * ab), ba.y);
+}
+
+// One thread per vertex: 24 B of normal and 32 B of colour in, 32 B out.
+__global__ __launch_bounds__(256) void k_mesh_light(const f64* __restrict__ normal, const double2* __restrict__ rgba,
+                                                    i64 nv, Mat3 N, MeshLights L, double2* __restrict__ lit) {
+    const i64 v = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (v >= nv) return;
+    light_vertex(N, L, normal[v * 3], normal[v * 3 + 1], normal[v * 3 + 2], rgba[v * 2], rgba[v * 2 + 1], lit + v * 2);
+}
+
+// One thread per (instance, vertex), g = k * nv + v: instance k's normal matrix is
+// loaded per lane like its 4x4 matrix (inst_matrix); nmats null: the identity for
+// every instance, through the same arithmetic.
+__global__ __launch_bounds__(256) void k_minst_light(const f64* __restrict__ normal, const double2* __restrict__ rgba,
+                                                     u32 nv, u32 total, const f64* __restrict__ nmats, MeshLights L,
+                                                     double2* __restrict__ lit) {
+    const u32 g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= total) return;
+    const InstOf in = inst_of(g, nv);
+    Mat3 N = {{1, 0, 0, 0, 1, 0, 0, 0, 1}};
+    if (nmats) {
+        const f64* p = nmats + (size_t)in.k * 9;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) N.m[j] = p[j];
+    }
+    const size_t v = in.r;
+    light_vertex(N, L, normal[v * 3], normal[v * 3 + 1], normal[v * 3 + 2], rgba[v * 2], rgba[v * 2 + 1],
+                 lit + (size_t)g * 2);
+}
+
+// Pass 2 of an unclipped lit draw: k_mesh_assemble's gather, and the soup's
+// attributes from the colour table in k_minst_assemble's shape -- H = 2: a
+// Gouraud corner's two words; H = 0: a flat triangle's two words, the lit colour
+// of its first index, written by its corners 0 and 1.
+template <int H>
+__global__ __launch_bounds__(256) void k_mesh_lit_assemble(const u32* __restrict__ idx, i64 ncorner,
+                                                           const double2* __restrict__ vxy, const f64* __restrict__ vz,
+                                                           const double2* __restrict__ lit, double2* __restrict__ xy,
+                                                           f64* __restrict__ z, double2* __restrict__ oattr) {
+    const i64 c = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (c >= ncorner) return;
+    const u32 i = idx[c];
+    xy[c] = vxy[i];
+    z[c] = vz[i];
+    if constexpr (H == 0) {
+        const i64 t = c / 3, w = c - t * 3;
+        if (w < 2) oattr[t * 2 + w] = lit[(i64)idx[t * 3] * 2 + w];
+    } else {
+        oattr[c * 2] = lit[(i64)i * 2];
+        oattr[c * 2 + 1] = lit[(i64)i * 2 + 1];
+    }
+}
+
+// The same for an instanced lit draw: k_minst_assemble with instance k's part of
+// the colour table in place of the mesh's expanded attributes.
+template <int H, bool TINT>
+__global__ __launch_bounds__(256) void k_minst_lit_assemble(const u32* __restrict__ idx, u32 per, u32 total, u32 nv,
+                                                            const double2* __restrict__ vxy, const f64* __restrict__ vz,
+                                                            const double2* __restrict__ lit, const f64* __restrict__ tint,
+                                                            double2* __restrict__ xy, f64* __restrict__ z,
+                                                            double2* __restrict__ oattr) {
+    const u32 c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= total) return;
+    const InstOf in = inst_of(c, per);
+    const size_t base = (size_t)in.k * nv, i = base + idx[in.r];
+    xy[c] = vxy[i];
+    z[c] = vz[i];
+    const f64* tk = tint + (size_t)in.k * 4;   // (TINT only)
+    if constexpr (H == 0) {
+        const u32 t = in.r / 3u, w = in.r - t * 3u;
+        if (w < 2u) {
+            double2 a = lit[(base + idx[t * 3u]) * 2 + w];
+            if constexpr (TINT) a = make_double2(a.x * tk[2 * w], a.y * tk[2 * w + 1]);
+            oattr[(size_t)(c / 3u) * 2 + w] = a;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            double2 a = lit[i * 2 + j];
+            if constexpr (TINT) a = make_double2(a.x * tk[2 * j], a.y * tk[2 * j + 1]);
+            oattr[(size_t)c * 2 + j] = a;
+        }
+    }
+}
+
+// A clipped instanced lit draw: k_mesh_attr per instance -- the colour table
+// through the indices into per-triangle attributes, instance k's at k * n
+// triangles (perTri = 3: one thread per batch corner; 1: per batch triangle, i0).
+__global__ __launch_bounds__(256) void k_minst_lit_attr(const u32* __restrict__ idx, u32 per, u32 total, u32 nv,
+                                                        int perTri, const double2* __restrict__ lit,
+                                                        double2* __restrict__ out) {
+    const u32 g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= total) return;
+    const InstOf in = inst_of(g, per);
+    const size_t i = (size_t)in.k * nv + idx[perTri == 3 ? in.r : in.r * 3u];
+    out[(size_t)g * 2] = lit[i * 2];
+    out[(size_t)g * 2 + 1] = lit[i * 2 + 1];
+}
+
+// ... and its emit pass: k_minst_clip_emit reading instance k's own attributes
+// (W 16-byte words per triangle: 6 Gouraud, 2 flat).
+template <int H, bool TINT>
+__global__ __launch_bounds__(256) void k_minst_lit_clip_emit(const u32* __restrict__ idx, u32 n, u32 total, u32 nv,
+                                                             const double2* __restrict__ clip,
+                                                             const double2* __restrict__ attr,
+                                                             const f64* __restrict__ tint, f64 wNear,
+                                                             const u32* __restrict__ keep, const u32* __restrict__ off,
+                                                             double2* __restrict__ xy, f64* __restrict__ z,
+                                                             double2* __restrict__ oattr) {
+    constexpr size_t W = H == 0 ? 2 : 3 * H;
+    const u32 g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= total) return;
+    const u32 k = keep[g];
+    if (k == 0) return;
+    const InstOf in = inst_of(g, n);
+    clip_emit_tri<H, false, TINT>(idx, clip + (size_t)in.k * nv * 2, attr + (size_t)in.k * n * W,
+                                  tint + (size_t)in.k * 4, wNear, (i64)in.r, k, (i64)off[g], xy, z, oattr, nullptr);
+}
+
 unsigned blocks_for(i64 threads) { return (unsigned)((threads + 255) / 256); }
 
 bool fail(const char* what, const char* why) {
@@ -519,8 +685,9 @@ bool fail(const char* what, const char* why) {
 }
 
 // uv: texel coordinates nv*2 (a textured mesh) or null (rgba nv*4, flat or Gouraud)
+// normal: nv*3, a lit colour mesh (the per-vertex colours stay on the device beside it), or null
 Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* idx, const f64* rgba, bool gouraud,
-                  const f64* uv) {
+                  const f64* uv, const f64* normal = nullptr) {
     const f64* vattr = uv ? uv : rgba;
     const char* why = nullptr;
     if (nv < 0 || n < 0) why = "negative count";
@@ -540,6 +707,7 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
     m->nv = nv;
     m->n = n;
     m->mode = uv ? nrtri::ATTR_TEX : (gouraud ? nrtri::ATTR_GOURAUD : nrtri::ATTR_FLAT);
+    m->lit = normal != nullptr;
     NR_CHECK(hipGetDevice(&m->device));
     if (!uv && n > 0) {
         m->opaque = true;
@@ -551,6 +719,7 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
     const int w2 = uv ? 1 : 2;   // 16-byte words per vertex attribute
     f64* dv = nullptr;           // the per-vertex attributes, on the device until expanded
     bool ok = hipMalloc(&m->pos, (size_t)nv * 3 * sizeof(f64)) == hipSuccess;
+    if (ok && normal) ok = hipMalloc(&m->normal, (size_t)nv * 3 * sizeof(f64)) == hipSuccess;
     if (ok && n > 0) {
         ok = hipMalloc(&m->idx, (size_t)n * 3 * sizeof(u32)) == hipSuccess &&
              hipMalloc(&m->attr, (size_t)n * nrtri::attr_stride(m->mode) * sizeof(f64)) == hipSuccess &&
@@ -563,10 +732,12 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
         if (m->pos) NR_CHECK(hipFree(m->pos));
         if (m->idx) NR_CHECK(hipFree(m->idx));
         if (m->attr) NR_CHECK(hipFree(m->attr));
+        if (m->normal) NR_CHECK(hipFree(m->normal));
         delete m;
         return nullptr;
     }
     NR_CHECK(hipMemcpyAsync(m->pos, pos, (size_t)nv * 3 * sizeof(f64), hipMemcpyHostToDevice, s));
+    if (normal) NR_CHECK(hipMemcpyAsync(m->normal, normal, (size_t)nv * 3 * sizeof(f64), hipMemcpyHostToDevice, s));
     if (n > 0) {
         NR_CHECK(hipMemcpyAsync(m->idx, idx, (size_t)n * 3 * sizeof(u32), hipMemcpyHostToDevice, s));
         NR_CHECK(hipMemcpyAsync(dv, vattr, (size_t)nv * w2 * 2 * sizeof(f64), hipMemcpyHostToDevice, s));
@@ -577,7 +748,8 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
         NR_CHECK(hipGetLastError());
     }
     NR_CHECK(hipStreamSynchronize(s));   // caller may reuse its arrays on return
-    if (dv) NR_CHECK(hipFree(dv));
+    if (normal) m->rgba = dv;            // (a lit mesh keeps them)
+    else if (dv) NR_CHECK(hipFree(dv));
     return m;
 }
 
@@ -622,6 +794,59 @@ bool assemble(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out, b
     return true;
 }
 
+// `normal9`, or the identity for null.
+Mat3 mat3_of(const f64* normal9) {
+    Mat3 N = {{1, 0, 0, 0, 1, 0, 0, 0, 1}};
+    if (normal9)
+        for (int k = 0; k < 9; ++k) N.m[k] = normal9[k];
+    return N;
+}
+
+// The light pass of a single lit draw of `m` under the context's lights, as they are now, into `table` (nv*4).
+void light_pass(RenderContext* ctx, const Mesh* m, const Mat3& N, f64* table) {
+    hipEvent_t a, b;
+    nr_timing_begin(ctx, NRK_MESH_LIGHT, &a, &b);
+    hipLaunchKernelGGL(k_mesh_light, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->normal,
+                       reinterpret_cast<const double2*>(m->rgba), m->nv, N, ctx->meshLights,
+                       reinterpret_cast<double2*>(table));
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_LIGHT, a, b);
+}
+
+// assemble() for a lit colour mesh (m->lit, m->n > 0): the light pass beside the vertex stage, then the assembly
+// gathering the soup's attributes from the colour table -- vertices | table nv*4 | xy n*6 | z n*3 (padded to an
+// even count) | attributes n*stride, all in ctx's mesh staging.
+bool assemble_lit(RenderContext* ctx, const Mesh* m, const f64* matrix, const Mat3& N, Soup* out) {
+    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
+    TriScratch& sc = ctx->tri;
+    const size_t nv = (size_t)m->nv, n = (size_t)m->n;
+    const size_t vzn = (nv + 1) & ~(size_t)1, zn = (n * 3 + 1) & ~(size_t)1;   // keep the table, xy and the attributes 16-byte aligned
+    const size_t stride = (size_t)nrtri::attr_stride(m->mode);
+    if (!sc.mstage.ensure(nv * 2 + vzn + nv * 4 + n * 6 + zn + n * stride)) return false;
+    f64* vxy = sc.mstage;
+    f64* vz = vxy + nv * 2;
+    f64* table = vz + vzn;
+    f64* xy = table + nv * 4;
+    f64* z = xy + n * 6;
+    f64* attr = z + zn;
+    hipEvent_t a, b;
+    nr_timing_begin(ctx, NRK_MESH_VERTEX, &a, &b);
+    hipLaunchKernelGGL(k_mesh_vertex<false>, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv,
+                       mat4_of(matrix), reinterpret_cast<double2*>(vxy), vz, nullptr);
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_VERTEX, a, b);
+    light_pass(ctx, m, N, table);
+    const auto gather = m->mode == nrtri::ATTR_GOURAUD ? k_mesh_lit_assemble<2> : k_mesh_lit_assemble<0>;
+    nr_timing_begin(ctx, NRK_MESH_ASSEMBLE, &a, &b);
+    hipLaunchKernelGGL(gather, dim3(blocks_for(m->n * 3)), dim3(256), 0, ctx->stream, m->idx, m->n * 3,
+                       reinterpret_cast<const double2*>(vxy), vz, reinterpret_cast<const double2*>(table),
+                       reinterpret_cast<double2*>(xy), z, reinterpret_cast<double2*>(attr));
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_ASSEMBLE, a, b);
+    *out = Soup{xy, z, attr, nullptr, m->n};
+    return true;
+}
+
 // A textured mesh drawn with the context's perspective state on; colour meshes ignore the state.
 inline bool persp_draw(const RenderContext* ctx, const Mesh* m) { return ctx->meshPersp && m->mode == ATTR_TEX; }
 
@@ -632,7 +857,11 @@ inline bool clip_stage_on(const RenderContext* ctx) { return ctx->meshNear > 0 |
 // the total n_out has been read back, the one wait of such a draw -- the emit
 // pass into ctx's mesh staging, sized to n_out.  out->n == 0: nothing is left
 // to draw (no staging is touched).  False: scratch could not be grown (latched).
-bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out, bool persp) {
+// lit (a lit colour mesh under that normal matrix, else null): the light pass and k_mesh_attr's expansion of its
+// colour table run before the emit pass, behind the soup in the staging, and the emit pass reads that expansion
+// where it reads the mesh's own attributes otherwise.
+bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out, bool persp,
+                      const Mat3* lit = nullptr) {
     if (m->n > (i64)INT_MAX) return fail("mesh clip stage", "more than 2^31 - 1 triangles");
     nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
     TriScratch& sc = ctx->tri;
@@ -672,18 +901,33 @@ bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup
     if (nout > 2 * n) return fail("mesh clip stage", "inconsistent triangle count");   // (never: the counts are 0, 1 or 2)
     const size_t stride = (size_t)nrtri::attr_stride(m->mode);
     const size_t zn = (nout * 3 + 1) & ~(size_t)1;   // keeps the attributes 16-byte aligned
-    if (!sc.mstage.ensure(nout * 6 + zn + nout * stride + (persp ? nout * 3 : 0))) return false;
+    const size_t soup = nout * 6 + zn + nout * stride + (persp ? nout * 3 : 0);   // (a lit draw has no q: even, what follows stays 16-byte aligned)
+    if (!sc.mstage.ensure(soup + (lit ? nv * 4 + n * stride : 0))) return false;
     f64* xy = sc.mstage;
     f64* z = xy + nout * 6;
     f64* attr = z + zn;
     f64* q = persp ? attr + nout * stride : nullptr;
+    const f64* src = m->attr;
+    if (lit) {
+        f64* table = xy + soup;
+        f64* expanded = table + nv * 4;
+        light_pass(ctx, m, *lit, table);
+        const int perTri = m->mode == nrtri::ATTR_FLAT ? 1 : 3;
+        nr_timing_begin(ctx, NRK_MESH_LIT_ATTR, &a, &b);
+        hipLaunchKernelGGL(k_mesh_attr, dim3(blocks_for(m->n * perTri)), dim3(256), 0, ctx->stream, m->idx,
+                           m->n * perTri, perTri, 2, reinterpret_cast<const double2*>(table),
+                           reinterpret_cast<double2*>(expanded));
+        NR_CHECK(hipGetLastError());
+        nr_timing_end(ctx, NRK_MESH_LIT_ATTR, a, b);
+        src = expanded;
+    }
     const auto emit = m->mode == nrtri::ATTR_GOURAUD ? k_mesh_clip_emit<2>
                       : m->mode != nrtri::ATTR_TEX   ? k_mesh_clip_emit<0>
                       : persp                        ? k_mesh_clip_emit<1, true>
                                                      : k_mesh_clip_emit<1>;
     nr_timing_begin(ctx, NRK_MESH_CLIP_EMIT, &a, &b);
     hipLaunchKernelGGL(emit, dim3(blocks_for(m->n)), dim3(256), 0, ctx->stream, m->idx, m->n, clip,
-                       reinterpret_cast<const double2*>(m->attr), wNear, keep, off, reinterpret_cast<double2*>(xy), z,
+                       reinterpret_cast<const double2*>(src), wNear, keep, off, reinterpret_cast<double2*>(xy), z,
                        reinterpret_cast<double2*>(attr), q);
     NR_CHECK(hipGetLastError());
     nr_timing_end(ctx, NRK_MESH_CLIP_EMIT, a, b);
@@ -699,8 +943,9 @@ bool draw_soup(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out) 
 }
 
 // ---- instanced draws: host side ---------------------------------------------------
-// The K matrices (K*16) and tints (K*4, or null) of an instanced draw, on the device.
-struct Instances { const f64* mats; const f64* tint; i64 K; };
+// The K matrices (K*16) and tints (K*4, or null) of an instanced draw, on the device; a lit draw's normal
+// matrices (K*9, or null: the identity for every instance).
+struct Instances { const f64* mats; const f64* tint; i64 K; const f64* normals = nullptr; };
 bool check_mesh(RenderContext* ctx, const Mesh* m, bool textured, const char* what);
 
 // The argument checks every instanced entry point shares, after the mesh's own: false with an error latched under
@@ -723,10 +968,12 @@ bool check_instances(const RenderContext* ctx, const Mesh* m, const f64* matrice
 // one asynchronous copy: the caller's arrays are free when this returns and the host waits for nothing but an
 // earlier such copy (of the draw before last), long done.  (The copy-and-wait of DrawTriangles' staging would add a host wait to every
 // draw, which is what an instanced draw is there to avoid.)  Settles first: minst follows mstage's rule.
-bool upload_instances(RenderContext* ctx, const f64* matrices, const f64* tint, i64 K, Instances* out) {
+// normals (a lit draw's, or null) travel behind the tints in the same copy.
+bool upload_instances(RenderContext* ctx, const f64* matrices, const f64* tint, i64 K, Instances* out,
+                      const f64* normals = nullptr) {
     nrtri::settle(ctx);
     TriScratch& sc = ctx->tri;
-    const size_t k = (size_t)K, need = k * (tint ? 20 : 16);
+    const size_t k = (size_t)K, ntint = tint ? k * 4 : 0, need = k * 16 + ntint + (normals ? k * 9 : 0);
     if (!sc.minst.ensure(need)) return false;
     const int slot = sc.minstNext;   // two pinned buffers in turn: the wait is for the copy of the draw before last
     sc.minstNext ^= 1;
@@ -746,9 +993,11 @@ bool upload_instances(RenderContext* ctx, const f64* matrices, const f64* tint, 
     f64* h = sc.h_minst[slot];
     std::memcpy(h, matrices, k * 16 * sizeof(f64));
     if (tint) std::memcpy(h + k * 16, tint, k * 4 * sizeof(f64));
+    if (normals) std::memcpy(h + k * 16 + ntint, normals, k * 9 * sizeof(f64));
     NR_CHECK(hipMemcpyAsync(sc.minst.p, h, need * sizeof(f64), hipMemcpyHostToDevice, ctx->stream));
     NR_CHECK(hipEventRecord(sc.evMinst[slot], ctx->stream));
-    *out = Instances{sc.minst.p, tint ? sc.minst.p + k * 16 : nullptr, K};
+    *out = Instances{sc.minst.p, tint ? sc.minst.p + k * 16 : nullptr, K,
+                     normals ? sc.minst.p + k * 16 + ntint : nullptr};
     return true;
 }
 
@@ -792,9 +1041,60 @@ bool assemble_instanced(RenderContext* ctx, const Mesh* m, const Instances& in, 
     return true;
 }
 
+// The light pass of an instanced lit draw: the colour table of all K*nv (instance, vertex) pairs.
+void light_pass_instanced(RenderContext* ctx, const Mesh* m, const Instances& in, f64* table) {
+    const size_t NV = (size_t)in.K * (size_t)m->nv;
+    hipEvent_t a, b;
+    nr_timing_begin(ctx, NRK_MESH_INST_LIGHT, &a, &b);
+    hipLaunchKernelGGL(k_minst_light, dim3(blocks_for((i64)NV)), dim3(256), 0, ctx->stream, m->normal,
+                       reinterpret_cast<const double2*>(m->rgba), (u32)m->nv, (u32)NV, in.normals, ctx->meshLights,
+                       reinterpret_cast<double2*>(table));
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_INST_LIGHT, a, b);
+}
+
+// assemble_instanced() for a lit colour mesh: the colour table K*nv*4 behind the vertex table, and the assembly
+// gathering instance k's attributes from its part of it.
+bool assemble_instanced_lit(RenderContext* ctx, const Mesh* m, const Instances& in, Soup* out) {
+    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
+    TriScratch& sc = ctx->tri;
+    const size_t NV = (size_t)in.K * (size_t)m->nv, N = (size_t)in.K * (size_t)m->n;
+    const size_t vzn = (NV + 1) & ~(size_t)1, zn = (N * 3 + 1) & ~(size_t)1;   // keep the table, xy and the attributes 16-byte aligned
+    const size_t stride = (size_t)nrtri::attr_stride(m->mode);
+    if (!sc.mstage.ensure(NV * 2 + vzn + NV * 4 + N * 6 + zn + N * stride)) return false;
+    f64* vxy = sc.mstage;
+    f64* vz = vxy + NV * 2;
+    f64* table = vz + vzn;
+    f64* xy = table + NV * 4;
+    f64* z = xy + N * 6;
+    f64* attr = z + zn;
+    const bool tint = in.tint != nullptr;
+    const auto gather = m->mode == nrtri::ATTR_GOURAUD ? (tint ? k_minst_lit_assemble<2, true> : k_minst_lit_assemble<2, false>)
+                                                       : (tint ? k_minst_lit_assemble<0, true> : k_minst_lit_assemble<0, false>);
+    hipEvent_t a, b;
+    nr_timing_begin(ctx, NRK_MESH_INST_VERTEX, &a, &b);
+    hipLaunchKernelGGL(k_minst_vertex<false>, dim3(blocks_for((i64)NV)), dim3(256), 0, ctx->stream, m->pos, (u32)m->nv,
+                       (u32)NV, in.mats, reinterpret_cast<double2*>(vxy), vz, nullptr);
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_INST_VERTEX, a, b);
+    light_pass_instanced(ctx, m, in, table);
+    nr_timing_begin(ctx, NRK_MESH_INST_ASSEMBLE, &a, &b);
+    hipLaunchKernelGGL(gather, dim3(blocks_for((i64)N * 3)), dim3(256), 0, ctx->stream, m->idx, (u32)(m->n * 3),
+                       (u32)(N * 3), (u32)m->nv, reinterpret_cast<const double2*>(vxy), vz,
+                       reinterpret_cast<const double2*>(table), in.tint, reinterpret_cast<double2*>(xy), z,
+                       reinterpret_cast<double2*>(attr));
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_INST_ASSEMBLE, a, b);
+    *out = Soup{xy, z, attr, nullptr, (i64)N};
+    return true;
+}
+
 // assemble_clipped() for K instances: the count, the scan and the emit run once over all K*n triangles, with one
 // read-back of the total, so the instances' clipped soups follow each other in instance order.
-bool assemble_instanced_clipped(RenderContext* ctx, const Mesh* m, const Instances& in, Soup* out, bool persp) {
+// lit (a lit colour mesh): as in assemble_clipped -- the light pass and the expansion of the colour table, K*n
+// triangles' worth, behind the soup; the emit pass is then the one that reads instance k's own attributes.
+bool assemble_instanced_clipped(RenderContext* ctx, const Mesh* m, const Instances& in, Soup* out, bool persp,
+                                bool lit = false) {
     nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
     TriScratch& sc = ctx->tri;
     const size_t NV = (size_t)in.K * (size_t)m->nv, N = (size_t)in.K * (size_t)m->n;
@@ -834,12 +1134,35 @@ bool assemble_instanced_clipped(RenderContext* ctx, const Mesh* m, const Instanc
     if (nout > 2 * N) return fail("mesh clip stage", "inconsistent triangle count");   // (never: the counts are 0, 1 or 2)
     const size_t stride = (size_t)nrtri::attr_stride(m->mode);
     const size_t zn = (nout * 3 + 1) & ~(size_t)1;   // keeps the attributes 16-byte aligned
-    if (!sc.mstage.ensure(nout * 6 + zn + nout * stride + (persp ? nout * 3 : 0))) return false;
+    const size_t soup = nout * 6 + zn + nout * stride + (persp ? nout * 3 : 0);   // (a lit draw has no q: even)
+    if (!sc.mstage.ensure(soup + (lit ? NV * 4 + N * stride : 0))) return false;
     f64* xy = sc.mstage;
     f64* z = xy + nout * 6;
     f64* attr = z + zn;
     f64* q = persp ? attr + nout * stride : nullptr;
     const bool tint = in.tint != nullptr;
+    if (lit) {
+        f64* table = xy + soup;
+        f64* expanded = table + NV * 4;
+        light_pass_instanced(ctx, m, in, table);
+        const int perTri = m->mode == nrtri::ATTR_FLAT ? 1 : 3;
+        nr_timing_begin(ctx, NRK_MESH_INST_LIT_ATTR, &a, &b);
+        hipLaunchKernelGGL(k_minst_lit_attr, dim3(blocks_for((i64)N * perTri)), dim3(256), 0, ctx->stream, m->idx,
+                           n * (u32)perTri, (u32)(N * perTri), nv, perTri, reinterpret_cast<const double2*>(table),
+                           reinterpret_cast<double2*>(expanded));
+        NR_CHECK(hipGetLastError());
+        nr_timing_end(ctx, NRK_MESH_INST_LIT_ATTR, a, b);
+        const auto lemit = m->mode == nrtri::ATTR_GOURAUD ? (tint ? k_minst_lit_clip_emit<2, true> : k_minst_lit_clip_emit<2, false>)
+                                                          : (tint ? k_minst_lit_clip_emit<0, true> : k_minst_lit_clip_emit<0, false>);
+        nr_timing_begin(ctx, NRK_MESH_INST_CLIP_EMIT, &a, &b);
+        hipLaunchKernelGGL(lemit, dim3(blocks_for((i64)N)), dim3(256), 0, ctx->stream, m->idx, n, (u32)N, nv, clip,
+                           reinterpret_cast<const double2*>(expanded), in.tint, wNear, keep, off,
+                           reinterpret_cast<double2*>(xy), z, reinterpret_cast<double2*>(attr));
+        NR_CHECK(hipGetLastError());
+        nr_timing_end(ctx, NRK_MESH_INST_CLIP_EMIT, a, b);
+        *out = Soup{xy, z, attr, nullptr, (i64)nout};
+        return true;
+    }
     const auto emit = m->mode == nrtri::ATTR_GOURAUD ? (tint ? k_minst_clip_emit<2, false, true> : k_minst_clip_emit<2, false, false>)
                       : m->mode != nrtri::ATTR_TEX   ? (tint ? k_minst_clip_emit<0, false, true> : k_minst_clip_emit<0, false, false>)
                       : persp                        ? k_minst_clip_emit<1, true, false>
@@ -854,28 +1177,37 @@ bool assemble_instanced_clipped(RenderContext* ctx, const Mesh* m, const Instanc
     return true;
 }
 
-// The soup an instanced draw rasterises under the context's clip and perspective state.
-bool instanced_soup(RenderContext* ctx, const Mesh* m, const Instances& in, Soup* out) {
+// The soup an instanced draw rasterises under the context's clip and perspective state; lit: a lit draw's,
+// also under the context's lights.
+bool instanced_soup(RenderContext* ctx, const Mesh* m, const Instances& in, Soup* out, bool lit = false) {
     const bool persp = persp_draw(ctx, m);
+    if (lit) return clip_stage_on(ctx) ? assemble_instanced_clipped(ctx, m, in, out, false, true)
+                                       : assemble_instanced_lit(ctx, m, in, out);
     return clip_stage_on(ctx) ? assemble_instanced_clipped(ctx, m, in, out, persp)
                               : assemble_instanced(ctx, m, in, out, persp);
 }
 
-// The four instanced draw entry points under the caller's name `what`.  onDevice: matrices and tint are device
-// arrays, read only by the vertex and assembly kernels launched here; the batch reads the context's staging.
+// What a *Lit call needs of its mesh, after check_mesh(textured = false).
+bool check_lit(const Mesh* m, const char* what) {
+    return m->lit ? true : fail(what, "a mesh without normals (create it with CreateLitMesh)");
+}
+
+// The instanced draw entry points under the caller's name `what`.  onDevice: matrices, tint and normals are device
+// arrays, read only by the vertex, light and assembly kernels launched here; the batch reads the context's staging.
+// lit: a lit draw (a colour mesh with normals), `normals` its K*9 normal matrices or null.
 void draw_instanced(RenderContext* ctx, Mesh* m, Texture* tex, bool textured, const f64* matrices, const f64* tint,
-                    i64 K, bool onDevice, const char* what) {
+                    i64 K, bool onDevice, const char* what, bool lit = false, const f64* normals = nullptr) {
     NR_CHECK(hipSetDevice(ctx->device));
     ctx->meshLastCount = 0;
-    if (!check_mesh(ctx, m, textured, what)) return;
+    if (!check_mesh(ctx, m, textured, what) || (lit && !check_lit(m, what))) return;
     if (ctx->recording) nr_settle(ctx);   // recorded draws come first
     if (textured && !nrtri::check_texture(ctx, tex, what)) return;
     bool empty;
     if (!check_instances(ctx, m, matrices, tint, K, true, &empty, what) || empty) return;
-    Instances in{matrices, tint, K};
-    if (!onDevice && !upload_instances(ctx, matrices, tint, K, &in)) return;
+    Instances in{matrices, tint, K, normals};
+    if (!onDevice && !upload_instances(ctx, matrices, tint, K, &in, normals)) return;
     Soup s;
-    if (!instanced_soup(ctx, m, in, &s)) return;
+    if (!instanced_soup(ctx, m, in, &s, lit)) return;
     ctx->meshLastCount = s.n;
     if (s.n <= 0) return;   // (clipped or culled away)
     if (textured) {
@@ -968,6 +1300,8 @@ void DestroyMesh(Mesh* m) {
     if (m->pos) NR_CHECK(hipFree(m->pos));
     if (m->idx) NR_CHECK(hipFree(m->idx));
     if (m->attr) NR_CHECK(hipFree(m->attr));
+    if (m->rgba) NR_CHECK(hipFree(m->rgba));
+    if (m->normal) NR_CHECK(hipFree(m->normal));
     NR_CHECK(hipSetDevice(prev));
     delete m;
 }
@@ -1159,6 +1493,129 @@ bool AssembleMeshInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, con
     const size_t k = (size_t)(s.n < cap ? s.n : cap);
     copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {attr_out, s.attr, (size_t)nrtri::attr_stride(m->mode)},
                       {q_out, s.q, 3}});
+    return true;
+}
+
+// ---- lit meshes (DESIGN.md §3 "Vertex lighting") ---------------------------------------------------------------
+// New: CreateMesh with per-vertex normals (nv*3): the mesh keeps them and its per-vertex colours on the device for
+// the light pass of the *Lit draws.  CreateMesh's checks, and NULL normals with nv > 0.  DrawMesh and
+// DrawMeshInstanced draw such a mesh unlit, from its expanded colours.
+Mesh* CreateLitMesh(i64 nv, const f64* pos, const f64* normal, i64 n, const uint32_t* idx, const f64* rgba,
+                    bool gouraud) {
+    if (!normal && nv > 0) {
+        fail("CreateLitMesh", "NULL normals");
+        return nullptr;
+    }
+    static const f64 none[3] = {0, 0, 0};
+    return create_mesh("CreateLitMesh", nv, pos, n, idx, rgba, gouraud, nullptr, normal ? normal : none);
+}
+
+// New: replaces the normals (nv*3) of a lit mesh; UpdateMeshPositions' contract.
+bool UpdateMeshNormals(Mesh* m, const f64* normal) {
+    if (!m) return fail("UpdateMeshNormals", "NULL mesh");
+    if (!m->lit) return fail("UpdateMeshNormals", "a mesh without normals (create it with CreateLitMesh)");
+    if (m->nv == 0) return true;
+    if (!normal) return fail("UpdateMeshNormals", "NULL normals");
+    int prev = 0;
+    NR_CHECK(hipGetDevice(&prev));
+    quiesce(m);
+    hipStream_t s = nr_stream_for(m->device);
+    NR_CHECK(hipMemcpyAsync(m->normal, normal, (size_t)m->nv * 3 * sizeof(f64), hipMemcpyHostToDevice, s));
+    NR_CHECK(hipStreamSynchronize(s));   // caller may reuse its array on return
+    NR_CHECK(hipSetDevice(prev));
+    return true;
+}
+
+bool GetMeshLit(Mesh* m) { return m->lit; }
+
+// New: the light state of this context's lit mesh draws: ambient3 (NULL: (1, 1, 1)) and nl directional lights
+// (dx, dy, dz, cr, cg, cb), nl*6, d towards the light in the space the normal matrix maps into.  Copied here; per
+// context, not part of the save / restore stack, not recorded; read when a draw is issued.  nl outside 0 .. 8 or
+// NULL lights with nl > 0 latch an error and leave the state unchanged.  The values are not validated.
+bool SetMeshLights(RenderContext* ctx, const f64* ambient3, const f64* lights, i64 nl) {
+    if (nl < 0 || nl > MESH_MAX_LIGHTS) return fail("SetMeshLights", "the light count must be 0 .. 8");
+    if (nl > 0 && !lights) return fail("SetMeshLights", "NULL lights");
+    MeshLights L;
+    if (ambient3)
+        for (int c = 0; c < 3; ++c) L.ambient[c] = ambient3[c];
+    for (i64 k = 0; k < nl * 6; ++k) L.light[k / 6][k % 6] = lights[k];
+    L.nl = (int)nl;
+    ctx->meshLights = L;
+    return true;
+}
+i64 GetMeshLightCount(RenderContext* ctx) { return ctx->meshLights.nl; }
+
+// New: DrawMesh of a lit mesh under the context's lights and the row-major 3x3 normal matrix `normal9` (NULL: the
+// identity): the light pass computes every vertex colour on the device, the rest of the draw is DrawMesh's.
+void DrawMeshLit(RenderContext* ctx, Mesh* m, const f64* matrix16, const f64* normal9) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    ctx->meshLastCount = 0;
+    if (!check_mesh(ctx, m, false, "DrawMeshLit") || !check_lit(m, "DrawMeshLit")) return;
+    if (ctx->recording) nr_settle(ctx);   // recorded draws come first
+    if (m->n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
+    const Mat3 N = mat3_of(normal9);
+    Soup s;
+    if (!(clip_stage_on(ctx) ? assemble_clipped(ctx, m, matrix16, &s, false, &N) : assemble_lit(ctx, m, matrix16, N, &s)))
+        return;
+    ctx->meshLastCount = s.n;
+    if (s.n <= 0) return;   // (clipped or culled away)
+    nrtri::draw(ctx, soup_batch(s, m->mode, m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED, nullptr, false));
+}
+
+// New: DrawMeshInstanced of a lit mesh: instance k under matrices[k] and the normal matrix normals[k] (K*9; NULL:
+// the identity for every instance); a tint multiplies the lit colours.  Host arrays, free again on return.
+void DrawMeshLitInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* normals, const f64* tint,
+                          i64 K) {
+    draw_instanced(ctx, m, nullptr, false, matrices, tint, K, false, "DrawMeshLitInstanced", true, normals);
+}
+
+// New: the same from device-resident matrices, normal matrices and tint (as DrawMeshInstancedDevice).
+void DrawMeshLitInstancedDevice(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* normals,
+                                const f64* tint, i64 K) {
+    draw_instanced(ctx, m, nullptr, false, matrices, tint, K, true, "DrawMeshLitInstancedDevice", true, normals);
+}
+
+// The mesh checks of the two lit Assemble calls, after check_assemble.
+static bool check_assemble_lit(const Mesh* m, const char* what) {
+    if (m->mode == nrtri::ATTR_TEX) return fail(what, "a textured mesh");
+    return check_lit(m, what);
+}
+
+// New: the soup a DrawMeshLit rasterises under the context's lights, near plane and cull mode -- the draw's own
+// kernels -- in AssembleMeshClipped's conventions (attr x12 Gouraud, x4 flat).  A sync point.
+bool AssembleMeshLit(RenderContext* ctx, Mesh* m, const f64* matrix16, const f64* normal9, i64 cap, f64* xy_out,
+                     f64* z_out, f64* attr_out, i64* n_out) {
+    const char* what = "AssembleMeshLit";
+    NR_CHECK(hipSetDevice(ctx->device));
+    if (!check_assemble(ctx, m, false, cap, xy_out && z_out && attr_out, n_out, what)) return false;
+    if (!check_assemble_lit(m, what)) return false;
+    if (m->n <= 0) return true;
+    const Mat3 N = mat3_of(normal9);
+    Soup s;
+    if (!(clip_stage_on(ctx) ? assemble_clipped(ctx, m, matrix16, &s, false, &N) : assemble_lit(ctx, m, matrix16, N, &s)))
+        return false;
+    *n_out = s.n;
+    const size_t k = (size_t)(s.n < cap ? s.n : cap);
+    copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {attr_out, s.attr, (size_t)nrtri::attr_stride(m->mode)}});
+    return true;
+}
+
+// New: the same for a DrawMeshLitInstanced (host arrays), in AssembleMeshInstanced's conventions without q.
+bool AssembleMeshLitInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* normals, const f64* tint,
+                              i64 K, i64 cap, f64* xy_out, f64* z_out, f64* attr_out, i64* n_out) {
+    const char* what = "AssembleMeshLitInstanced";
+    NR_CHECK(hipSetDevice(ctx->device));
+    if (!check_assemble(ctx, m, false, cap, xy_out && z_out && attr_out, n_out, what)) return false;
+    if (!check_assemble_lit(m, what)) return false;
+    bool empty;
+    if (!check_instances(ctx, m, matrices, tint, K, false, &empty, what)) return false;
+    if (empty) return true;
+    Instances in;
+    Soup s;
+    if (!upload_instances(ctx, matrices, tint, K, &in, normals) || !instanced_soup(ctx, m, in, &s, true)) return false;
+    *n_out = s.n;
+    const size_t k = (size_t)(s.n < cap ? s.n : cap);
+    copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {attr_out, s.attr, (size_t)nrtri::attr_stride(m->mode)}});
     return true;
 }
 

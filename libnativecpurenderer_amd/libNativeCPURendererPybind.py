@@ -535,6 +535,107 @@ class RenderContext:
         no = nout.value
         return xy[:no].copy(), z[:no].copy(), attr[:no].copy(), (None if q is None else q[:no].copy())
 
+    # lit mesh draws (DESIGN.md §3 "Vertex lighting"): per-vertex normals under
+    # this context's ambient colour and directional lights, computed on the
+    # device; the light state is per context, not saved / restored, not recorded
+    def set_mesh_lights(self, ambient=None, lights=None):
+        """ambient: (r, g, b) or None for (1, 1, 1); lights: up to 8 rows (dx,
+        dy, dz, cr, cg, cb), d pointing towards the light, or None for no
+        light.  More than 8 raises (the error stays latched) and leaves the
+        state unchanged."""
+        amb = None if ambient is None else np.ascontiguousarray(ambient, dtype=np.float64).reshape(3)
+        lt = np.zeros((0, 6)) if lights is None else np.ascontiguousarray(lights, dtype=np.float64).reshape(-1, 6)
+        nl = lt.shape[0]
+        if not lib.SetMeshLights(self._ptr, None if amb is None else _f64_ptr(amb), _f64_ptr(lt) if nl else None, nl):
+            raise RuntimeError("SetMeshLights failed: " + _lib.last_error())
+
+    def get_mesh_light_count(self) -> int:
+        return lib.GetMeshLightCount(self._ptr)
+
+    @staticmethod
+    def _lit_mesh(mesh):
+        if mesh.textured:
+            raise ValueError("a textured Mesh cannot be drawn lit")
+        if not mesh.lit:
+            raise ValueError("a lit draw needs a Mesh created with normals")
+
+    @staticmethod
+    def _lit_instances(mesh, matrices, normal_matrices, tint):
+        """(matrices (K, 16), normal matrices (K, 9) or None, tint (K, 4) or None), checked."""
+        RenderContext._lit_mesh(mesh)
+        matrices, tint = RenderContext._instances(mesh, matrices, None, tint)
+        if normal_matrices is not None:
+            normal_matrices = np.ascontiguousarray(normal_matrices, dtype=np.float64).reshape(-1, 9)
+            if normal_matrices.shape[0] != matrices.shape[0]:
+                raise ValueError("normal_matrices must hold one 3x3 per matrix")
+        return matrices, normal_matrices, tint
+
+    def draw_mesh_lit(self, mesh: "Mesh", matrix=None, normal_matrix=None):
+        """draw_mesh of a lit Mesh (Mesh(..., normals=...)) with its vertex
+        colours lit on the device under this context's lights; normal_matrix:
+        the row-major 3x3 that takes the normals into the lights' space (None:
+        the identity).  Normals are not renormalised."""
+        self._lit_mesh(mesh)
+        m, mp = self._matrix16(matrix)
+        nm = None if normal_matrix is None else np.ascontiguousarray(normal_matrix, dtype=np.float64).reshape(9)
+        lib.DrawMeshLit(self._ptr, mesh._ptr, mp, None if nm is None else _f64_ptr(nm))
+
+    def draw_mesh_lit_instanced(self, mesh: "Mesh", matrices, normal_matrices=None, tint=None):
+        """draw_mesh_instanced of a lit Mesh: instance k lit under
+        normal_matrices[k] ((K, 9) or (K, 3, 3); None: the identity), its lit
+        colours then times tint[k]."""
+        matrices, nrm, tint = self._lit_instances(mesh, matrices, normal_matrices, tint)
+        k = matrices.shape[0]
+        lib.DrawMeshLitInstanced(self._ptr, mesh._ptr, _f64_ptr(matrices) if k else None,
+                                 None if nrm is None else _f64_ptr(nrm), None if tint is None else _f64_ptr(tint), k)
+
+    def draw_mesh_lit_instanced_device(self, mesh: "Mesh", matrices, k: int, normal_matrices=None, tint=None):
+        """draw_mesh_lit_instanced with matrices (k*16 f64), normal matrices
+        (k*9) and tint (k*4) already in HBM, as for draw_mesh_instanced_device."""
+        self._lit_mesh(mesh)
+
+        def addr(a):
+            if a is None:
+                return None
+            return a.data_ptr() if hasattr(a, "data_ptr") else int(a)
+        lib.DrawMeshLitInstancedDevice(self._ptr, mesh._ptr, addr(matrices), addr(normal_matrices), addr(tint), int(k))
+
+    def assemble_mesh_lit(self, mesh: "Mesh", matrix=None, normal_matrix=None):
+        """(xy (n_out, 6), z (n_out, 3), attr (n_out, 12 Gouraud / 4 flat)):
+        the soup draw_mesh_lit would rasterise under this context's lights,
+        near plane and cull mode -- the draw's own kernels (a sync point)."""
+        self._lit_mesh(mesh)
+        m, mp = self._matrix16(matrix)
+        nm = None if normal_matrix is None else np.ascontiguousarray(normal_matrix, dtype=np.float64).reshape(9)
+        cap = 2 * mesh.triangle_count
+        xy = np.empty((cap, 6), dtype=np.float64)
+        z = np.empty((cap, 3), dtype=np.float64)
+        attr = np.empty((cap, 12 if mesh.gouraud else 4), dtype=np.float64)
+        nout = ctypes.c_long(0)
+        if not lib.AssembleMeshLit(self._ptr, mesh._ptr, mp, None if nm is None else _f64_ptr(nm), cap, _f64_ptr(xy),
+                                   _f64_ptr(z), _f64_ptr(attr), ctypes.byref(nout)):
+            raise RuntimeError("AssembleMeshLit failed: " + _lib.last_error())
+        k = nout.value
+        return xy[:k].copy(), z[:k].copy(), attr[:k].copy()
+
+    def assemble_mesh_lit_instanced(self, mesh: "Mesh", matrices, normal_matrices=None, tint=None):
+        """(xy (n_out, 6), z (n_out, 3), attr (n_out, 12 | 4)): the soup
+        draw_mesh_lit_instanced would rasterise (a sync point)."""
+        matrices, nrm, tint = self._lit_instances(mesh, matrices, normal_matrices, tint)
+        k = matrices.shape[0]
+        cap = 2 * k * mesh.triangle_count
+        xy = np.empty((cap, 6), dtype=np.float64)
+        z = np.empty((cap, 3), dtype=np.float64)
+        attr = np.empty((cap, 12 if mesh.gouraud else 4), dtype=np.float64)
+        nout = ctypes.c_long(0)
+        if not lib.AssembleMeshLitInstanced(self._ptr, mesh._ptr, _f64_ptr(matrices) if k else None,
+                                            None if nrm is None else _f64_ptr(nrm),
+                                            None if tint is None else _f64_ptr(tint), k, cap, _f64_ptr(xy), _f64_ptr(z),
+                                            _f64_ptr(attr), ctypes.byref(nout)):
+            raise RuntimeError("AssembleMeshLitInstanced failed: " + _lib.last_error())
+        no = nout.value
+        return xy[:no].copy(), z[:no].copy(), attr[:no].copy()
+
     # ---- additions: sync, device interop, measurement ------------------
     def flush(self):
         lib.Flush(self._ptr)
@@ -1145,13 +1246,17 @@ class Mesh:
     """Device-resident indexed mesh (new): vertices + indices uploaded once,
     drawn per frame under a 4x4 matrix (RenderContext.draw_mesh)."""
 
-    def __init__(self, positions, indices, colors=None, uv=None, gouraud: typing.Optional[bool] = None):
+    def __init__(self, positions, indices, colors=None, uv=None, gouraud: typing.Optional[bool] = None,
+                 normals=None):
         """positions: (nv, 3); indices: (n, 3) integers < nv (stored as
         uint32); exactly one of colors ((nv, 4) RGBA per vertex; gouraud
         (default) interpolates them, flat takes each triangle's first index)
-        and uv ((nv, 2) texel coordinates: a textured mesh)."""
+        and uv ((nv, 2) texel coordinates: a textured mesh).  normals ((nv, 3),
+        a colour mesh only): a lit mesh, for RenderContext.draw_mesh_lit."""
         if (colors is None) == (uv is None):
             raise ValueError("exactly one of colors and uv")
+        if normals is not None and uv is not None:
+            raise ValueError("a textured Mesh takes no normals")
         pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
         nv = pos.shape[0]
         ind = np.asarray(indices)
@@ -1169,8 +1274,18 @@ class Mesh:
         else:
             colors = np.ascontiguousarray(colors, dtype=np.float64).reshape(nv, 4)
             self.gouraud = True if gouraud is None else bool(gouraud)
-            self._ptr = _check(lib.CreateMesh(nv, _f64_ptr(pos), n, ip, _f64_ptr(colors), self.gouraud), "CreateMesh")
+            if normals is None:
+                self._ptr = _check(lib.CreateMesh(nv, _f64_ptr(pos), n, ip, _f64_ptr(colors), self.gouraud), "CreateMesh")
+            else:
+                nrm = np.ascontiguousarray(normals, dtype=np.float64).reshape(nv, 3)
+                self._ptr = _check(lib.CreateLitMesh(nv, _f64_ptr(pos), _f64_ptr(nrm), n, ip, _f64_ptr(colors),
+                                                     self.gouraud), "CreateLitMesh")
         self._can_release = True
+
+    @property
+    def lit(self) -> bool:
+        """Created with normals: what the draw_mesh_lit calls need."""
+        return bool(lib.GetMeshLit(self._ptr))
 
     @property
     def vertex_count(self) -> int:
@@ -1188,6 +1303,15 @@ class Mesh:
             raise ValueError("update_positions: the vertex count is fixed at creation")
         if not lib.UpdateMeshPositions(self._ptr, _f64_ptr(pos)):
             raise RuntimeError("UpdateMeshPositions failed: " + _lib.last_error())
+
+    def update_normals(self, normals):
+        """New normals (nv, 3) of a lit Mesh for the next draws; draws
+        already issued keep the old ones."""
+        nrm = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+        if nrm.shape[0] != self.vertex_count:
+            raise ValueError("update_normals: the vertex count is fixed at creation")
+        if not lib.UpdateMeshNormals(self._ptr, _f64_ptr(nrm)):
+            raise RuntimeError("UpdateMeshNormals failed: " + _lib.last_error())
 
     def __del__(self):
         if getattr(self, "_can_release", False):
