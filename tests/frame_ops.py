@@ -17,7 +17,11 @@ resources   dict made before the first operation:
             bufs    [("c", n, seed, spread, gouraud, blended) |
                      ("t", n, seed, spread, "const" | "free")]   TriangleBuffers
             meshes  [("c", space, rows, cols, seed, gouraud, blended) |
+                     ("l", space, rows, cols, seed, gouraud, blended) |
                      ("tu", space, n, seed, spread) | ("ts", space, rows, cols, seed)]
+                    "l": a lit colour mesh, positions and colours as "c",
+                    normals mesh_light_ref.sphere_normals plus a seeded
+                    perturbation (not renormalised).
                     space "screen" (positions are pixels and depths; drawn
                     under None / IDENT16) or "model" (positions in [-1, 1]^3;
                     drawn under mesh_ref.affine / perspective / behind_eye).
@@ -50,6 +54,51 @@ recording, runs each operation:
   begin / end / flush (command recording), gather (gather_frame_u8), knobs
           -> nothing
 
+The five sticky states of the mesh and textured draws -- near plane, cull mode,
+mesh perspective, triangle texture filter, lights -- are tracked by the
+interpreter itself (near, cull, persp, filt, ambient, lights), identically on
+both sides; the lowerings read that tracked state and never ask the library.
+A state operation calls the setter on the GPU and nothing on the oracle, and a
+GPU run ends by asserting that the five getters return the tracked state: no
+resize, save / restore, set_color, recording or draw between may have touched
+them (DESIGN.md documents no operation that resets one).  Operation by
+operation, all bit-exact:
+
+  "mesh" / "mesh2" of a colour (or lit, drawn unlit) mesh
+          -> draw_triangles of mesh_clip_ref.clip_soup(mesh, M, near, cull)
+             (mesh_ref.expand with both off)
+  "meshi" (draw_mesh_instanced, host or device matrices and tints)
+          -> draw_triangles of mesh_inst_ref.instanced_soup(mesh, mats, tint,
+             near, cull); a textured mesh as the textured meshes below, from
+             the same soup
+  "lmesh" / "lmesh2" (draw_mesh_lit; draw, update_normals and
+      update_positions, draw)
+          -> draw_triangles of mesh_light_ref.lit_soup(mesh, M, N, ambient,
+             lights, near, cull)
+  "lmeshi" (draw_mesh_lit_instanced and its device form)
+          -> draw_triangles of mesh_light_ref.lit_instanced_soup(...)
+  an empty soup draws nothing on either side
+  textured draws with one (u, v) per triangle under the bilinear filter
+          -> flat draw_triangles coloured bilinear_ref.sample_bilinear(texels,
+             u, v): a0 + (a1-a0)*w1 + (a2-a0)*w2 returns a constant exactly,
+             at a cut vertex too (a + (a-a)*t)
+  "ptri" (a textured soup with q: one UV and one q in {0.25, 0.5, 1, 2, 4} per
+      triangle; u*q, 1/q and (u*q)*(1/q) are exact)
+          -> the affine lowering of its (u, v), nearest or bilinear
+  textured meshes with the mesh perspective on, under None / the identity / an
+      affine matrix (cw and q exactly 1)
+          -> the affine lowering
+  the 2x2 "ts" mesh under the nearest filter, any matrix, perspective on or off
+          -> texel (0, 0), as before
+
+The one substitution rule.  No exact lowering exists for free UVs under the
+bilinear filter (uv "free" soups and buffers, the "ts" mesh) nor for a "tu"
+mesh with the mesh perspective on under a perspective or behind-eye matrix
+(an instanced draw: under any such matrix).  For such a draw the interpreter
+switches the offending state off on the GPU side (set_triangle_texture_filter(0)
+or set_mesh_perspective(False)), draws, and switches it back on; the tracked
+state is unchanged and the lowering uses the state as drawn.
+
 Rules of the interpreter, the same on both sides: a draw whose texture is
 narrower or lower than 2 texels (the snapshot of a 1-pixel-wide frame) is left
 out -- the library rejects a textured batch from it
@@ -59,8 +108,8 @@ context, whose framebuffer they alias; every texture, buffer, mesh and device
 array lives until the frame's last readback.
 
 What this leaves to the dedicated tests: per-pixel sampling with varying UVs
-on real textures (test_textured_gpu.py), shards and RCCL, warm fault
-injection.
+on real textures (test_textured_gpu.py, test_persp_gpu.py,
+test_bilinear_gpu.py), shards and RCCL, warm fault injection.
 """
 from __future__ import annotations
 
@@ -69,6 +118,10 @@ import random
 import numpy as np
 from hypothesis import HealthCheck, given, settings, strategies as st
 
+import bilinear_ref as B
+import mesh_clip_ref as MC
+import mesh_inst_ref as MI
+import mesh_light_ref as ML
 import mesh_ref as MR
 import scenes
 import textured_ref as T
@@ -82,7 +135,11 @@ KNOBS_OFF = dict(ordered=False, coop=0, paircap=0, split=None, warm=0, record=Fa
 KNOB_VALUES = dict(ordered=(False, True), coop=(0, 1, 2), paircap=(0, 50), split=(None, (64, 64)),
                    warm=(0, 1, 2), record=(False, True), fmt=(None, "rgb", "yuv420p"))
 
-BATCH_OPS = ("tri", "ttri", "buf", "buf2", "mesh", "mesh2")
+NEAR_VALUES = (0.0, 0.5, MI.NEAR)
+Q_VALUES = (0.25, 0.5, 1.0, 2.0, 4.0)
+
+BATCH_OPS = ("tri", "ttri", "buf", "buf2", "mesh", "mesh2", "meshi", "lmesh", "lmesh2", "lmeshi", "ptri")
+STATE5_OPS = ("near", "cull", "mpersp", "filter", "lights")
 OPS = """
 ("tri", src, n, seed, spread, gouraud, blended)       colour soup; src "host" | "dev" | "dev8"
 ("ttri", src, n, seed, spread, uvkind, texref)        textured soup; uvkind "const" | "free" (texref then "tiny")
@@ -90,6 +147,17 @@ OPS = """
 ("buf2", i, texref, dx)                               the same twice, translate(dx, 0) between (0: the second is warm)
 ("mesh", i, mat, texref)                              resource mesh i; mat indexes the matrices of its space
 ("mesh2", i, mat, texref, seed)                       draw, update_positions(seed), draw
+("meshi", i, K, seed, tint, src)                      draw_mesh_instanced of resource mesh i under K seeded matrices of its
+                                                      space; tint None | "opaque" | "alpha" (None for textured meshes);
+                                                      src "host" | "dev" | "dev8" (matrices and tint); a "tu" mesh
+                                                      samples the resource texture ("res", seed)
+("lmesh", i, mat, nseed)                              draw_mesh_lit of the i-th lit mesh; nseed: a seeded rotation3 or None
+("lmesh2", i, mat, nseed, seed)                       draw, update_normals(seed) and update_positions(seed), draw
+("lmeshi", i, K, seed, tint, src)                     draw_mesh_lit_instanced (seeded normal matrices, None for seed % 3 == 0)
+("ptri", src, n, seed, spread, texref)                textured soup with q: one UV and one q of Q_VALUES per triangle
+("near", w) ("cull", mode) ("mpersp", on) ("filter", mode)   the sticky states: w in NEAR_VALUES, mode 0 | 1 | 2, 0 | 1
+("lights", seed, nl)                                  set_mesh_lights(*mesh_light_ref.random_lights(nl, seed)), nl in 0..8;
+                                                      seed None: (None, None), the default lights
 ("fill", c) ("rect", c, g) ("line", c, g) ("circle", c, g) ("grd", c, g)
 ("tex", texref, g) ("stex", texref, g, uv4) ("setpx", x, y, c) ("applypx", x, y, c)
 ("snap", which, shared)                               take the snapshot of that slot (again)
@@ -169,12 +237,15 @@ def mesh_positions(spec, W, H, seed):
 def mesh_dict(spec, W, H):
     """The mesh of a spec as mesh_ref's dict (pos, idx, colors + gouraud | uv)."""
     kind, space = spec[0], spec[1]
-    if kind == "c":
+    if kind in ("c", "l"):
         _, _, rows, cols, seed, gouraud, blended = spec
         p, g = mesh_positions(spec, W, H, seed)
         col = g.uniform(0, 1, size=(p.shape[0], 4))
         col[:, 3] = g.uniform(0.1, 0.9, size=p.shape[0]) if blended else 1.0
-        return dict(pos=_to_space(space, p, W, H), idx=MR.grid_indices(rows, cols), colors=col, gouraud=gouraud)
+        mesh = dict(pos=_to_space(space, p, W, H), idx=MR.grid_indices(rows, cols), colors=col, gouraud=gouraud)
+        if kind == "l":
+            mesh["normals"] = mesh_normals(spec, seed)
+        return mesh
     if kind == "ts":
         _, _, rows, cols, seed = spec
         p, g = mesh_positions(spec, W, H, seed)
@@ -204,6 +275,113 @@ def mesh_matrix(space, mat, W, H):
         return (("none", None), ("ident", MR.IDENT16))[mat % 2]
     return (("affine", MR.affine(W, H)), ("perspective", MR.perspective(W, H)),
             ("perspective", MR.behind_eye(W, H)), ("affine", MR.affine(W, H, ax=1.1, ay=-0.7, scale=0.3)))[mat % 4]
+
+
+def mesh_normals(spec, seed):
+    """The normals of a lit mesh for `seed`: the sphere's analytic ones plus a
+    perturbation (their lengths are then not 1: nothing renormalises them)."""
+    n = ML.sphere_normals(spec[2], spec[3])
+    return np.ascontiguousarray(n + scenes.rng(seed + 3).uniform(-0.15, 0.15, size=n.shape))
+
+
+def moved_mesh(spec, mesh, W, H, seed):
+    """`mesh` with the positions (a lit mesh: and the normals) of `seed`."""
+    p, _ = mesh_positions(spec, W, H, seed)
+    p = _to_space(spec[1], p, W, H)
+    if spec[0] == "tu":           # (stored through the permutation, as at creation)
+        pos = np.empty_like(p)
+        pos[mesh["idx"].reshape(-1).astype(np.int64)] = p
+        p = pos
+    out = dict(mesh, pos=p)
+    if spec[0] == "l":
+        out["normals"] = mesh_normals(spec, seed)
+    return out
+
+
+_INSTANCE_MATS = (0, 1, 2, 2, 2, 3)       # (perspective and behind-eye at least as often as the affine ones)
+
+
+def instance_matrices(space, K, seed, W, H):
+    """(labels, (K, 16)): K matrices of the mesh's space, each one of
+    mesh_matrix's set times a seeded placement (a uniform scale and an offset)."""
+    g = scenes.rng(seed)
+    labels, mats = [], []
+    for _ in range(K):
+        s = g.uniform(0.3, 0.8)
+        A = np.eye(4)
+        if space == "screen":
+            A[0, 0] = A[1, 1] = s
+            A[:3, 3] = (W / 2 * (1 - s) + g.uniform(-0.3, 0.3) * W, H / 2 * (1 - s) + g.uniform(-0.3, 0.3) * H,
+                        g.uniform(-0.2, 0.2))
+            label, M = "ident", A
+        else:
+            A[0, 0] = A[1, 1] = A[2, 2] = s
+            A[:3, 3] = g.uniform(-0.7, 0.7, size=3)
+            label, M = mesh_matrix(space, _INSTANCE_MATS[int(g.integers(len(_INSTANCE_MATS)))], W, H)
+            M = M.reshape(4, 4) @ A
+            if label == "affine":
+                M[3] = (0.0, 0.0, 0.0, 1.0)
+        labels.append(label)
+        mats.append(M.reshape(16))
+    return labels, np.ascontiguousarray(np.stack(mats))
+
+
+def instance_tint(kind, K, seed):
+    """(K, 4) colour factors in [0.3, 1]: "opaque" alpha 1, "alpha" alpha in
+    [0.2, 0.9] for about half of the instances, the first included; None."""
+    if kind is None:
+        return None
+    g = scenes.rng(seed + 11)
+    t = g.uniform(0.3, 1.0, size=(K, 4))
+    t[:, 3] = 1.0
+    if kind == "alpha":
+        sel = g.random(K) < 0.5
+        sel[0] = True
+        t[sel, 3] = g.uniform(0.2, 0.9, size=int(sel.sum()))
+    return np.ascontiguousarray(t)
+
+
+def normal_matrix(nseed):
+    """A seeded mesh_light_ref.rotation3, or None."""
+    if nseed is None:
+        return None
+    ax, ay = scenes.rng(nseed + 17).uniform(-np.pi, np.pi, size=2)
+    return ML.rotation3(ax, ay)
+
+
+def instance_normals(K, seed):
+    """(K, 9) seeded rotations; None (the identity) for seed % 3 == 0."""
+    if seed % 3 == 0:
+        return None
+    return np.ascontiguousarray(np.stack([normal_matrix(seed + 31 * k) for k in range(K)]))
+
+
+def light_state(seed, nl):
+    """(ambient, lights) of a ("lights", seed, nl) operation."""
+    if seed is None:
+        return None, None
+    return ML.random_lights(nl, seed)
+
+
+def mesh_draw_soup(mesh, M, near, cull):
+    """(xy, z, attr) of a single unlit mesh draw under the clip state."""
+    if near > 0 or cull != 0:
+        return MC.clip_soup(mesh, M, near, cull)[:3]
+    return MR.expand(mesh, M)
+
+
+def textured_colours(texels, uv, filt):
+    """The flat colours (n, 4) of triangles with one (u, v) each, uv (n, >= 2)."""
+    if filt:
+        return np.ascontiguousarray(B.sample_bilinear(texels, uv[:, 0], uv[:, 1]))
+    return T.flat_colours(texels, uv[:, :2])
+
+
+def perspective_soup(n, W, H, seed, spread, size):
+    """textured_soup with uv "const" plus q (n, 3): one of Q_VALUES per triangle."""
+    xy, z, uv = textured_soup(n, W, H, seed, spread, "const", size)
+    q = np.asarray(Q_VALUES)[scenes.rng(seed + 2).integers(0, len(Q_VALUES), size=n)]
+    return xy, z, uv, np.ascontiguousarray(np.repeat(q[:, None], 3, axis=1))
 
 
 def tile_pairs(xy, m, W, H):
@@ -238,6 +416,12 @@ class _Run:
         self.batches = []                       # (kind, raster path or None, tile pairs)
         self.snaps = {}
         self.aux = None
+        # the five sticky states, tracked here and never read back from the library before the run's end
+        self.near, self.cull, self.persp, self.filt = 0.0, 0, False, 0
+        self.ambient = self.lights = None
+        self.counts = []                        # (full, rasterised) triangle counts of the mesh draws
+        self.over_cap = False                   # a batch of more than 50 tile pairs since the last synchronisation
+        self.changed_over_cap = 0               # changes of the five states while such a batch may be pending
         if self.gpu:
             from libnativecpurenderer_amd import libNativeCPURendererPybind as R
             self.R = R
@@ -293,8 +477,10 @@ class _Run:
             gm = None
             if self.gpu and self.triangles:
                 gm = (self.R.Mesh(mesh["pos"], mesh["idx"], uv=mesh["uv"]) if "uv" in mesh else
-                      self.R.Mesh(mesh["pos"], mesh["idx"], colors=mesh["colors"], gouraud=mesh["gouraud"]))
+                      self.R.Mesh(mesh["pos"], mesh["idx"], colors=mesh["colors"], gouraud=mesh["gouraud"],
+                                  normals=mesh.get("normals")))
             self.meshes.append([spec, mesh, gm])
+        self.lit = [e for e in self.meshes if e[0][0] == "l"]
 
     def texture(self, ref, prim=False):
         if prim and not self.gpu and ref[0] == "snap" and ref[1] == "main" and ref[2]:
@@ -329,6 +515,7 @@ class _Run:
             return
         path = ctx.last_raster_path() if self.gpu else None
         self.batches.append((kind, path, tile_pairs(xy, ctx.get_transform(), ctx.width, ctx.height)))
+        self.over_cap |= ctx is self.ctx and self.batches[-1][2] > 50
 
     def _device(self, arrays, offset):
         import torch
@@ -358,21 +545,34 @@ class _Run:
             ctx.draw_triangles_device(txy, tc, xy.shape[0], z=tz, gouraud=gouraud)
         self._note("colour", xy, ctx)
 
-    def textured_batch(self, tex, xy, z, uv, uvkind, src="host", gbuf=None):
+    def _nearest_for(self, free):
+        """The substitution rule for free UVs: the filter as drawn, and, on the
+        GPU side under the bilinear filter, the setter calls around the draw."""
+        if not (free and self.filt):
+            return self.filt, False
+        if self.gpu:
+            self.ctx.set_triangle_texture_filter(0)
+        return 0, self.gpu
+
+    def textured_batch(self, tex, xy, z, uv, uvkind, src="host", gbuf=None, q=None):
         if not self.triangles or tex.width < 2 or tex.height < 2:
             return
         assert uvkind == "const" or (tex.width, tex.height) == (2, 2), "free UVs are lowered on 2x2 textures only"
+        filt, back = self._nearest_for(uvkind != "const")
         if not self.gpu:
-            flat = T.flat_colours(self.texels(tex), uv[:, :2])
+            flat = textured_colours(self.texels(tex), uv, filt)
             self.ctx.draw_triangles(xy, flat, z=z, gouraud=False)
         elif src == "host":
-            self.ctx.draw_textured_triangles(tex, xy, uv, z=z)
+            self.ctx.draw_textured_triangles(tex, xy, uv, z=z, q=q)
         elif src == "buf":
             self.ctx.draw_triangle_buffer(gbuf, tex)
         else:
             txy, tuv = self._device((xy, uv), src == "dev8")
             tz, = self._device((z,), False)
-            self.ctx.draw_textured_triangles_device(tex, txy, tuv, xy.shape[0], z=tz)
+            tq = None if q is None else self._device((q,), src == "dev8")[0]
+            self.ctx.draw_textured_triangles_device(tex, txy, tuv, xy.shape[0], z=tz, q=tq)
+        if back:
+            self.ctx.set_triangle_texture_filter(1)
         self._note("textured", xy)
 
     def draw_buffer(self, i, texref):
@@ -386,40 +586,155 @@ class _Run:
             ref = texref if spec[4] == "const" else ("tiny", spec[2], 3 + spec[2] % 2)
             self.textured_batch(self.texture(ref), xy, z, a, spec[4], "buf", gbuf)
 
+    def _mesh_texture(self, spec, texref):
+        """The texture of a mesh draw (None: a colour mesh), and whether the draw is left out."""
+        if spec[0] not in ("tu", "ts"):
+            return None, False
+        tex = self.texture(texref if spec[0] == "tu" else ("tiny", spec[4], 3 + spec[4] % 2))
+        return tex, tex.width < 2 or tex.height < 2
+
+    def _textured_mesh_states(self, spec, labels):
+        """The substitution rule for a textured mesh draw under matrices of
+        `labels`: the filter as drawn, and a function that restores what the
+        GPU side switched off."""
+        filt, back = self._nearest_for(spec[0] == "ts")
+        off = self.gpu and self.persp and spec[0] == "tu" and "perspective" in labels
+        if off:
+            self.ctx.set_mesh_perspective(False)
+
+        def restore():
+            if back:
+                self.ctx.set_triangle_texture_filter(1)
+            if off:
+                self.ctx.set_mesh_perspective(True)
+        return filt, restore
+
+    def _oracle_soup(self, mesh, soup, tex, filt):
+        xy, z, attr = soup
+        if xy.shape[0] == 0:
+            return
+        if tex is None:
+            self.ctx.draw_triangles(xy, attr, z=z, gouraud=bool(mesh["gouraud"]))
+        else:
+            self.ctx.draw_triangles(xy, textured_colours(self.texels(tex), attr, filt), z=z, gouraud=False)
+
+    def _note_mesh(self, kind, full, xy):
+        self.counts.append((full, xy.shape[0]))
+        with np.errstate(all="ignore"):
+            self._note(kind, xy)
+
     def draw_mesh(self, i, mat, texref):
         if not self.meshes or not self.triangles:
             return
         spec, mesh, gm = self.meshes[i % len(self.meshes)]
-        _, M = mesh_matrix(spec[1], mat, self.W0, self.H0)
-        xy, z, attr = MR.expand(mesh, M)
-        tex = None
-        if "uv" in mesh:
-            tex = self.texture(texref if spec[0] == "tu" else ("tiny", spec[4], 3 + spec[4] % 2))
-            if tex.width < 2 or tex.height < 2:
-                return
+        label, M = mesh_matrix(spec[1], mat, self.W0, self.H0)
+        tex, skip = self._mesh_texture(spec, texref)
+        if skip:
+            return
+        soup = mesh_draw_soup(mesh, M, self.near, self.cull)
+        filt, restore = self._textured_mesh_states(spec, (label,))
         if self.gpu:
             self.ctx.draw_mesh(gm, M, texture=tex)
-        elif tex is None:
-            self.ctx.draw_triangles(xy, attr, z=z, gouraud=bool(mesh["gouraud"]))
         else:
-            self.ctx.draw_triangles(xy, T.flat_colours(self.texels(tex), attr[:, :2]), z=z, gouraud=False)
-        with np.errstate(all="ignore"):
-            self._note("mesh", xy)
+            self._oracle_soup(mesh, soup, tex, filt)
+        restore()
+        self._note_mesh("mesh", mesh["idx"].shape[0], soup[0])
 
-    def move_mesh(self, i, seed):
-        if not self.meshes:
-            return
-        entry = self.meshes[i % len(self.meshes)]
-        spec, mesh = entry[0], entry[1]
-        p, _ = mesh_positions(spec, self.W0, self.H0, seed)
-        p = _to_space(spec[1], p, self.W0, self.H0)
-        if spec[0] == "tu":           # (stored through the permutation, as at creation)
-            pos = np.empty_like(p)
-            pos[mesh["idx"].reshape(-1).astype(np.int64)] = p
-            p = pos
-        entry[1] = dict(mesh, pos=p)
+    def move_mesh(self, entry, seed):
+        entry[1] = moved_mesh(entry[0], entry[1], self.W0, self.H0, seed)
         if entry[2] is not None:
-            entry[2].update_positions(p)
+            if entry[0][0] == "l":
+                entry[2].update_normals(entry[1]["normals"])
+            entry[2].update_positions(entry[1]["pos"])
+
+    def _instances(self, spec, K, seed, tint, src, normals=False):
+        """labels, the host arrays (matrices, normal matrices, tint) and what the GPU call takes for them."""
+        labels, mats = instance_matrices(spec[1], K, seed, self.W0, self.H0)
+        host = [mats, instance_normals(K, seed) if normals else None,
+                instance_tint(None if spec[0] in ("tu", "ts") else tint, K, seed)]
+        args = host
+        if self.gpu and src != "host":
+            args = [None if a is None else self._device((a,), src == "dev8")[0] for a in host]
+        return labels, host, args
+
+    def draw_mesh_instanced(self, i, K, seed, tint, src):
+        if not self.meshes or not self.triangles:
+            return
+        spec, mesh, gm = self.meshes[i % len(self.meshes)]
+        tex, skip = self._mesh_texture(spec, ("res", seed))     # (a "tu" mesh: the resource texture its seed names)
+        if skip:
+            return
+        labels, (mats, _, tn), (gmats, _, gtn) = self._instances(spec, K, seed, tint, src)
+        soup = MI.instanced_soup(mesh, mats, tn, self.near, self.cull)[:3]
+        filt, restore = self._textured_mesh_states(spec, labels)
+        if not self.gpu:
+            self._oracle_soup(mesh, soup, tex, filt)
+        elif src == "host":
+            self.ctx.draw_mesh_instanced(gm, gmats, texture=tex, tint=gtn)
+        else:
+            self.ctx.draw_mesh_instanced_device(gm, gmats, K, texture=tex, tint=gtn)
+        restore()
+        self._note_mesh("instanced", K * mesh["idx"].shape[0], soup[0])
+
+    def draw_mesh_lit(self, i, mat, nseed):
+        if not self.lit or not self.triangles:
+            return
+        spec, mesh, gm = self.lit[i % len(self.lit)]
+        _, M = mesh_matrix(spec[1], mat, self.W0, self.H0)
+        N = normal_matrix(nseed)
+        soup = ML.lit_soup(mesh, M, N, self.ambient, self.lights, self.near, self.cull)
+        if self.gpu:
+            self.ctx.draw_mesh_lit(gm, M, N)
+        else:
+            self._oracle_soup(mesh, soup, None, 0)
+        self._note_mesh("lit", mesh["idx"].shape[0], soup[0])
+
+    def draw_mesh_lit_instanced(self, i, K, seed, tint, src):
+        if not self.lit or not self.triangles:
+            return
+        spec, mesh, gm = self.lit[i % len(self.lit)]
+        _, (mats, nm, tn), (gmats, gnm, gtn) = self._instances(spec, K, seed, tint, src, normals=True)
+        soup = ML.lit_instanced_soup(mesh, mats, nm, tn, self.ambient, self.lights, self.near, self.cull)
+        if not self.gpu:
+            self._oracle_soup(mesh, soup, None, 0)
+        elif src == "host":
+            self.ctx.draw_mesh_lit_instanced(gm, gmats, gnm, gtn)
+        else:
+            self.ctx.draw_mesh_lit_instanced_device(gm, gmats, K, gnm, gtn)
+        self._note_mesh("lit", K * mesh["idx"].shape[0], soup[0])
+
+    def set_state(self, k, op):
+        ctx, before = self.ctx, (self.near, self.cull, self.persp, self.filt, self.ambient, self.lights)
+        if k == "near":
+            self.near = float(op[1])
+            if self.gpu:
+                ctx.set_mesh_near_plane(self.near)
+        elif k == "cull":
+            self.cull = int(op[1])
+            if self.gpu:
+                ctx.set_mesh_cull(self.cull)
+        elif k == "mpersp":
+            self.persp = bool(op[1])
+            if self.gpu:
+                ctx.set_mesh_perspective(self.persp)
+        elif k == "filter":
+            self.filt = int(op[1])
+            if self.gpu:
+                ctx.set_triangle_texture_filter(self.filt)
+        else:
+            self.ambient, self.lights = light_state(op[1], op[2])
+            if self.gpu:
+                ctx.set_mesh_lights(self.ambient, self.lights)
+        after = (self.near, self.cull, self.persp, self.filt, self.ambient, self.lights)
+        self.changed_over_cap += self.over_cap and repr(before) != repr(after)
+
+    def check_states(self):
+        """The five getters against the tracked state (GPU side)."""
+        ctx = self.ctx
+        got = (ctx.get_mesh_near_plane(), ctx.get_mesh_cull(), ctx.mesh_perspective(), ctx.get_triangle_texture_filter(),
+               ctx.get_mesh_light_count())
+        want = (self.near, self.cull, self.persp, self.filt, 0 if self.lights is None else len(self.lights))
+        assert got == want, f"sticky states {got} != tracked {want}"
 
     # ---- one operation --------------------------------------------------------
     def op(self, op):
@@ -445,8 +760,27 @@ class _Run:
             self.draw_mesh(op[1], op[2], op[3])
         elif k == "mesh2":
             self.draw_mesh(op[1], op[2], op[3])
-            self.move_mesh(op[1], op[4])
+            if self.meshes:
+                self.move_mesh(self.meshes[op[1] % len(self.meshes)], op[4])
             self.draw_mesh(op[1], op[2], op[3])
+        elif k == "meshi":
+            self.draw_mesh_instanced(op[1], op[2], op[3], op[4], op[5])
+        elif k == "lmesh":
+            self.draw_mesh_lit(op[1], op[2], op[3])
+        elif k == "lmesh2":
+            self.draw_mesh_lit(op[1], op[2], op[3])
+            if self.lit:
+                self.move_mesh(self.lit[op[1] % len(self.lit)], op[4])
+            self.draw_mesh_lit(op[1], op[2], op[3])
+        elif k == "lmeshi":
+            self.draw_mesh_lit_instanced(op[1], op[2], op[3], op[4], op[5])
+        elif k == "ptri":
+            _, src, n, seed, spread, texref = op
+            tex = self.texture(texref)
+            xy, z, uv, q = perspective_soup(n, W0, H0, seed, spread, (tex.width, tex.height))
+            self.textured_batch(tex, xy, z, uv, "const", src, q=q)
+        elif k in STATE5_OPS:
+            self.set_state(k, op)
         elif k == "fill":
             ctx.fill_color(*op[1])
         elif k == "rect":
@@ -512,12 +846,16 @@ class _Run:
             self.W, self.H = op[1], op[2]
             self.snaps.pop(("main", True), None)
         elif k == "getcolor":
+            self.over_cap = False
             self.probes.append(np.array(ctx.get_color(op[1], op[2])[:4 if self.alpha else 3], dtype=np.float64))
         elif k == "readf64":
+            self.over_cap = False
             self.probes.append(ctx.get_buffer_numpy())
         elif k == "readdepth":
+            self.over_cap = False
             self.probes.append(ctx.get_depth_buffer())
         elif k in ("begin", "end", "flush", "gather"):
+            self.over_cap &= k in ("begin", "end")
             if self.gpu:
                 {"begin": ctx.begin_commands, "end": ctx.end_commands, "flush": ctx.flush_commands,
                  "gather": ctx.gather_frame_u8}[k]()
@@ -537,6 +875,8 @@ class _Run:
                 continue
             self.op(op)
         out = {}
+        if self.gpu:
+            self.check_states()
         if fmt and self.gpu:
             ctx.gather_frame_u8()
             out["frame"] = ctx.get_frame_u8()
@@ -546,6 +886,8 @@ class _Run:
         out["probes"] = self.probes
         out["batches"] = self.batches
         out["warm"] = ctx.warm_batch_count() if self.gpu else 0
+        out["counts"] = self.counts
+        out["changed_over_cap"] = self.changed_over_cap
         self.keep.clear()
         return out
 
@@ -553,7 +895,11 @@ class _Run:
 def run(fac, frame, triangles=True):
     """Executes `frame` on `fac`: dict f64, depth, u8, frame (with a frame
     format), probes (list of arrays), batches [(kind, raster path, tile
-    pairs)], warm.  triangles=False leaves the triangle operations out."""
+    pairs)] (kind colour, textured, mesh, instanced or lit), warm, counts
+    [(full, rasterised triangles)] of the mesh draws, changed_over_cap (how
+    often one of the five states changed after a batch of more than 50 tile
+    pairs and before the next flush, gather or probe).  triangles=False leaves
+    the triangle operations out."""
     return _Run(fac, frame, triangles).run()
 
 
@@ -606,13 +952,64 @@ def kinds(frame):
     def mesh(i, mat, ref):
         if meshes:
             spec = meshes[i % len(meshes)]
-            out.add({"c": "mesh:colour", "tu": "mesh:textured-unshared", "ts": "mesh:textured-2x2"}[spec[0]])
+            out.add({"c": "mesh:colour", "l": "mesh:colour", "tu": "mesh:textured-unshared",
+                     "ts": "mesh:textured-2x2"}[spec[0]])
             out.add("matrix:" + mesh_matrix(spec[1], mat, 8, 8)[0])
             if spec[0] == "tu":
                 texref(ref, "soup")
 
+    # the mesh draws under the tracked clip state: the triangle counts of their reference soups
+    near, cull, nl = 0.0, 0, 0
+    dicts = {}
+    lit = [i for i, spec in enumerate(meshes) if spec[0] == "l"]
+
+    def clipped(i, mats):
+        """Notes whether the near plane or the cull changed the draw's triangle count."""
+        if i not in dicts:
+            dicts[i] = mesh_dict(meshes[i], W, H)
+        if near > 0 or cull:
+            for M in mats:
+                n0 = dicts[i]["idx"].shape[0]
+                n1 = int(MC.clip_soup(dicts[i], M, near, 0)[3].sum()) if near > 0 else n0
+                n2 = int(MC.clip_soup(dicts[i], M, near, cull)[3].sum()) if cull else n1
+                if n1 != n0:
+                    out.add("clip:cut")
+                if n2 < n1:
+                    out.add("cull:dropped")
+
+    def move(i, seed):
+        clipped(i, ())
+        dicts[i] = moved_mesh(meshes[i], dicts[i], W, H, seed)
+
     for op in ops:
         k = op[0]
+        if k in ("mesh", "mesh2") and meshes:
+            i = op[1] % len(meshes)
+            clipped(i, [mesh_matrix(meshes[i][1], op[2], W, H)[1]])
+            if k == "mesh2":
+                move(i, op[4])
+                clipped(i, [mesh_matrix(meshes[i][1], op[2], W, H)[1]])
+        elif k in ("lmesh", "lmesh2") and lit:
+            i = lit[op[1] % len(lit)]
+            out.update({k, "lights:0"} if nl == 0 else {k, "lights:8"} if nl == 8 else {k})
+            clipped(i, [mesh_matrix(meshes[i][1], op[2], W, H)[1]])
+            if k == "lmesh2":
+                move(i, op[4])
+                clipped(i, [mesh_matrix(meshes[i][1], op[2], W, H)[1]])
+        elif (k == "meshi" and meshes) or (k == "lmeshi" and lit):
+            i = op[1] % len(meshes) if k == "meshi" else lit[op[1] % len(lit)]
+            out.add(k)
+            if k == "lmeshi" and nl in (0, 8):
+                out.add(f"lights:{nl}")
+            if op[4] == "alpha" and meshes[i][0] in ("c", "l"):
+                out.add("tint:alpha")
+            clipped(i, instance_matrices(meshes[i][1], op[2], op[3], W, H)[1])
+        elif k == "near":
+            near = float(op[1])
+        elif k == "cull":
+            cull = int(op[1])
+        elif k == "lights":
+            nl = 0 if op[1] is None else op[2]
         if k == "tri":
             out.add("colour:" + {"host": "host", "dev": "device", "dev8": "device"}[op[1]])
         elif k == "ttri":
@@ -626,6 +1023,11 @@ def kinds(frame):
             mesh(op[1], op[2], op[3])
             if k == "mesh2" and meshes:
                 out.add("mesh:update_positions")
+        elif k in ("meshi", "lmesh", "lmesh2", "lmeshi"):
+            pass                                   # (noted above, where the mesh exists)
+        elif k == "ptri":
+            out.add("ptri")
+            texref(op[5], "soup")
         elif k in ("tex", "stex"):
             out.add(k)
             texref(op[1], "draw_texture")
@@ -640,7 +1042,7 @@ def kinds(frame):
     return out
 
 
-ALL_KINDS = (
+BASE_KINDS = (
     "colour:host", "colour:buffer", "colour:device",
     "textured:host", "textured:buffer", "textured:device", "uv:const", "uv:free",
     "mesh:colour", "mesh:textured-unshared", "mesh:textured-2x2", "mesh:update_positions", "buffer:again",
@@ -654,6 +1056,10 @@ ALL_KINDS = (
     "getcolor", "readf64", "readdepth",
     "begin", "end", "flush", "gather",
 )
+# the state frames add the five states, the draws that read them and what those draws must reach
+STATE_KINDS = ("near", "cull", "mpersp", "filter", "lights", "meshi", "lmesh", "lmesh2", "lmeshi", "ptri",
+               "clip:cut", "cull:dropped", "tint:alpha", "lights:0", "lights:8")
+ALL_KINDS = BASE_KINDS + STATE_KINDS
 
 
 def batch_kinds(frame):
@@ -677,7 +1083,49 @@ def batch_kinds(frame):
         elif k in ("mesh", "mesh2") and meshes:
             epochs[-1].add("mesh")
             count += 2 if k == "mesh2" else 1
+        elif k == "ptri":
+            epochs[-1].add("textured"); count += 1
+        elif k == "meshi" and meshes:
+            epochs[-1].add("instanced"); count += 1
+        elif k in ("lmesh", "lmesh2", "lmeshi") and any(spec[0] == "l" for spec in meshes):
+            epochs[-1].add("lit")
+            count += 2 if k == "lmesh2" else 1
     return epochs, count
+
+
+_DEFAULT5 = dict(near=0.0, cull=0, mpersp=False, filter=0, lights=(None, 0))
+
+
+def state_stats(frame):
+    """What a frame does with the five sticky states: dict of three flags.
+    two_states      a mesh draw is issued with at least two of the five at a
+                    non-default value
+    changed_between one of the five changes value between two mesh or textured
+                    batches with no flush, gather or probe between them
+    meets_others    a lit or instanced draw shares a depth-buffer epoch with a
+                    colour, textured or (single, unlit) mesh batch"""
+    W, H, alpha, knobs, res, ops = frame
+    bufs, meshes = res.get("bufs", []), res.get("meshes", [])
+    has_lit = any(spec[0] == "l" for spec in meshes)
+    state = dict(_DEFAULT5)
+    two = between = False
+    pending = changed = False            # a mesh or textured batch issued; a state changed since
+    for op in ops:
+        k = op[0]
+        mesh_draw = (k in ("mesh", "mesh2", "meshi") and meshes) or (k in ("lmesh", "lmesh2", "lmeshi") and has_lit)
+        textured = k in ("ttri", "ptri") or (k in ("buf", "buf2") and bufs and bufs[op[1] % len(bufs)][0] == "t")
+        if k in STATE5_OPS:
+            new = (op[1], 0 if op[1] is None else op[2]) if k == "lights" else type(_DEFAULT5[k])(op[1])
+            changed |= pending and new != state[k]
+            state[k] = new
+        elif mesh_draw or textured:
+            two |= bool(mesh_draw) and sum(state[n] != _DEFAULT5[n] for n in state) >= 2
+            between |= changed
+            pending, changed = True, False
+        elif k in ("flush", "gather", "getcolor", "readf64", "readdepth"):
+            pending = changed = False
+    meets = any(e & {"lit", "instanced"} and e & {"colour", "textured", "mesh"} for e in batch_kinds(frame)[0])
+    return dict(two_states=two, changed_between=between, meets_others=meets)
 
 
 # ---------------------------------------------------------------------------
@@ -836,6 +1284,91 @@ class _Gen:
                 self.state_op(late) if x < 0.80 else self.other_op())
 
 
+class _StateGen(_Gen):
+    """The generator of the state frames: _Gen's vocabulary plus the five
+    sticky states and the draws that read them, on a random stream of its own
+    (make_small_state_frame / make_large_state_frame; the streams of the
+    "small" and "large" examples are not touched)."""
+
+    def resources(self):
+        """_Gen's textures and buffers; one to three meshes, a lit one first."""
+        r, lim = self.r, self.lim
+        res = super().resources()
+        meshes = []
+        for k in range(r.choice([2, 2, 3, 3])):
+            kind = "l" if k == 0 else r.choice(["c", "tu", "tu", "ts", "ts"])
+            space = r.choice(["screen", "model"] + ["model"] * (kind == "l"))
+            if kind == "tu":
+                s = r.choice([0.05, 0.3, 1.0])
+                meshes.append(("tu", space, self.count(lim["maxmesh"], 1, 0.45 * max(self.W, self.H) * s), self.seed(), s))
+                continue
+            rows = r.randint(1, 10 if lim["maxmesh"] <= 200 else 40)
+            cols = r.randint(1, max(1, min(50, lim["maxmesh"] // (2 * rows))))
+            meshes.append(("ts", space, rows, cols, self.seed()) if kind == "ts" else
+                          (kind, space, rows, cols, self.seed(), r.random() < 0.6, r.random() < 0.3))
+        r.shuffle(meshes)
+        res["meshes"] = meshes
+        return res
+
+    def mesh_triangles(self, i):
+        spec = self.res["meshes"][i]
+        return spec[2] if spec[0] == "tu" else 2 * spec[2] * spec[3]
+
+    def instances(self, i):
+        """K of an instanced draw of mesh i: small frames 1..6 and at most 600
+        triangles; large frames at most 40, 4000 triangles and the
+        bounding-box budget, which an instance of mean scale 0.55 enters with
+        the frame's area (both faces of the sphere, boxes twice their triangles)."""
+        n = max(1, self.mesh_triangles(i))
+        if not self.lim["budget"]:
+            return self.r.randint(1, max(1, min(6, 600 // n)))
+        top = min(40, 4000 // n, int(self.lim["budget"] // (1.2 * self.W * self.H)))
+        return self.r.randint(1, max(1, top))
+
+    def lit_index(self):
+        lit = [i for i, spec in enumerate(self.res["meshes"]) if spec[0] == "l"]
+        k = self.r.randrange(len(lit))
+        return k, lit[k]
+
+    def batch_op(self):
+        r = self.r
+        kind = r.choice(["old"] * 14 + ["meshi"] * 4 + ["lmesh"] * 3 + ["lmesh2"] * 2 + ["lmeshi"] * 3 + ["ptri"] * 2)
+        if kind == "old":
+            return super().batch_op()
+        if kind == "ptri":
+            src, spread = self.src(), r.choice(_SPREADS)
+            return ("ptri", src, self.count(self.lim["maxn"], 1, spread), self.seed(), spread, self.texref())
+        if kind == "meshi":
+            i = r.randrange(len(self.res["meshes"]))
+            return ("meshi", i, self.instances(i), self.seed(), r.choice([None, "opaque", "alpha"]), self.src())
+        k, i = self.lit_index()
+        if kind == "lmeshi":
+            return ("lmeshi", k, self.instances(i), self.seed(), r.choice([None, "opaque", "alpha"]), self.src())
+        nseed = self.seed() if r.random() < 0.7 else None
+        if kind == "lmesh":
+            return ("lmesh", k, r.choice(_INSTANCE_MATS), nseed)
+        return ("lmesh2", k, r.choice(_INSTANCE_MATS), nseed, self.seed())
+
+    def five_op(self):
+        r = self.r
+        kind = r.choice(STATE5_OPS + ("lights", "near"))
+        if kind == "near":
+            return ("near", r.choice(NEAR_VALUES + NEAR_VALUES[1:]))
+        if kind == "cull":
+            return ("cull", r.choice([0, 1, 2, 1, 2]))
+        if kind == "mpersp":
+            return ("mpersp", r.random() < 0.7)
+        if kind == "filter":
+            return ("filter", int(r.random() < 0.7))
+        x = r.random()
+        return ("lights", None, 0) if x < 0.1 else ("lights", self.seed(), 0 if x < 0.3 else 8 if x < 0.7 else r.randint(1, 7))
+
+    def op(self, late=False):
+        x = self.r.random()
+        return (self.batch_op() if x < 0.34 else self.prim_op() if x < 0.47 else self.state_op(late) if x < 0.64 else
+                self.five_op() if x < 0.85 else self.other_op())
+
+
 def _even(fmt, v):
     return v + (v & 1) if fmt == "yuv420p" else v
 
@@ -874,10 +1407,46 @@ def make_large_frame(seed, salt, alpha, fmt, keep):
     return (W, H, alpha, knobs, res, ops)
 
 
+def make_small_state_frame(seed, salt, alpha, fmt, keep):
+    r = _rng(seed, f"state/{salt}", alpha, fmt)
+    W, H = _even(fmt, _size(r, 1, 140)), _even(fmt, _size(r, 1, 110))
+    g = _StateGen(r, W, H, SMALL)
+    knobs, res = g.knobs(fmt), g.resources()
+    planned = r.choice(_STATE_NOPS)
+    ops = [g.op(late=k >= planned // 2) for k in range(min(keep, planned))]
+    ops = [("resize", _even(fmt, op[1]), _even(fmt, op[2])) if op[0] == "resize" else op for op in ops]
+    return (W, H, alpha, knobs, res, ops)
+
+
+def make_large_state_frame(seed, salt, alpha, fmt, keep):
+    r = _rng(seed, f"state/{salt}", alpha, fmt)
+    W, H = _even(fmt, _size(r, 64, 700)), _even(fmt, _size(r, 32, 420))
+    g = _StateGen(r, W, H, LARGE)
+    knobs, res = g.knobs(fmt), g.resources()
+    ops = []
+    for _ in range(min(keep, r.randint(1, 4))):
+        for _ in range(r.randint(0, 3)):
+            ops.append(g.five_op())
+        ops.append(g.batch_op())
+        if r.random() < 0.5:
+            ops.append(r.choice([g.prim_op, g.state_op, g.other_op])())
+    return (W, H, alpha, knobs, res, ops)
+
+
 _NOPS = (8, 9, 10, 10, 10, 10, 10, 10)
+_STATE_NOPS = (16, 17, 18, 18, 18, 18, 18, 18)
 _seed = st.integers(0, 2**31 - 1)
 _fmt = st.sampled_from(KNOB_VALUES["fmt"])
 _keep = st.sampled_from([10] * 20 + [5, 2, 1])     # (shrinking cuts a frame's tail)
+_state_keep = st.sampled_from([18] * 20 + [9, 4, 2])
+# hypothesis mixes integer constants (|v| >= 100) from the source of every project module the process has imported
+# into what st.integers draws, so the examples that come from _seed depend on the process's imports (the library
+# binding, say, which a GPU run imports and a CPU run of this file alone does not).  The "small" and "large" examples
+# keep _seed: they are what they are.  The state frames draw their seeds as five digits below 64, which no such
+# constant fits, and are the same examples in every process (tests/test_frame_ops.py checks both statements).
+_digit = st.integers(0, 63)
+_stable_seed = st.builds(lambda a, b, c, d, e: (((a * 64 + b) * 64 + c) * 64 + d) * 64 + e,
+                         _digit, _digit, _digit, _digit, _digit)
 
 
 def small_frames():
@@ -892,16 +1461,35 @@ def large_frames():
     return st.builds(make_large_frame, _seed, _seed, st.booleans(), _fmt, _keep)
 
 
+def small_state_frames():
+    """small_frames' sizes with 1-18 operations: the five sticky states, the
+    instanced, lit and perspective draws that read them (K in 1..6, at most 600
+    triangles per instanced draw) and everything small_frames holds."""
+    return st.builds(make_small_state_frame, _stable_seed, _stable_seed, st.booleans(), _fmt, _state_keep)
+
+
+def large_state_frames():
+    """large_frames' sizes and budget (which counts the instances: K at most 40
+    and at most 4000 triangles per instanced draw), state changes before each
+    of the 1-4 triangle operations."""
+    return st.builds(make_large_state_frame, _stable_seed, _stable_seed, st.booleans(), _fmt, _state_keep)
+
+
 SMALL_EXAMPLES = 200
 LARGE_EXAMPLES = 50
 
 
 def for_each_frame(size, visit):
-    """Calls visit(frame) for the examples of the "small" or "large" frames:
+    """Calls visit(frame) for the examples of the "small", "large",
+    "small-state" or "large-state" frames:
     one inner @given function with fixed settings and derandomize=True, so
     that every caller (the generator's own CPU test and the GPU test) draws
-    exactly the same examples."""
-    strategy, n = {"small": (small_frames(), SMALL_EXAMPLES), "large": (large_frames(), LARGE_EXAMPLES)}[size]
+    the same examples -- the state frames in every process, the "small" and
+    "large" ones in processes that have imported the same project modules
+    (see _stable_seed)."""
+    strategy, n = {"small": (small_frames(), SMALL_EXAMPLES), "large": (large_frames(), LARGE_EXAMPLES),
+                   "small-state": (small_state_frames(), SMALL_EXAMPLES),
+                   "large-state": (large_state_frames(), LARGE_EXAMPLES)}[size]
 
     @settings(max_examples=n, deadline=None, derandomize=True, database=None,
               suppress_health_check=list(HealthCheck))

@@ -1,11 +1,19 @@
 """The frame vocabulary on the oracle alone (no GPU): its lowerings are what
 tests/frame_ops.py claims, and the frames its strategies generate -- exactly
 the examples tests/test_fuzz_mixed_gpu.py runs -- are worth running."""
+import hashlib
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
+import bilinear_ref as B
 import frame_ops as F
+import mesh_clip_ref as MC
 import mesh_ref as MR
+import persp_ref as P
 import scenes
 import textured_ref as T
 
@@ -35,6 +43,108 @@ def test_unshared_mesh_expands_to_its_soup(space):
     assert np.array_equal(uv[:, 0:2], uv[:, 2:4]) and np.array_equal(uv[:, 0:2], uv[:, 4:6])   # one UV per triangle
 
 
+# ---- the lowerings of the state frames ------------------------------------------
+def _constant_uv_batch(n=14, seed=3):
+    """A small soup with one (u, v) per triangle on a 9 x 7 RGBA texture: inside
+    it, past every edge, on texel centres and borders."""
+    tex = scenes.rng(seed).uniform(0, 1, size=(7, 9, 4))
+    b = T.soup(60, 40, n, seed, tex, spread=25.0, ct=(0.9, 0.8, 0.7, 0.5))
+    g = scenes.rng(seed + 1)
+    uv = np.stack([g.uniform(-2, 11, n), g.uniform(-2, 9, n)], axis=1)
+    uv[:4] = [[0.0, 0.0], [8.0, 6.0], [3.5, 2.0], [7.999, 5.999]]
+    return dict(b, uv=np.ascontiguousarray(np.repeat(uv[:, None], 3, axis=1).reshape(n, 6)))
+
+
+@pytest.mark.parametrize("mode", ["zw", "nz"])
+def test_constant_uv_bilinear_is_a_flat_colour(oracle, mode):
+    """frame_ops' lowering (flat draw_triangles of sample_bilinear at the
+    triangle's UV) against bilinear_ref's per-fragment derivations."""
+    b = _constant_uv_batch()
+    ctx = oracle.context(60, 40, True)
+    ctx.set_color(*B.BG)
+    T._set_depth_mode(ctx, mode)
+    if mode != "nz":
+        ctx.clear_depth(B.CLEAR)
+    ctx.set_transform(*b["m"])
+    ctx.set_color_transform(*b["ct"])
+    flat = F.textured_colours(b["tex"], b["uv"], 1)
+    assert not scenes.bits_equal(flat, F.textured_colours(b["tex"], b["uv"], 0))
+    ctx.draw_triangles(b["xy"], flat, z=b["z"], gouraud=False)
+    got = ctx.get_buffer_numpy()
+    info = {}
+    want, depth = B.expected_loop(60, 40, True, B.BG, mode, B.CLEAR, [b], info)
+    assert info["covered"].mean() > 0.3
+    assert scenes.bits_equal(got, want)
+    if mode != "nz":
+        assert scenes.bits_equal(ctx.get_depth_buffer(), depth)
+        opaque = dict(b, tex=np.ascontiguousarray(b["tex"][..., :3]), ct=(0.9, 0.8, 0.7, 1.0))
+        ctx = oracle.context(60, 40, False)
+        ctx.set_color(*B.BG)
+        T._set_depth_mode(ctx, mode)
+        ctx.clear_depth(B.CLEAR)
+        ctx.set_transform(*opaque["m"])
+        ctx.set_color_transform(*opaque["ct"])
+        ctx.draw_triangles(opaque["xy"], F.textured_colours(opaque["tex"], opaque["uv"], 1), z=opaque["z"], gouraud=False)
+        want, depth = B.expected_payload(60, 40, False, B.BG, mode, B.CLEAR, [opaque])
+        assert scenes.bits_equal(ctx.get_buffer_numpy(), want) and scenes.bits_equal(ctx.get_depth_buffer(), depth)
+
+
+def test_power_of_two_q_returns_the_uv_bit_for_bit():
+    g = scenes.rng(21)
+    u = np.concatenate([g.uniform(-1e6, 1e6, 4000), g.uniform(-3, 43, 4000), 10.0 ** g.uniform(-200, 200, 2000),
+                        [0.0, -0.0, 1.0, 36.999999999999996]])
+    v = g.permutation(u)
+    for q in F.Q_VALUES:
+        qs = np.full(u.shape, q)
+        U, V = u * qs, v * qs                       # the payload products, constant over the triangle
+        gu, gv = P.persp_uv(U, V, qs)
+        assert scenes.bits_equal(gu, u) and scenes.bits_equal(gv, v)
+    xy, z, uv, q = F.perspective_soup(50, 97, 61, 5, 40.0, (37, 23))
+    assert set(np.unique(q)) <= set(F.Q_VALUES) and len(np.unique(q)) == len(F.Q_VALUES)
+    assert (q == q[:, :1]).all() and (uv.reshape(-1, 3, 2) == uv.reshape(-1, 3, 2)[:, :1]).all()
+    px, py = np.meshgrid(np.arange(0.5, 97, 7.0), np.arange(0.5, 61, 5.0))
+    for t in range(50):                             # and through the whole per-fragment expression
+        fu, fv, _, _ = P.fragment_uv(xy[t], uv[t], q[t], T.IDENT, px.ravel(), py.ravel())
+        ok = np.isfinite(fu)
+        assert ok.any() and (fu[ok] == uv[t, 0]).all() and (fv[ok] == uv[t, 1]).all()
+
+
+def test_affine_matrices_give_q_exactly_one():
+    for spec in (("tu", "model", 40, 7, 1.0), ("tu", "screen", 40, 8, 0.3), ("ts", "model", 4, 5, 9)):
+        mesh = F.mesh_dict(spec, 97, 61)
+        mats = [F.mesh_matrix(spec[1], m, 97, 61) for m in range(4)]
+        labels, inst = F.instance_matrices(spec[1], 12, 5, 97, 61)
+        mats += list(zip(labels, inst))
+        assert {lab for lab, _ in mats} >= ({"affine", "perspective"} if spec[1] == "model" else {"none", "ident"})
+        for label, M in mats:
+            q = P.expand_q(mesh, M)[3]
+            if label == "perspective":
+                assert not (q == 1.0).all()
+            else:
+                assert scenes.bits_equal(q, np.ones_like(q)), label
+                for near in F.NEAR_VALUES:          # cw == 1 >= every near plane: nothing is cut, q stays 1
+                    cq = P.clip_soup_q(mesh, M, near, 1, True)[3]
+                    assert scenes.bits_equal(cq, np.ones_like(cq))
+
+
+def test_a_cut_vertex_of_a_constant_uv_triangle_keeps_its_uv():
+    spec = ("tu", "model", 150, 11, 1.0)
+    mesh = F.mesh_dict(spec, 97, 61)
+    M = MR.behind_eye(97, 61)
+    full = MR.expand(mesh, M)[2]
+    cut = 0
+    for near in F.NEAR_VALUES[1:]:
+        info = {}
+        xy, z, uv, counts = MC.clip_soup(mesh, M, near, 0, info)
+        inside = info["inside"]
+        cut += int(((inside == 1) | (inside == 2)).sum())
+        src = np.repeat(np.arange(150), counts)     # the source triangle of every output triangle
+        assert scenes.bits_equal(uv, np.ascontiguousarray(full[src]))
+        assert (uv.reshape(-1, 3, 2) == uv.reshape(-1, 3, 2)[:, :1]).all()
+    assert cut >= 20, "the near planes cut too few triangles to show anything"
+
+
+# ---- the interpreter ---------------------------------------------------------------
 FIXED = (97, 61, True, F.KNOBS_OFF,
          dict(texs=[(9, 7, 4, "u8", 5, None), (20, 11, 3, "f64", 6, (5, 4))],
               bufs=[("c", 40, 1, 40.0, True, False), ("t", 30, 2, 40.0, "const")],
@@ -54,13 +164,105 @@ def test_run_on_the_oracle_is_deterministic(oracle):
     bare = F.run(oracle, FIXED, triangles=False)
     assert bare["batches"] == [] and not scenes.bits_equal(bare["f64"], a["f64"])
     assert F.kinds(FIXED) <= set(F.ALL_KINDS)
+    _state_operations_are_deterministic(oracle)
+
+
+STATE_FIXED = (97, 61, True, F.KNOBS_OFF,
+               dict(texs=[(9, 7, 4, "u8", 5, None), (20, 11, 3, "f64", 6, None)], bufs=[("t", 30, 2, 40.0, "free")],
+                    meshes=[("l", "model", 4, 6, 3, True, False), ("tu", "model", 20, 4, 0.3), ("ts", "screen", 3, 3, 8),
+                            ("c", "screen", 3, 4, 9, False, True)]),
+               [("lights", 4, 8), ("near", 0.5), ("cull", 2), ("lmesh", 0, 2, 12), ("mpersp", True), ("filter", 1),
+                ("mesh", 1, 1, ("res", 0)), ("mesh", 1, 0, ("res", 1)), ("mesh", 2, 1, ("res", 0)), ("buf", 0, ("res", 0)),
+                ("meshi", 1, 3, 21, None, "host"), ("meshi", 3, 4, 22, "alpha", "dev8"), ("lights", 5, 0),
+                ("lmesh2", 0, 1, None, 13), ("near", F.NEAR_VALUES[2]), ("cull", 1), ("lmeshi", 0, 5, 23, "opaque", "dev"),
+                ("ptri", "dev8", 30, 24, 40.0, ("res", 1)), ("lights", None, 0), ("lmeshi", 0, 2, 24, "alpha", "host"),
+                ("filter", 0), ("near", 0.0), ("cull", 0), ("mpersp", False), ("mesh2", 0, 2, ("res", 0), 14)])
+
+
+def _state_operations_are_deterministic(oracle):
+    """The same for a frame that uses every operation of the state vocabulary."""
+    a, b = F.run(oracle, STATE_FIXED), F.run(oracle, STATE_FIXED)
+    assert F.mismatches(a, b) == [] and a["batches"] == b["batches"] and a["counts"] == b["counts"]
+    assert len(a["counts"]) == 12 and {k for k, _, _ in a["batches"]} == {"mesh", "textured", "instanced", "lit"}
+    assert any(got < full for full, got in a["counts"]) and any(got > 0 for _, got in a["counts"])
+    bare = F.run(oracle, STATE_FIXED, triangles=False)
+    assert bare["batches"] == [] and not scenes.bits_equal(bare["f64"], a["f64"])
+    used = F.kinds(STATE_FIXED)
+    assert used <= set(F.ALL_KINDS) and set(F.STATE_KINDS) <= used, set(F.STATE_KINDS) - used
+    # every state reaches the frame: the same operations with the five setters left out draw another one
+    plain = STATE_FIXED[:5] + ([op for op in STATE_FIXED[5] if op[0] not in F.STATE5_OPS],)
+    assert not scenes.bits_equal(F.run(oracle, plain)["f64"], a["f64"])
+    stats = F.state_stats(STATE_FIXED)
+    assert stats == dict(two_states=True, changed_between=True, meets_others=True)
+
+
+def _digest(size):
+    frames = []
+    F.for_each_frame(size, frames.append)
+    return hashlib.sha256(repr(frames[:20]).encode()).hexdigest()
+
+
+_DIGESTS = """
+import hashlib, sys
+sys.path[:0] = [{tests!r}, {root!r}]
+for name in {imports!r}:
+    __import__(name)
+import frame_ops as F
+for size in ("small", "large", "small-state", "large-state"):
+    frames = []
+    F.for_each_frame(size, frames.append)
+    print(size, hashlib.sha256(repr(frames[:20]).encode()).hexdigest())
+"""
+
+
+def _fresh_digests(imports=()):
+    """{size: digest of repr of the first 20 frames} in a fresh interpreter that
+    imports `imports`, then frame_ops."""
+    tests = os.path.dirname(os.path.abspath(__file__))
+    code = _DIGESTS.format(tests=tests, root=os.path.dirname(tests), imports=tuple(imports))
+    out = subprocess.run([sys.executable, "-c", code], check=True, capture_output=True, text=True).stdout
+    return dict(line.split() for line in out.splitlines())
+
+
+def test_the_old_example_streams_are_what_they_were():
+    """The "small" and "large" examples are the regression record.  Their
+    makers are pure functions of the five drawn arguments, pinned here on a
+    fixed argument list.  What hypothesis draws for those arguments depends on
+    the integer constants in the project modules a process has imported
+    (frame_ops.py, at _stable_seed), so the digest of the first 20 examples is
+    pinned where that set is fixed: in a fresh interpreter that imports
+    frame_ops alone.  All four digests are the parent commit's, computed
+    before the state frames were added."""
+    pure = {}
+    for name, make in (("small", F.make_small_frame), ("large", F.make_large_frame)):
+        frames = [make(1000003 * s + 17, 7 * s + 1, bool(s & 1), F.KNOB_VALUES["fmt"][s % 3], 10) for s in range(20)]
+        pure[name] = hashlib.sha256(repr(frames).encode()).hexdigest()
+    assert pure == dict(small="fecaaa06a176d2bf2229951e96797e706d3a20c18e9db91a7fa3917a76184d57",
+                        large="57f693796f265a5449e5a519d3d86c4a8cd9c954b77e9b22845ee2a74c35e62a")
+    alone = _fresh_digests()
+    assert alone["small"] == "b74c46a1eb7793abbb0177b2555ef9a0f79a222212dd31de4fe1bfeff9ddcdae"
+    assert alone["large"] == "07effb809ee42c79aed22c9026ae5340ef15728ec0bd561e69d063a638c5c628"
+
+
+def test_the_state_examples_are_the_same_in_every_process():
+    """The CPU test below vouches for the examples the GPU tests run only if
+    both draw the same ones: whatever this process has imported, and in a
+    fresh interpreter with and without the library's binding and the largest
+    GPU test module imported first."""
+    here = {size: _digest(size) for size in ("small-state", "large-state")}
+    alone = _fresh_digests()
+    other = _fresh_digests(("libnativecpurenderer_amd.libNativeCPURendererPybind", "test_parity_gpu"))
+    for size, digest in here.items():
+        assert alone[size] == digest and other[size] == digest, size
+    # (the old examples do move with the imports: the reason the state frames draw their seeds differently)
+    assert (other["small"], other["large"]) != (alone["small"], alone["large"])
 
 
 def _fraction(flags):
     return sum(bool(f) for f in flags) / max(len(flags), 1)
 
 
-@pytest.mark.parametrize("size", ["small", "large"])
+@pytest.mark.parametrize("size", ["small", "large", "small-state", "large-state"])
 def test_generated_frames_are_worth_running(oracle, size):
     """The examples of the GPU property tests (the same strategies, settings
     and derandomize=True, frame_ops.for_each_frame), on the oracle only."""
@@ -75,13 +277,15 @@ def test_generated_frames_are_worth_running(oracle, size):
             changed.append(not scenes.bits_equal(out["f64"], bare["f64"]))
 
     F.for_each_frame(size, visit)
-    assert len(frames) >= {"small": 150, "large": 20}[size]
+    assert len(frames) >= {"small": 150, "large": 20}[size.split("-")[0]]
     assert all(finite), "an oracle frame holds a NaN or an infinity"
     report = {}
-    if size == "small":
+    if size.startswith("small"):
+        # (the old frames: the kinds they were written for; the state frames: every kind)
+        wanted = F.BASE_KINDS if size == "small" else F.ALL_KINDS
         used = [F.kinds(fr) for fr in frames]
-        assert set().union(*used) <= set(F.ALL_KINDS)
-        for k in F.ALL_KINDS:
+        assert set().union(*used) <= set(wanted)
+        for k in wanted:
             report[k] = _fraction([k in u for u in used])
         low = {k: v for k, v in report.items() if v < 0.10}
         assert not low, f"operation kinds in fewer than 10 % of the frames: {low}"
@@ -93,5 +297,29 @@ def test_generated_frames_are_worth_running(oracle, size):
         assert mixed >= 0.30, f"{mixed:.0%} of the frames mix triangle kinds in one depth buffer"
         four = _fraction([F.batch_kinds(fr)[1] >= 4 for fr in frames])
         assert four >= 0.25, f"{four:.0%} of the frames hold four or more triangle batches"
+    if size == "small-state":
+        stats = [F.state_stats(fr) for fr in frames]
+        two = _fraction([s["two_states"] for s in stats])
+        assert two >= 0.30, f"{two:.0%} of the frames hold a mesh draw under two or more non-default states"
+        between = _fraction([s["changed_between"] for s in stats])
+        assert between >= 0.20, f"{between:.0%} of the frames change a state between two unsynchronised batches"
+        meets = _fraction([s["meets_others"] for s in stats])
+        assert meets >= 0.25, f"{meets:.0%} of the frames hold a lit or instanced draw beside another kind"
+    if size.endswith("-state"):         # the sizes the state frames promise
+        for fr in frames:
+            meshes = fr[4]["meshes"]
+            tri = [m[2] if m[0] == "tu" else 2 * m[2] * m[3] for m in meshes]
+            lit = [t for m, t in zip(meshes, tri) if m[0] == "l"]
+            for op in fr[5]:
+                if op[0] in ("meshi", "lmeshi"):
+                    n = tri[op[1] % len(tri)] if op[0] == "meshi" else lit[op[1] % len(lit)]
+                    if size == "small-state":
+                        assert 1 <= op[2] <= 6 and (op[2] == 1 or op[2] * n <= 600) and n <= 200
+                        assert fr[0] <= 140 and fr[1] <= 110
+                    else:
+                        assert 1 <= op[2] <= 40 and (op[2] == 1 or op[2] * n <= 4000)
+                        assert op[2] == 1 or op[2] * 1.2 * fr[0] * fr[1] <= F.LARGE["budget"]
+                if op[0] == "lights":
+                    assert 0 <= op[2] <= 8
     assert len(changed) >= len(frames) // 2
     assert _fraction(changed) >= 0.80, f"the triangles change {_fraction(changed):.0%} of the frames that hold some"

@@ -3,16 +3,20 @@ CPU oracle bit for bit: f64 framebuffer, u32 depth, u8 readback, the frame
 output (u8 image / YUV420P planes) and every mid-frame probe.
 
 A frame is plain data of tests/frame_ops.py's vocabulary (colour soups from
-host arrays, TriangleBuffers and device arrays; textured soups; indexed meshes
-with update_positions; primitives, textures, pixels; snapshots of the frame
-and of an auxiliary context; state; probes; command recording; the frame
-output; the testing knobs of the rasters), run by its one interpreter on the
-library and on the oracle.  frame_ops.py states how the oracle, which has no
+host arrays, TriangleBuffers and device arrays; textured soups, with q too;
+indexed meshes with update_positions, instanced with tints, lit, lit and
+instanced; the five sticky states those draws read -- near plane, cull mode,
+mesh perspective, texture filter, lights; primitives, textures, pixels;
+snapshots of the frame and of an auxiliary context; state; probes; command
+recording; the frame output; the testing knobs of the rasters), run by its one
+interpreter on the library and on the oracle.  frame_ops.py states how the oracle, which has no
 textured draw, mesh, buffer or recording, runs each operation;
 tests/test_frame_ops.py checks the lowerings and that the generated frames
 are worth running, on exactly the examples drawn here.
 
-Two property tests draw the frames (hypothesis, derandomized); the fixed
+Four property tests draw the frames (hypothesis, derandomized: the "small" and
+"large" examples, which never change, and the "small-state" and "large-state"
+ones, which add the states and the draws that read them); the fixed
 sequences below them are the hand-offs between kinds named one by one, in the
 same data, so that a failing fuzz frame (printed with its knobs) can be added
 as one more entry of FIXED.
@@ -24,6 +28,11 @@ Running time, measured with --durations on one MI355X (call phase, two runs):
     test_random_mixed_large_frames_match_oracle                     0.62 s (50 examples)
 The example counts (frame_ops.SMALL_EXAMPLES = 200, LARGE_EXAMPLES = 50) are above the floor of 150 small and 20
 large frames and keep each test shorter than its old counterpart; each fixed sequence takes about 10 ms.
+The state frames beside the frames above, in one session each (call phase, two sessions):
+    test_random_mixed_frames_match_oracle                           1.40 s, 1.15 s (200 examples)
+    test_random_state_frames_match_oracle                           2.08 s, 1.76 s (200 examples, up to 18 operations)
+    test_random_mixed_large_frames_match_oracle                     0.74 s, 0.60 s (50 examples)
+    test_random_large_state_frames_match_oracle                     0.75 s, 0.72 s (50 examples)
 """
 import hypothesis  # noqa: F401  (a missing package fails the module: these tests never skip)
 import pytest
@@ -43,6 +52,7 @@ class Reached:
         self.paths = set()          # (triangle kind, raster path)
         self.warm = 0
         self.over_cap = 0           # frames under set_pair_capacity_override(50) with a batch of more pairs
+        self.changed_over_cap = 0   # ... where one of the five sticky states changed before the next synchronisation
         self.frames = 0
 
     def note(self, frame, got):
@@ -50,12 +60,16 @@ class Reached:
         self.paths |= {(kind, path) for kind, path, _ in got["batches"]}
         self.warm += got["warm"] > 0
         self.over_cap += frame[3]["paircap"] == 50 and any(pairs > 50 for _, _, pairs in got["batches"])
+        self.changed_over_cap += frame[3]["paircap"] == 50 and got["changed_over_cap"] > 0
 
-    def check(self):
-        want = {(k, p) for k in ("colour", "textured", "mesh") for p in ("order-free", "ordered")}
+    def check(self, states=False):
+        kinds = ("colour", "textured", "mesh") + (("instanced", "lit") if states else ())
+        want = {(k, p) for k in kinds for p in ("order-free", "ordered")}
         assert want <= self.paths, f"never reached: {sorted(want - self.paths)}"
         assert self.warm > 0, "no frame with a warm batch"
         assert self.over_cap > 0, "no frame overflowed the pair capacity of 50"
+        if states:
+            assert self.changed_over_cap > 0, "no sticky state changed while an overflowed batch could be pending"
 
 
 def _compare(gpu, oracle, frame, reached=None):
@@ -66,6 +80,7 @@ def _compare(gpu, oracle, frame, reached=None):
         print("mismatching frame:", repr(frame))
     assert not bad, (bad, frame)
     assert [b[0] for b in got["batches"]] == [b[0] for b in want["batches"]]
+    assert got["counts"] == want["counts"]
     if reached is not None:
         reached.note(frame, got)
     return got
@@ -83,6 +98,20 @@ def test_random_mixed_large_frames_match_oracle(gpu, oracle):
     F.for_each_frame("large", lambda fr: _compare(gpu, oracle, fr, reached))
     assert reached.frames >= 20
     reached.check()
+
+
+def test_random_state_frames_match_oracle(gpu, oracle):
+    reached = Reached()
+    F.for_each_frame("small-state", lambda fr: _compare(gpu, oracle, fr, reached))
+    assert reached.frames >= 150
+    reached.check(states=True)
+
+
+def test_random_large_state_frames_match_oracle(gpu, oracle):
+    reached = Reached()
+    F.for_each_frame("large-state", lambda fr: _compare(gpu, oracle, fr, reached))
+    assert reached.frames >= 20
+    reached.check(states=True)
 
 
 # ---- fixed sequences -----------------------------------------------------------
@@ -118,6 +147,25 @@ def _fast_clear(batch1, batch2):
             [BG, ("cleardepth", 0xFFFFFFF0), ("transform", TWO_TILES), batch1, ("transform", IDENT),
              ("tex", ("res", 1), [-5.0, -4.0, 210.0, 150.0]), ("getcolor", 190.0, 130.0),
              ("transform", TWO_TILES), batch2, ("readdepth",)])
+
+
+LIT_MESH = ("l", "model", 8, 12, 3, True, False)          # 192 triangles
+TU_MESH = ("tu", "model", 40, 7, 0.3)
+
+
+def _states_survive(fmt):
+    res = dict(texs=[RGB_TEX], bufs=[], meshes=[LIT_MESH, TU_MESH])
+    return (_knobs(fmt=fmt, coop=2), res,
+            [("lights", 4, 8), ("near", 0.5), ("cull", 2), ("mpersp", True), ("filter", 1),
+             ("save", [0.0] * 4), ("resize", 150, 100), ("restore", [0.0] * 4), BG,
+             ("meshi", 1, 3, 31, None, "host"), ("lmesh", 0, 2, 12), ("lmesh2", 0, 1, None, 13),
+             ("lmeshi", 0, 3, 32, "alpha", "dev8"), ("ptri", "dev", 80, 33, 40.0, ("res", 0))])
+
+
+def _tinted_lit_between_instanced(test, write):
+    return (_knobs(), dict(texs=[], bufs=[], meshes=[LIT_MESH]),
+            [("depthstate", test, write), ("lights", 4, 3), ("meshi", 0, 4, 41, "opaque", "host"),
+             ("lmeshi", 0, 4, 42, "alpha", "host"), ("meshi", 0, 4, 43, None, "dev")])
 
 
 _TEXTURED = ("ttri", "host", 300, 21, 40.0, "const", ("res", 0))
@@ -176,6 +224,28 @@ FIXED = {
         _knobs(), dict(texs=[RGB_TEX], bufs=[("c", 120, 71, 40.0, True, False)], meshes=[GOURAUD_MESH]),
         [("mesh2", 0, 1, ("res", 0), 72), ("buf2", 0, ("res", 0), 0.0), ("resize", 150, 100),
          ("mesh", 0, 1, ("res", 0)), ("buf", 0, ("res", 0))]),
+    # the mesh staging regrown by a larger draw, then reused by a smaller one, while the lit draw that filled it
+    # first is re-run; lights, near plane and cull mode change while that draw is pending
+    "lit_rerun_after_the_staging_regrows_and_shrinks": (
+        _knobs(paircap=50), dict(texs=[RGB_TEX], bufs=[], meshes=[LIT_MESH, ("c", "model", 10, 10, 4, True, False), TU_MESH]),
+        [("lights", 4, 3), ("lmesh", 0, 1, 12), ("lights", 5, 8), ("near", 0.5), ("cull", 1),
+         ("meshi", 1, 5, 31, "opaque", "host"), ("mesh", 2, 2, ("res", 0))]),
+    "recorded_filter_and_perspective_flushed_once": (
+        _knobs(record=True), dict(texs=[RGB_TEX], bufs=[("t", 120, 32, 40.0, "const")], meshes=[TU_MESH]),
+        [("buf", 0, ("res", 0)), ("filter", 1), ("mpersp", True), ("mesh", 0, 0, ("res", 0)), ("filter", 0),
+         ("ptri", "host", 100, 33, 40.0, ("res", 0))]),
+    "states_survive_save_resize_restore_clear": _states_survive("yuv420p"),
+    "tinted_lit_instances_between_instanced_test_write": _tinted_lit_between_instanced(True, True),
+    "tinted_lit_instances_between_instanced_test_only": _tinted_lit_between_instanced(True, False),
+    "tinted_lit_instances_between_instanced_depth_off": _tinted_lit_between_instanced(False, False),
+    # a textured buffer drawn warm under another filter than the draw that left its tile lists
+    "warm_textured_buffer_across_filter_changes": (
+        _knobs(warm=1), dict(texs=[RGB_TEX], bufs=[("t", 120, 32, 40.0, "const")], meshes=[]),
+        [("buf", 0, ("res", 0)), ("filter", 1), ("buf", 0, ("res", 0)), ("cleardepth", 0xFFFFFFFF), ("filter", 0),
+         ("buf", 0, ("res", 0)), ("filter", 1), ("buf", 0, ("res", 0))]),
+    "lit_mesh_updated_while_its_draw_is_pending": (
+        _knobs(paircap=50), dict(texs=[], bufs=[], meshes=[LIT_MESH]),
+        [("lights", 4, 3), ("lmesh2", 0, 1, 12, 13), ("readdepth",)]),
 }
 
 
@@ -197,6 +267,24 @@ def _expect(name, frame, got):
         assert (got["depth"][:32, :64] != 0xFFFFFFF0).any()
     if name.startswith("texture_shared"):
         assert paths == ["order-free"] if not frame[2] else paths == ["ordered"]
+    kinds, counts = [k for k, _, _ in got["batches"]], got["counts"]
+    if name.startswith("lit_rerun"):
+        assert kinds == ["lit", "instanced", "mesh"] and pairs[0] > 50 and got["changed_over_cap"] == 3
+        assert counts[0] == (192, 192) and counts[1][0] == 1000 and counts[2][0] == 40      # regrown, then smaller
+        assert 0 < counts[1][1] != 1000 and 0 < counts[2][1] != 40                          # both under the clip stage
+    if name.startswith("recorded_filter"):
+        assert frame[3]["record"] and not any(op[0] in ("flush", "end") for op in frame[5])
+        assert kinds == ["textured", "mesh", "textured"] and counts == [(40, 40)]
+    if name.startswith("states_survive"):
+        assert kinds == ["instanced", "lit", "lit", "lit", "lit", "textured"]
+        assert got["f64"].shape[:2] == (100, 150) and frame[3]["coop"] == 2 and "frame" in got
+        assert all(0 < n < full for full, n in counts)         # near plane and cull mode reached every mesh draw
+    if name.startswith("tinted_lit"):
+        assert kinds == ["instanced", "lit", "instanced"] and paths == ["order-free", "ordered", "order-free"]
+    if name.startswith("warm_textured"):
+        assert kinds == ["textured"] * 4 and got["warm"] >= 2
+    if name.startswith("lit_mesh_updated"):
+        assert kinds == ["lit", "lit"] and min(pairs) > 50
 
 
 @pytest.mark.parametrize("alpha", [False, True], ids=["rgb", "rgba"])
