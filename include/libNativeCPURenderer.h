@@ -292,6 +292,37 @@ bool AssembleMeshLit(RenderContext* ctx, Mesh* m, const f64* matrix16, const f64
 bool AssembleMeshLitInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* normals, const f64* tint,
                               i64 K, i64 cap, f64* xy_out, f64* z_out, f64* attr_out, i64* n_out);   /* NEW: the same
                                  for a DrawMeshLitInstanced, in AssembleMeshInstanced's conventions without q */
+/* NEW: skinned meshes (DESIGN §3 "Skinned meshes"): linear-blend skinning on the device.  A MeshSkin keeps a bind
+   pose -- nv positions, optionally nv normals, four joints (u32) and four weights (f64) per vertex, for nb bones --
+   and PoseMesh rewrites a mesh's positions (and normals) from it under a palette of nb row-major 3x4 matrices
+   [R | t], 12 doubles each, by one kernel.  Per vertex, in f64, every product and sum rounded in the order written
+   (no FMA, no division, no sqrt, no renormalisation), with B_k = palette[j_k], k = 0 .. 3, all four evaluated:
+     x_k = ((B_k[0]*px + B_k[1]*py) + B_k[2]*pz) + B_k[3]   (y_k: entries 4..7, z_k: entries 8..11)
+     X   = ((w0*x_0 + w1*x_1) + w2*x_2) + w3*x_3            (Y, Z likewise)
+     a_k = (B_k[0]*nx + B_k[1]*ny) + B_k[2]*nz              (b_k: entries 4..6, c_k: entries 8..10; no translation)
+     NX  = ((w0*a_0 + w1*a_1) + w2*a_2) + w3*a_3            (NY, NZ likewise)
+   Posing always starts from the bind pose.  Weights are not validated; every joint, zero-weight ones included,
+   must be < nb (checked at creation).  The normals are rewritten when the mesh is lit AND the skin has bind
+   normals; otherwise a lit mesh keeps its own.  Draws issued before a Pose call keep the old pose, draws issued
+   after it see the new one, on any context of the device, and the host waits for nothing.  Every existing mesh
+   draw works on the posed mesh unchanged.  Each error latches a message under the entry point's name and changes
+   nothing: NULL arguments, nb <= 0 or beyond 32 bits, a joint >= nb, a mesh and a skin of different vertex counts,
+   mesh, skin and context not all on one device.  nv == 0 is valid and does nothing. */
+typedef struct MeshSkin MeshSkin;
+MeshSkin* CreateMeshSkin(i64 nv, const f64* bindPos, const f64* bindNormal, const uint32_t* joints,
+                         const f64* weights, i64 nb);                    /* NEW: bindNormal NULL: positions only;
+                                 joints and weights nv*4; host arrays, the caller's again on return */
+void DestroyMeshSkin(MeshSkin* s);                                       /* NEW: waits for the device's stream */
+i64 GetMeshSkinBoneCount(MeshSkin* s);                                   /* NEW */
+void SetMeshSkinVariant(MeshSkin* s, i64 mode);                          /* NEW (A/B and tests): the skin kernel 0 auto,
+                                 1 palette from global memory, 2 staged in LDS (nb <= 128); the same bits */
+bool PoseMesh(RenderContext* ctx, Mesh* m, MeshSkin* s, const f64* palette);   /* NEW: host palette nb*12, the
+                                 caller's again on return (one asynchronous copy through a pinned buffer) */
+bool PoseMeshDevice(RenderContext* ctx, Mesh* m, MeshSkin* s, const f64* palette);   /* NEW: device pointer, 16-byte
+                                 aligned, valid and unchanged until the call's kernel has executed; read only by it */
+bool GetMeshPositions(Mesh* m, f64* out);                                /* NEW: nv*3 to the host; a sync point */
+bool GetMeshNormals(Mesh* m, f64* out);                                  /* NEW: a lit mesh only (else false, error
+                                 latched) */
 void SetFragmentCounting(RenderContext* ctx, bool on);                   /* NEW: covered-fragment counter */
 i64 GetFragmentCount(RenderContext* ctx);                                /* NEW */
 i64 GetLastRasterPath(RenderContext* ctx);                               /* NEW: 1 order-free tiled, 2 ordered */

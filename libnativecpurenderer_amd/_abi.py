@@ -117,6 +117,14 @@ DEVICE_ABI = {
     "DrawMeshLitInstancedDevice": (None, (P, P, P, P, P, L)),
     "AssembleMeshLit": (B, (P, P, P, P, L, P, P, P, P)),
     "AssembleMeshLitInstanced": (B, (P, P, P, P, P, L, L, P, P, P, P)),
+    "CreateMeshSkin": (P, (L, P, P, P, P, L)),
+    "DestroyMeshSkin": (None, (P,)),
+    "GetMeshSkinBoneCount": (L, (P,)),
+    "SetMeshSkinVariant": (None, (P, L)),
+    "PoseMesh": (B, (P, P, P, P)),
+    "PoseMeshDevice": (B, (P, P, P, P)),
+    "GetMeshPositions": (B, (P, P)),
+    "GetMeshNormals": (B, (P, P)),
     "SetFragmentCounting": (None, (P, B)),
     "GetFragmentCount": (L, (P,)),
     "GetLastRasterPath": (L, (P,)),

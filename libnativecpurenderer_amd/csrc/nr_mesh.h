@@ -1,0 +1,47 @@
+// nr_mesh.h — what the mesh front end (nr_mesh.hip) and the skin pass
+// (nr_skin.hip) share: the Mesh handle and the pinned hand-off buffers of a
+// host call's small per-draw arrays.
+#pragma once
+#include "nr_tri.h"
+
+struct Mesh {
+    i64 nv = 0, n = 0;
+    int mode = nrtri::ATTR_FLAT;   // AttrMode of the expanded attributes
+    bool opaque = false;           // colour mesh: every vertex alpha == 1 (textured: decided per draw by the texture)
+    int device = 0;
+    f64* pos = nullptr;            // nv*3
+    u32* idx = nullptr;            // n*3, every entry < nv (checked on the host at creation)
+    f64* attr = nullptr;           // expanded: n*12 Gouraud, n*4 flat (the colour of i0), n*6 textured
+    // a lit mesh (CreateLitMesh) also keeps what the light pass reads: the per-vertex colours and normals
+    bool lit = false;
+    f64* rgba = nullptr;           // nv*4 (with n > 0)
+    f64* normal = nullptr;         // nv*3
+};
+// pos and normal are read only by the vertex, clip-vertex and light kernels that a draw or Assemble* call
+// launches on the device's main stream (nr_stream_for), and rgba only by the light kernels: a pending batch, or
+// its overflow re-run, reads the context's staging and the expanded attr.  So a kernel on that stream that
+// rewrites pos or normal (PoseMesh, nr_skin.hip) is ordered between the draws around it with no host wait.
+
+// One of the context's two pinned buffers (TriScratch::h_minst), in turn, grown to `need` doubles, for the next
+// asynchronous host-to-device copy of a call's matrices: the host waits only for the copy of the call before
+// last, long done.  The caller fills it, enqueues its copy on the context's stream and records
+// sc.evMinst[*slot] behind it.  Null: hipHostMalloc failed (nothing latched).
+inline f64* nr_mesh_pinned(TriScratch& sc, size_t need, int* slot) {
+    const int k = sc.minstNext;
+    sc.minstNext ^= 1;
+    if (sc.evMinst[k]) NR_CHECK(hipEventSynchronize(sc.evMinst[k]));
+    else NR_CHECK(hipEventCreateWithFlags(&sc.evMinst[k], hipEventDisableTiming));
+    if (sc.h_minst_cap[k] < need) {
+        if (sc.h_minst[k]) NR_CHECK(hipHostFree(sc.h_minst[k]));
+        sc.h_minst[k] = nullptr;
+        sc.h_minst_cap[k] = 0;
+        if (hipHostMalloc((void**)&sc.h_minst[k], need * sizeof(f64)) != hipSuccess) {
+            (void)hipGetLastError();
+            sc.h_minst[k] = nullptr;
+            return nullptr;
+        }
+        sc.h_minst_cap[k] = need;
+    }
+    *slot = k;
+    return sc.h_minst[k];
+}

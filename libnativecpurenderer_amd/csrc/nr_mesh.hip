@@ -47,7 +47,7 @@
 // k_minst_light), whose output -- a per-draw vertex-colour table in the staging,
 // never in the mesh -- feeds the assembly, clip and instancing passes in place
 // of the mesh's own colours.  Unlit draws run none of it.
-#include "nr_tri.h"
+#include "nr_mesh.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -56,20 +56,6 @@
 #include <cstring>
 #include <initializer_list>
 #include <string>
-
-struct Mesh {
-    i64 nv = 0, n = 0;
-    int mode = nrtri::ATTR_FLAT;   // AttrMode of the expanded attributes
-    bool opaque = false;           // colour mesh: every vertex alpha == 1 (textured: decided per draw by the texture)
-    int device = 0;
-    f64* pos = nullptr;            // nv*3
-    u32* idx = nullptr;            // n*3, every entry < nv (checked on the host at creation)
-    f64* attr = nullptr;           // expanded: n*12 Gouraud, n*4 flat (the colour of i0), n*6 textured
-    // a lit mesh (CreateLitMesh) also keeps what the light pass reads: the per-vertex colours and normals
-    bool lit = false;
-    f64* rgba = nullptr;           // nv*4 (with n > 0)
-    f64* normal = nullptr;         // nv*3
-};
 
 namespace nrtri {
 namespace {
@@ -975,22 +961,9 @@ bool upload_instances(RenderContext* ctx, const f64* matrices, const f64* tint, 
     TriScratch& sc = ctx->tri;
     const size_t k = (size_t)K, ntint = tint ? k * 4 : 0, need = k * 16 + ntint + (normals ? k * 9 : 0);
     if (!sc.minst.ensure(need)) return false;
-    const int slot = sc.minstNext;   // two pinned buffers in turn: the wait is for the copy of the draw before last
-    sc.minstNext ^= 1;
-    if (sc.evMinst[slot]) NR_CHECK(hipEventSynchronize(sc.evMinst[slot]));
-    else NR_CHECK(hipEventCreateWithFlags(&sc.evMinst[slot], hipEventDisableTiming));
-    if (sc.h_minst_cap[slot] < need) {
-        if (sc.h_minst[slot]) NR_CHECK(hipHostFree(sc.h_minst[slot]));
-        sc.h_minst[slot] = nullptr;
-        sc.h_minst_cap[slot] = 0;
-        if (hipHostMalloc((void**)&sc.h_minst[slot], need * sizeof(f64)) != hipSuccess) {
-            (void)hipGetLastError();
-            sc.h_minst[slot] = nullptr;
-            return fail("instanced mesh draw", "hipHostMalloc failed");
-        }
-        sc.h_minst_cap[slot] = need;
-    }
-    f64* h = sc.h_minst[slot];
+    int slot = 0;   // two pinned buffers in turn: the wait is for the copy of the draw before last
+    f64* h = nr_mesh_pinned(sc, need, &slot);
+    if (!h) return fail("instanced mesh draw", "hipHostMalloc failed");
     std::memcpy(h, matrices, k * 16 * sizeof(f64));
     if (tint) std::memcpy(h + k * 16, tint, k * 4 * sizeof(f64));
     if (normals) std::memcpy(h + k * 16 + ntint, normals, k * 9 * sizeof(f64));

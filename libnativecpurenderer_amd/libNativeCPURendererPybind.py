@@ -636,6 +636,35 @@ class RenderContext:
         no = nout.value
         return xy[:no].copy(), z[:no].copy(), attr[:no].copy()
 
+    # skinned meshes (DESIGN.md §3 "Skinned meshes"): one kernel rewrites the
+    # mesh's positions (and normals) from the skin's bind pose; no host wait
+    @staticmethod
+    def _pose_args(mesh, skin):
+        if mesh.vertex_count != skin.vertex_count:
+            raise ValueError("the Mesh and the MeshSkin differ in their vertex count")
+
+    def pose_mesh(self, mesh: "Mesh", skin: "MeshSkin", palette):
+        """Poses `mesh` from `skin`'s bind pose under `palette`: one row-major
+        3x4 matrix [R | t] per bone, (nb, 12) or (nb, 3, 4).  Draws already
+        issued keep the old pose, later draws -- on any context -- see the new
+        one; the array is the caller's again on return."""
+        self._pose_args(mesh, skin)
+        pal = np.ascontiguousarray(palette, dtype=np.float64)
+        if pal.size != skin.bone_count * 12 or pal.ndim < 2 or pal.shape[0] != skin.bone_count:
+            raise ValueError("palette must be (bone_count, 12) or (bone_count, 3, 4)")
+        if not lib.PoseMesh(self._ptr, mesh._ptr, skin._ptr, _f64_ptr(pal)):
+            raise RuntimeError("PoseMesh failed: " + _lib.last_error())
+
+    def pose_mesh_device(self, mesh: "Mesh", skin: "MeshSkin", palette):
+        """pose_mesh with the palette (bone_count*12 f64, 16-byte aligned)
+        already in HBM: a device address or an object with .data_ptr(), as for
+        draw_mesh_instanced_device -- keep it alive and unchanged until the
+        call's kernel has executed."""
+        self._pose_args(mesh, skin)
+        addr = palette.data_ptr() if hasattr(palette, "data_ptr") else int(palette)
+        if not lib.PoseMeshDevice(self._ptr, mesh._ptr, skin._ptr, addr):
+            raise RuntimeError("PoseMeshDevice failed: " + _lib.last_error())
+
     # ---- additions: sync, device interop, measurement ------------------
     def flush(self):
         lib.Flush(self._ptr)
@@ -1313,9 +1342,72 @@ class Mesh:
         if not lib.UpdateMeshNormals(self._ptr, _f64_ptr(nrm)):
             raise RuntimeError("UpdateMeshNormals failed: " + _lib.last_error())
 
+    def positions(self) -> np.ndarray:
+        """The current positions (nv, 3), e.g. after RenderContext.pose_mesh
+        (a sync point)."""
+        out = np.empty((self.vertex_count, 3), dtype=np.float64)
+        if not lib.GetMeshPositions(self._ptr, _f64_ptr(out)):
+            raise RuntimeError("GetMeshPositions failed: " + _lib.last_error())
+        return out
+
+    def normals(self) -> np.ndarray:
+        """The current normals (nv, 3) of a lit Mesh (a sync point)."""
+        out = np.empty((self.vertex_count, 3), dtype=np.float64)
+        if not lib.GetMeshNormals(self._ptr, _f64_ptr(out)):
+            raise RuntimeError("GetMeshNormals failed: " + _lib.last_error())
+        return out
+
     def __del__(self):
         if getattr(self, "_can_release", False):
             lib.DestroyMesh(self._ptr)
+            self._can_release = False
+
+
+class MeshSkin:
+    """Device-resident bind pose of a skinned Mesh (new): positions, optional
+    normals, four joints and four weights per vertex, for bone_count bones
+    (RenderContext.pose_mesh)."""
+
+    def __init__(self, bind_positions, joints, weights, bone_count: int, bind_normals=None):
+        """bind_positions: (nv, 3); joints: (nv, 4) integers < bone_count, the
+        zero-weight ones too (stored as uint32); weights: (nv, 4), not
+        validated; bind_normals ((nv, 3)): also pose a lit Mesh's normals."""
+        pos = np.ascontiguousarray(bind_positions, dtype=np.float64).reshape(-1, 3)
+        nv = pos.shape[0]
+        jn = np.asarray(joints)
+        if jn.size != nv * 4:
+            raise ValueError("joints must be (nv, 4)")
+        if jn.size and (jn.min() < 0 or jn.max() > 0xFFFFFFFF):
+            raise ValueError("joints must fit uint32")
+        jn = np.ascontiguousarray(jn, dtype=np.uint32).reshape(nv, 4)
+        wt = np.ascontiguousarray(weights, dtype=np.float64)
+        if wt.size != nv * 4:
+            raise ValueError("weights must be (nv, 4)")
+        nrm = None
+        if bind_normals is not None:
+            nrm = np.ascontiguousarray(bind_normals, dtype=np.float64)
+            if nrm.size != nv * 3:
+                raise ValueError("bind_normals must be (nv, 3)")
+        self._can_release = False
+        self.vertex_count = nv
+        self.has_normals = nrm is not None
+        self._ptr = _check(lib.CreateMeshSkin(nv, _f64_ptr(pos), None if nrm is None else _f64_ptr(nrm),
+                                              jn.ctypes.data_as(ctypes.c_void_p), _f64_ptr(wt), int(bone_count)),
+                           "CreateMeshSkin")
+        self._can_release = True
+
+    @property
+    def bone_count(self) -> int:
+        return lib.GetMeshSkinBoneCount(self._ptr)
+
+    def set_variant(self, mode: int):
+        """A/B and tests: the skin kernel 0 automatic, 1 the palette read from
+        global memory, 2 staged in LDS (at most 128 bones); the same bits."""
+        lib.SetMeshSkinVariant(self._ptr, int(mode))
+
+    def __del__(self):
+        if getattr(self, "_can_release", False):
+            lib.DestroyMeshSkin(self._ptr)
             self._can_release = False
 
 
