@@ -163,6 +163,29 @@ void DrawTexturedTrianglesPerspective(RenderContext* ctx, Texture* tex, const f6
 void DrawTexturedTrianglesPerspectiveDevice(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z,
                                             const f64* uv, const f64* q, i64 n);   /* NEW: device pointers (as
                                  DrawTrianglesDevice) */
+/* NEW: modulated textured triangles -- texel times vertex colour (DESIGN §3 "Modulated textured draws").  uvc:
+   n*18, per corner k = 0..2 (u_k, v_k, r_k, g_k, b_k, A_k): a texel-unit UV and a colour; q: n*3 as above (all
+   1.0 for affine mapping: there is no separate affine form).  With I(x) = x0 + (x1 - x0)*w1 + (x2 - x0)*w2, the
+   Gouraud-channel expression on the raster's own barycentrics, per covered fragment, in f64, every operation
+   rounded in the order written:
+       a_k = u_k * q_k;  b_k = v_k * q_k                      (per triangle, as the perspective mode)
+       U = I(a), V = I(b), Q = I(q);  rq = 1.0 / Q;  u = U * rq;  v = V * rq
+       T = texel at (u, v) by the context's filter (nearest, or bilinear), unchanged; the alpha of a texture
+           without alpha is the literal 1.0
+       G_c = I(c)  for c in r, g, b, A
+       src_c = T_c * G_c                                      (one rounded product per channel)
+       ApplyPixel(src) as every triangle draw (colour transform, blend); depth as every triangle draw
+   A NaN stays a NaN (payload bits unspecified); q is not validated.  Every colour (1, 1, 1, 1) gives
+   DrawTexturedTrianglesPerspective's frame; a texture of texels all 1.0 under the nearest filter gives the Gouraud
+   DrawTriangles frame of those colours.  The batch takes the order-free raster exactly when the texture has no
+   alpha, every A_k == 1, the colour transform's alpha is 1 and the ordered raster is not forced.  A NULL uvc or a
+   NULL q latches an error under the entry point's name and draws nothing; every texture check of
+   DrawTexturedTriangles applies. */
+void DrawTexturedTrianglesModulated(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uvc,
+                                    const f64* q, i64 n);                 /* NEW: host arrays */
+void DrawTexturedTrianglesModulatedDevice(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z,
+                                          const f64* uvc, const f64* q, i64 n);   /* NEW: device pointers (as
+                                 DrawTrianglesDevice: xy / uvc re-staged when not 16-byte aligned, z and q the caller's) */
 TriangleBuffer* CreateTexturedTriangleBuffer(i64 n, const f64* xy, const f64* z,
                                              const f64* uv);              /* NEW: one H2D upload; no texture bound */
 void DrawTexturedTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb, Texture* tex);   /* NEW: texture chosen per
@@ -289,6 +312,27 @@ bool AssembleMeshLit(RenderContext* ctx, Mesh* m, const f64* matrix16, const f64
                      f64* z_out, f64* attr_out, i64* n_out);             /* NEW: the soup a DrawMeshLit rasterises under
                                  ctx's lights, near plane and cull mode (the draw's own kernels), in
                                  AssembleMeshClipped's conventions (attr x12 Gouraud / x4 flat); a sync point */
+/* NEW: textured colour meshes -- lit, textured, posed (DESIGN §3 "Modulated textured draws").  A mesh with both a
+   texel-unit uv (nv*2) and a colour (nv*4) per vertex, and normals (nv*3) or NULL (GetMeshLit).  It keeps the
+   per-vertex uv and rgba on the device; its expanded attributes are n*18, per corner (u, v, r, g, b, a).
+   DrawTexturedMesh draws it as a DrawTexturedTrianglesModulated batch, modulated by its own colours, unlit;
+   DrawTexturedMeshLit first runs the light pass of DrawMeshLit on the colours (the uv untouched).  Every state of
+   DrawTexturedMesh applies (transform, depth, colour transform, filter, near plane, cull, SetMeshPerspective,
+   sharding, GetMeshLastTriangleCount): the clip stage interpolates all six attribute values in clip space, a cut
+   vertex has q = 1 / wNear, and with the perspective state off every q is 1.0.  With the default lights and colours
+   in [0, 1] the lit draw is the unlit draw bit for bit.  UpdateMeshPositions, UpdateMeshNormals, PoseMesh and
+   GetMeshNormals work on it as on a lit colour mesh.  DrawMesh, DrawMeshLit, every *Instanced draw and the other
+   Assemble* calls (AssembleMesh apart) latch "not supported for a textured colour mesh" and draw nothing;
+   DrawTexturedMeshLit on another kind of mesh, or on one without normals, latches an error, draws nothing and
+   sets the last count to 0. */
+Mesh* CreateTexturedColorMesh(i64 nv, const f64* pos, const f64* normal, i64 n, const uint32_t* idx, const f64* uv,
+                              const f64* rgba);                          /* NEW: normal nv*3 or NULL; CreateMesh's
+                                 checks, and NULL uv or rgba with n > 0 */
+void DrawTexturedMeshLit(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrix16, const f64* normal9);   /* NEW */
+bool AssembleTexturedColorMesh(RenderContext* ctx, Mesh* m, const f64* matrix16, const f64* normal9, bool lit, i64 cap,
+                               f64* xy_out, f64* z_out, f64* uvc_out, f64* q_out, i64* n_out);   /* NEW: the soup such
+                                 a draw rasterises (the draw's own kernels), in AssembleMeshPerspective's conventions
+                                 (uvc x18, q x3); lit false: DrawTexturedMesh's, normal9 ignored; a sync point */
 bool AssembleMeshLitInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* normals, const f64* tint,
                               i64 K, i64 cap, f64* xy_out, f64* z_out, f64* attr_out, i64* n_out);   /* NEW: the same
                                  for a DrawMeshLitInstanced, in AssembleMeshInstanced's conventions without q */

@@ -80,6 +80,8 @@ DEVICE_ABI = {
     "DrawTexturedTrianglesDevice": (None, (P, P, P, P, P, L)),
     "DrawTexturedTrianglesPerspective": (None, (P, P, P, P, P, P, L)),
     "DrawTexturedTrianglesPerspectiveDevice": (None, (P, P, P, P, P, P, L)),
+    "DrawTexturedTrianglesModulated": (None, (P, P, P, P, P, P, L)),
+    "DrawTexturedTrianglesModulatedDevice": (None, (P, P, P, P, P, P, L)),
     "CreateTexturedTriangleBuffer": (P, (L, P, P, P)),
     "DrawTexturedTriangleBuffer": (None, (P, P, P)),
     "SetTriangleTextureFilter": (B, (P, L)),
@@ -108,6 +110,9 @@ DEVICE_ABI = {
     "DrawTexturedMeshInstancedDevice": (None, (P, P, P, P, L)),
     "AssembleMeshInstanced": (B, (P, P, P, P, L, L, P, P, P, P, P)),
     "CreateLitMesh": (P, (L, P, P, L, P, P, B)),
+    "CreateTexturedColorMesh": (P, (L, P, P, L, P, P, P)),
+    "DrawTexturedMeshLit": (None, (P, P, P, P, P)),
+    "AssembleTexturedColorMesh": (B, (P, P, P, P, B, L, P, P, P, P, P)),
     "UpdateMeshNormals": (B, (P, P)),
     "GetMeshLit": (B, (P,)),
     "SetMeshLights": (B, (P, P, P, L)),

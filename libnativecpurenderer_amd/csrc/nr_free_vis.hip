@@ -132,6 +132,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                                            const u64* key, unsigned char* lds, u32& nU) {
     using St = ShadeStage<MODE, HS>;
     constexpr int RM = attr_unfiltered(MODE);   // the mode of the shading records (a bilinear batch: its nearest counterpart's)
+    static_assert(St::REC == RecLen<RM>::REC, "the staged slots hold the records build_record<RM> writes");
     constexpr int PPT = TH * TW / NT;
     static_assert(PPT <= 32, "overflow bitmask");
     const int tid = opaque_tid();
@@ -260,15 +261,19 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
         // them (as the flat path keeps FQ loads in flight).  Ordinary cached
         // loads: the texture is read again by other tiles.  A bilinear mode
         // gathers four texels per pixel (24 VGPRs) and keeps the two fractions,
-        // so it has one pixel's loads in flight, not two.
+        // so it has one pixel's loads in flight, not two.  A modulated mode keeps
+        // each pixel's record index across the gather and forms the barycentrics
+        // again for the corner colours when the texel arrives (record_modulate).
         static_assert(OVF_Q > 0, "unstaged winners are shaded in pass 3b");
         constexpr bool BIL = attr_bilinear(MODE);
+        constexpr bool MOD = attr_modulated(MODE);
         constexpr int TQ = BIL ? 1 : 2;
         static_assert(PPT % TQ == 0, "pixel groups");
 #pragma unroll 1
         for (int k0 = 0; k0 < PPT; k0 += TQ) {
             i64 ti[TQ];   // texel offset, or -1: nothing to fetch
             f64 fu[BIL ? TQ : 1], fv[BIL ? TQ : 1];   // (bilinear: the footprint's fractions)
+            int dj[MOD ? TQ : 1];                     // (modulated: the pixel's staged record)
 #pragma unroll
             for (int j = 0; j < TQ; ++j) {
                 const int k = k0 + j;
@@ -298,6 +303,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                     ovf |= 1u << k;
                     continue;
                 }
+                if constexpr (MOD) dj[j] = d;
                 if constexpr (BIL) {
                     f64 u, v;
                     record_uv<MODE>(rec + d * St::REC, px, py, u, v);
@@ -326,6 +332,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                 const i64 px = x0 + lx, py = y0 + ly;
                 const i64 gp = py * fp.W + px;
                 f64 cr = c[j][0], cg = c[j][1], cb = c[j][2], ca = 1.0;
+                if constexpr (MOD) record_modulate(rec + dj[j] * St::REC, px, py, cr, cg, cb, ca);
                 apply_winner(fp, gp, cr, cg, cb, ca);
                 store_colour(fp, gp, px, py, cr, cg, cb, ca);
             }
@@ -1060,12 +1067,13 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& 
     const bool wide = !C && t.n != 0 && t.heavy > 0 && t.heavy < WIDE_HEAVY;
     auto kernel = vis_kernel<Z, C, G, false>(wide, coop);
     // a marking frame (fp.winMask; never a counting batch, never LESS without write -- and only a repeat
-    // TriangleBuffer draw marks, which has no q: the filtered perspective mode has no marking instance)
+    // TriangleBuffer draw marks, which has no q: the filtered perspective mode and the modulated modes have no
+    // marking instance)
     // The key cache's batches are those of a pruned list, so they too exist only where a marking frame does.  A
     // cached batch runs k_keys at the workgroup size k_vis would take; the capture frame (one per generation) the
     // narrow capturing instance of its raster shape.
     bool narrow = false;
-    if constexpr (!C && Z != 2 && G != ATTR_TEX_PERSP_BIL) {
+    if constexpr (!C && Z != 2 && G != ATTR_TEX_PERSP_BIL && !attr_modulated(G)) {
         if (va.kkeys) {
             const bool w = wide || keys_wide_forced();
             hipExtLaunchKernelGGL(w ? k_keys<Z, G, 2 * VWG> : k_keys<Z, G, VWG>, dim3(grid), dim3(w ? 2 * VWG : VWG), 0, s,
@@ -1094,7 +1102,9 @@ void launch_vis_any(const FrameParams& fp, const TriScratch& sc, const BatchTota
 #define NR_VG(ZM, G) (fp.fragCounter ? launch_vis<ZM, true, G>(fp, sc, t, va, grid, s, start, stop) \
                                      : launch_vis<ZM, false, G>(fp, sc, t, va, grid, s, start, stop))
 #define NR_VZ(ZM)                                            \
-    (mode == ATTR_TEX_PERSP_BIL ? NR_VG(ZM, ATTR_TEX_PERSP_BIL) \
+    (mode == ATTR_TEXC_BIL ? NR_VG(ZM, ATTR_TEXC_BIL)        \
+     : mode == ATTR_TEXC    ? NR_VG(ZM, ATTR_TEXC)           \
+     : mode == ATTR_TEX_PERSP_BIL ? NR_VG(ZM, ATTR_TEX_PERSP_BIL) \
      : mode == ATTR_TEX_BIL ? NR_VG(ZM, ATTR_TEX_BIL)        \
      : mode == ATTR_TEX_PERSP ? NR_VG(ZM, ATTR_TEX_PERSP)    \
      : mode == ATTR_TEX     ? NR_VG(ZM, ATTR_TEX)            \

@@ -7,15 +7,17 @@
 struct Mesh {
     i64 nv = 0, n = 0;
     int mode = nrtri::ATTR_FLAT;   // AttrMode of the expanded attributes
-    bool opaque = false;           // colour mesh: every vertex alpha == 1 (textured: decided per draw by the texture)
+    bool opaque = false;           // colour mesh: every vertex alpha == 1 (textured: decided per draw by the texture;
+                                   // textured colour: by both)
     int device = 0;
     f64* pos = nullptr;            // nv*3
     u32* idx = nullptr;            // n*3, every entry < nv (checked on the host at creation)
-    f64* attr = nullptr;           // expanded: n*12 Gouraud, n*4 flat (the colour of i0), n*6 textured
+    f64* attr = nullptr;           // expanded: n*12 Gouraud, n*4 flat (the colour of i0), n*6 textured, n*18 textured colour
     // a lit mesh (CreateLitMesh) also keeps what the light pass reads: the per-vertex colours and normals
     bool lit = false;
     f64* rgba = nullptr;           // nv*4 (with n > 0)
     f64* normal = nullptr;         // nv*3
+    f64* uv = nullptr;             // nv*2: a textured colour mesh (ATTR_TEXC) also keeps its uv, and its rgba above whether lit or not
 };
 // pos and normal are read only by the vertex, clip-vertex and light kernels that a draw or Assemble* call
 // launches on the device's main stream (nr_stream_for), and rgba only by the light kernels: a pending batch, or

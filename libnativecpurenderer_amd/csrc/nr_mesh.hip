@@ -47,6 +47,14 @@
 // k_minst_light), whose output -- a per-draw vertex-colour table in the staging,
 // never in the mesh -- feeds the assembly, clip and instancing passes in place
 // of the mesh's own colours.  Unlit draws run none of it.
+//
+// Textured colour meshes (CreateTexturedColorMesh, DrawTexturedMeshLit, DESIGN.md
+// §3 "Modulated textured draws"): a uv and a colour per vertex, expanded to three
+// 16-byte words per corner (u v | r g | b a) and drawn as a modulated batch --
+// the texel times the interpolated colour.  A lit draw runs the same light pass
+// on the colours and gathers the corner words from the mesh's uv and the colour
+// table; the clip stage emits three words per corner; every draw has a q (1.0
+// without the perspective state).
 #include "nr_mesh.h"
 
 #include <hipcub/hipcub.hpp>
@@ -56,6 +64,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <string>
+#include <vector>
 
 namespace nrtri {
 namespace {
@@ -663,18 +672,65 @@ __global__ __launch_bounds__(256) void k_minst_lit_clip_emit(const u32* __restri
                                   tint + (size_t)in.k * 4, wNear, (i64)in.r, k, (i64)off[g], xy, z, oattr, nullptr);
 }
 
+// ---- textured colour meshes (DESIGN.md §3 "Modulated textured draws") -------------
+// The soup's attributes are three 16-byte words per corner, (u v | r g | b a).  An unlit draw reads the mesh's
+// own expansion (k_mesh_attr, three words per vertex); a lit draw gathers them from the mesh's per-vertex uv and
+// the light pass's two-word colour table.
+// Pass 2 of an unclipped lit draw: k_mesh_assemble's gather and the corner's three words.
+template <bool Q>
+__global__ __launch_bounds__(256) void k_mesh_uvc_assemble(const u32* __restrict__ idx, i64 ncorner,
+                                                           const double2* __restrict__ vxy, const f64* __restrict__ vz,
+                                                           const f64* __restrict__ vq, const double2* __restrict__ uv,
+                                                           const double2* __restrict__ lit, double2* __restrict__ xy,
+                                                           f64* __restrict__ z, f64* __restrict__ q,
+                                                           double2* __restrict__ oattr) {
+    const i64 c = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (c >= ncorner) return;
+    const i64 i = (i64)idx[c];
+    xy[c] = vxy[i];
+    z[c] = vz[i];
+    if constexpr (Q) q[c] = vq[i];
+    oattr[c * 3] = uv[i];
+    oattr[c * 3 + 1] = lit[i * 2];
+    oattr[c * 3 + 2] = lit[i * 2 + 1];
+}
+
+// A clipped lit draw: the expansion the emit pass reads, one thread per corner.
+__global__ __launch_bounds__(256) void k_mesh_uvc_attr(const u32* __restrict__ idx, i64 ncorner,
+                                                       const double2* __restrict__ uv, const double2* __restrict__ lit,
+                                                       double2* __restrict__ out) {
+    const i64 c = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (c >= ncorner) return;
+    const i64 i = (i64)idx[c];
+    out[c * 3] = uv[i];
+    out[c * 3 + 1] = lit[i * 2];
+    out[c * 3 + 2] = lit[i * 2 + 1];
+}
+
+// The 1/w of a draw with the perspective state off: every corner's q is 1.0.
+__global__ __launch_bounds__(256) void k_mesh_unit_q(f64* __restrict__ q, i64 count) {
+    const i64 c = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (c < count) q[c] = 1.0;
+}
+
 unsigned blocks_for(i64 threads) { return (unsigned)((threads + 255) / 256); }
+
+void unit_q(RenderContext* ctx, f64* q, i64 count) {
+    hipLaunchKernelGGL(k_mesh_unit_q, dim3(blocks_for(count)), dim3(256), 0, ctx->stream, q, count);
+    NR_CHECK(hipGetLastError());
+}
 
 bool fail(const char* what, const char* why) {
     nr_set_error_msg((std::string(what) + ": " + why).c_str());
     return false;
 }
 
-// uv: texel coordinates nv*2 (a textured mesh) or null (rgba nv*4, flat or Gouraud)
+// uv: texel coordinates nv*2 (a textured mesh) or null (rgba nv*4, flat or Gouraud); both uv and rgba: a textured
+// colour mesh (ATTR_TEXC), which keeps its per-vertex uv and rgba on the device beside the expansion
 // normal: nv*3, a lit colour mesh (the per-vertex colours stay on the device beside it), or null
 Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* idx, const f64* rgba, bool gouraud,
                   const f64* uv, const f64* normal = nullptr) {
-    const f64* vattr = uv ? uv : rgba;
+    const f64* vattr = uv ? uv : rgba;   // (both: the interleaved array below)
     const char* why = nullptr;
     if (nv < 0 || n < 0) why = "negative count";
     else if (nv > (i64)0xFFFFFFFFll) why = "vertex count does not fit 32-bit indices";
@@ -692,17 +748,27 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
     Mesh* m = new Mesh();
     m->nv = nv;
     m->n = n;
-    m->mode = uv ? nrtri::ATTR_TEX : (gouraud ? nrtri::ATTR_GOURAUD : nrtri::ATTR_FLAT);
+    const bool uvc = uv && rgba;
+    m->mode = uvc ? nrtri::ATTR_TEXC : (uv ? nrtri::ATTR_TEX : (gouraud ? nrtri::ATTR_GOURAUD : nrtri::ATTR_FLAT));
     m->lit = normal != nullptr;
     NR_CHECK(hipGetDevice(&m->device));
-    if (!uv && n > 0) {
+    if (rgba && n > 0) {
         m->opaque = true;
         for (i64 v = 0; v < nv; ++v)
             if (rgba[v * 4 + 3] != 1) { m->opaque = false; break; }
     }
     if (nv == 0) return m;   // (then n == 0: every index would be out of range)
     hipStream_t s = nr_stream_for(m->device);
-    const int w2 = uv ? 1 : 2;   // 16-byte words per vertex attribute
+    const int w2 = uvc ? 3 : (uv ? 1 : 2);   // 16-byte words per vertex attribute
+    std::vector<f64> inter;                  // (a textured colour mesh: u v | r g | b a per vertex)
+    if (uvc && n > 0) {
+        inter.resize((size_t)nv * 6);
+        for (i64 v = 0; v < nv; ++v) {
+            inter[v * 6] = uv[v * 2]; inter[v * 6 + 1] = uv[v * 2 + 1];
+            for (int c = 0; c < 4; ++c) inter[v * 6 + 2 + c] = rgba[v * 4 + c];
+        }
+        vattr = inter.data();
+    }
     f64* dv = nullptr;           // the per-vertex attributes, on the device until expanded
     bool ok = hipMalloc(&m->pos, (size_t)nv * 3 * sizeof(f64)) == hipSuccess;
     if (ok && normal) ok = hipMalloc(&m->normal, (size_t)nv * 3 * sizeof(f64)) == hipSuccess;
@@ -710,6 +776,9 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
         ok = hipMalloc(&m->idx, (size_t)n * 3 * sizeof(u32)) == hipSuccess &&
              hipMalloc(&m->attr, (size_t)n * nrtri::attr_stride(m->mode) * sizeof(f64)) == hipSuccess &&
              hipMalloc(&dv, (size_t)nv * w2 * 2 * sizeof(f64)) == hipSuccess;
+        if (ok && uvc)
+            ok = hipMalloc(&m->uv, (size_t)nv * 2 * sizeof(f64)) == hipSuccess &&
+                 hipMalloc(&m->rgba, (size_t)nv * 4 * sizeof(f64)) == hipSuccess;
     }
     if (!ok) {
         (void)hipGetLastError();
@@ -719,6 +788,8 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
         if (m->idx) NR_CHECK(hipFree(m->idx));
         if (m->attr) NR_CHECK(hipFree(m->attr));
         if (m->normal) NR_CHECK(hipFree(m->normal));
+        if (m->uv) NR_CHECK(hipFree(m->uv));
+        if (m->rgba) NR_CHECK(hipFree(m->rgba));
         delete m;
         return nullptr;
     }
@@ -727,6 +798,10 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
     if (n > 0) {
         NR_CHECK(hipMemcpyAsync(m->idx, idx, (size_t)n * 3 * sizeof(u32), hipMemcpyHostToDevice, s));
         NR_CHECK(hipMemcpyAsync(dv, vattr, (size_t)nv * w2 * 2 * sizeof(f64), hipMemcpyHostToDevice, s));
+        if (uvc) {
+            NR_CHECK(hipMemcpyAsync(m->uv, uv, (size_t)nv * 2 * sizeof(f64), hipMemcpyHostToDevice, s));
+            NR_CHECK(hipMemcpyAsync(m->rgba, rgba, (size_t)nv * 4 * sizeof(f64), hipMemcpyHostToDevice, s));
+        }
         const int perTri = m->mode == nrtri::ATTR_FLAT ? 1 : 3;
         const i64 nout = n * perTri;
         hipLaunchKernelGGL(k_mesh_attr, dim3(blocks_for(nout)), dim3(256), 0, s, m->idx, nout, perTri, w2,
@@ -734,7 +809,7 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
         NR_CHECK(hipGetLastError());
     }
     NR_CHECK(hipStreamSynchronize(s));   // caller may reuse its arrays on return
-    if (normal) m->rgba = dv;            // (a lit mesh keeps them)
+    if (normal && !uvc) m->rgba = dv;    // (a lit mesh keeps them; a textured colour mesh has its own copy)
     else if (dv) NR_CHECK(hipFree(dv));
     return m;
 }
@@ -833,8 +908,61 @@ bool assemble_lit(RenderContext* ctx, const Mesh* m, const f64* matrix, const Ma
     return true;
 }
 
-// A textured mesh drawn with the context's perspective state on; colour meshes ignore the state.
-inline bool persp_draw(const RenderContext* ctx, const Mesh* m) { return ctx->meshPersp && m->mode == ATTR_TEX; }
+// A textured mesh (or a textured colour mesh) drawn with the context's perspective state on; colour meshes ignore
+// the state.
+inline bool persp_draw(const RenderContext* ctx, const Mesh* m) {
+    return ctx->meshPersp && (m->mode == ATTR_TEX || m->mode == ATTR_TEXC);
+}
+
+// The unclipped soup of a textured colour mesh (m->mode == ATTR_TEXC, m->n > 0): assemble() with a q for every
+// draw -- 1 / cw under the perspective state, else 1.0 -- and, lit (the normal matrix, else null), the light pass
+// beside the vertex stage and the attributes gathered from the uv and the colour table: vertices | table nv*4 |
+// xy n*6 | z n*3 | q n*3 (each padded to an even count) | attributes n*18, all in ctx's mesh staging.
+bool assemble_uvc(RenderContext* ctx, const Mesh* m, const f64* matrix, const Mat3* lit, Soup* out) {
+    const bool persp = persp_draw(ctx, m);
+    if (!lit) {
+        if (persp) return assemble(ctx, m, matrix, out, true);
+        nrtri::settle(ctx);
+        TriScratch& sc = ctx->tri;
+        const size_t nv = (size_t)m->nv, n = (size_t)m->n, vzn = (nv + 1) & ~(size_t)1;
+        if (!sc.mstage.ensure(nv * 2 + vzn + n * 12)) return false;   // (assemble: nv*2 + vzn + n*9, then q n*3)
+        if (!assemble(ctx, m, matrix, out, false)) return false;      // (settled already; the staging is large enough)
+        f64* q = const_cast<f64*>(out->z) + n * 3;
+        unit_q(ctx, q, (i64)n * 3);
+        out->q = q;
+        return true;
+    }
+    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
+    TriScratch& sc = ctx->tri;
+    const size_t nv = (size_t)m->nv, n = (size_t)m->n;
+    const size_t vzn = (nv + 1) & ~(size_t)1, zn = (n * 3 + 1) & ~(size_t)1;
+    if (!sc.mstage.ensure(nv * 2 + 2 * vzn + nv * 4 + n * 6 + 2 * zn + n * 18)) return false;
+    f64* vxy = sc.mstage;
+    f64* vz = vxy + nv * 2;
+    f64* vq = vz + vzn;
+    f64* table = vq + vzn;
+    f64* xy = table + nv * 4;
+    f64* z = xy + n * 6;
+    f64* q = z + zn;
+    f64* attr = q + zn;
+    hipEvent_t a, b;
+    nr_timing_begin(ctx, NRK_MESH_VERTEX, &a, &b);
+    hipLaunchKernelGGL(persp ? k_mesh_vertex<true> : k_mesh_vertex<false>, dim3(blocks_for(m->nv)), dim3(256), 0,
+                       ctx->stream, m->pos, m->nv, mat4_of(matrix), reinterpret_cast<double2*>(vxy), vz, vq);
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_VERTEX, a, b);
+    light_pass(ctx, m, *lit, table);
+    nr_timing_begin(ctx, NRK_MESH_ASSEMBLE, &a, &b);
+    hipLaunchKernelGGL(persp ? k_mesh_uvc_assemble<true> : k_mesh_uvc_assemble<false>, dim3(blocks_for(m->n * 3)),
+                       dim3(256), 0, ctx->stream, m->idx, m->n * 3, reinterpret_cast<const double2*>(vxy), vz, vq,
+                       reinterpret_cast<const double2*>(m->uv), reinterpret_cast<const double2*>(table),
+                       reinterpret_cast<double2*>(xy), z, q, reinterpret_cast<double2*>(attr));
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, NRK_MESH_ASSEMBLE, a, b);
+    if (!persp) unit_q(ctx, q, (i64)n * 3);
+    *out = Soup{xy, z, attr, q, m->n};
+    return true;
+}
 
 inline bool clip_stage_on(const RenderContext* ctx) { return ctx->meshNear > 0 || ctx->meshCull != 0; }
 
@@ -887,14 +1015,27 @@ bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup
     if (nout > 2 * n) return fail("mesh clip stage", "inconsistent triangle count");   // (never: the counts are 0, 1 or 2)
     const size_t stride = (size_t)nrtri::attr_stride(m->mode);
     const size_t zn = (nout * 3 + 1) & ~(size_t)1;   // keeps the attributes 16-byte aligned
-    const size_t soup = nout * 6 + zn + nout * stride + (persp ? nout * 3 : 0);   // (a lit draw has no q: even, what follows stays 16-byte aligned)
+    const bool uvc = m->mode == nrtri::ATTR_TEXC;    // (a textured colour mesh has a q in every draw: 1.0 without the state)
+    // (a lit colour draw has no q, a lit textured colour draw a padded one: even, what follows stays 16-byte aligned)
+    const size_t soup = nout * 6 + zn + nout * stride + (uvc ? zn : (persp ? nout * 3 : 0));
     if (!sc.mstage.ensure(soup + (lit ? nv * 4 + n * stride : 0))) return false;
     f64* xy = sc.mstage;
     f64* z = xy + nout * 6;
     f64* attr = z + zn;
-    f64* q = persp ? attr + nout * stride : nullptr;
+    f64* q = persp || uvc ? attr + nout * stride : nullptr;
     const f64* src = m->attr;
-    if (lit) {
+    if (lit && uvc) {
+        f64* table = xy + soup;
+        f64* expanded = table + nv * 4;
+        light_pass(ctx, m, *lit, table);
+        nr_timing_begin(ctx, NRK_MESH_LIT_ATTR, &a, &b);
+        hipLaunchKernelGGL(k_mesh_uvc_attr, dim3(blocks_for(m->n * 3)), dim3(256), 0, ctx->stream, m->idx, m->n * 3,
+                           reinterpret_cast<const double2*>(m->uv), reinterpret_cast<const double2*>(table),
+                           reinterpret_cast<double2*>(expanded));
+        NR_CHECK(hipGetLastError());
+        nr_timing_end(ctx, NRK_MESH_LIT_ATTR, a, b);
+        src = expanded;
+    } else if (lit) {
         f64* table = xy + soup;
         f64* expanded = table + nv * 4;
         light_pass(ctx, m, *lit, table);
@@ -907,7 +1048,8 @@ bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup
         nr_timing_end(ctx, NRK_MESH_LIT_ATTR, a, b);
         src = expanded;
     }
-    const auto emit = m->mode == nrtri::ATTR_GOURAUD ? k_mesh_clip_emit<2>
+    const auto emit = uvc                            ? (persp ? k_mesh_clip_emit<3, true> : k_mesh_clip_emit<3>)
+                      : m->mode == nrtri::ATTR_GOURAUD ? k_mesh_clip_emit<2>
                       : m->mode != nrtri::ATTR_TEX   ? k_mesh_clip_emit<0>
                       : persp                        ? k_mesh_clip_emit<1, true>
                                                      : k_mesh_clip_emit<1>;
@@ -917,6 +1059,7 @@ bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup
                        reinterpret_cast<double2*>(attr), q);
     NR_CHECK(hipGetLastError());
     nr_timing_end(ctx, NRK_MESH_CLIP_EMIT, a, b);
+    if (uvc && !persp) unit_q(ctx, q, (i64)nout * 3);
     *out = Soup{xy, z, attr, q, (i64)nout};
     return true;
 }
@@ -932,7 +1075,7 @@ bool draw_soup(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out) 
 // The K matrices (K*16) and tints (K*4, or null) of an instanced draw, on the device; a lit draw's normal
 // matrices (K*9, or null: the identity for every instance).
 struct Instances { const f64* mats; const f64* tint; i64 K; const f64* normals = nullptr; };
-bool check_mesh(RenderContext* ctx, const Mesh* m, bool textured, const char* what);
+bool check_mesh(RenderContext* ctx, const Mesh* m, bool textured, const char* what, bool uvcOk = false);
 
 // The argument checks every instanced entry point shares, after the mesh's own: false with an error latched under
 // `what`, or *empty when there is nothing to draw (no error).  Nothing is allocated or read before them.
@@ -1214,6 +1357,7 @@ void copy_out(RenderContext* ctx, size_t k, std::initializer_list<CopyOut> parts
 bool check_assemble(RenderContext* ctx, const Mesh* m, bool textured, i64 cap, bool outputs, i64* n_out,
                     const char* what) {
     if (!m) return fail(what, "NULL mesh");
+    if (m->mode == nrtri::ATTR_TEXC) return fail(what, "not supported for a textured colour mesh");
     if (textured && m->mode != nrtri::ATTR_TEX) return fail(what, "a colour mesh");
     if (m->device != ctx->device) return fail(what, "mesh on another device");
     if (!n_out) return fail(what, "NULL output");
@@ -1224,9 +1368,12 @@ bool check_assemble(RenderContext* ctx, const Mesh* m, bool textured, i64 cap, b
 }
 
 // The checks every mesh draw shares (in the style of check_texture).
-bool check_mesh(RenderContext* ctx, const Mesh* m, bool textured, const char* what) {
+// uvcOk: the call also draws a textured colour mesh (as a textured one); every other call rejects that kind.
+bool check_mesh(RenderContext* ctx, const Mesh* m, bool textured, const char* what, bool uvcOk) {
     if (!m) return fail(what, "NULL mesh");
-    if ((m->mode == nrtri::ATTR_TEX) != textured)
+    if (m->mode == nrtri::ATTR_TEXC) {
+        if (!uvcOk) return fail(what, "not supported for a textured colour mesh");
+    } else if ((m->mode == nrtri::ATTR_TEX) != textured)
         return fail(what, textured ? "a colour mesh (use DrawMesh)" : "a textured mesh (use DrawTexturedMesh)");
     if (m->device != ctx->device) return fail(what, "mesh on another device");
     return true;
@@ -1274,6 +1421,7 @@ void DestroyMesh(Mesh* m) {
     if (m->idx) NR_CHECK(hipFree(m->idx));
     if (m->attr) NR_CHECK(hipFree(m->attr));
     if (m->rgba) NR_CHECK(hipFree(m->rgba));
+    if (m->uv) NR_CHECK(hipFree(m->uv));
     if (m->normal) NR_CHECK(hipFree(m->normal));
     NR_CHECK(hipSetDevice(prev));
     delete m;
@@ -1314,15 +1462,36 @@ void DrawMesh(RenderContext* ctx, Mesh* m, const f64* matrix16) {
     nrtri::draw(ctx, soup_batch(s, m->mode, m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED, nullptr, false));
 }
 
-// New: draws a textured mesh sampled from `tex` (chosen per draw).
+// The soup a draw of the textured colour mesh `m` rasterises: lit (its normal matrix) or not (null).
+static bool uvc_soup(RenderContext* ctx, const Mesh* m, const f64* matrix16, const Mat3* lit, Soup* s) {
+    return clip_stage_on(ctx) ? assemble_clipped(ctx, m, matrix16, s, persp_draw(ctx, m), lit)
+                              : assemble_uvc(ctx, m, matrix16, lit, s);
+}
+
+// ... and its modulated batch: opaque when the texture has no alpha (draw_textured) and every vertex alpha is 1
+// (the light pass copies alpha; a cut vertex's is 1 + 0 * t).
+static void draw_uvc_batch(RenderContext* ctx, const Mesh* m, Texture* tex, const Soup& s) {
+    Batch b = soup_batch(s, nrtri::ATTR_TEX, m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED, nullptr, false);
+    b.modulated = true;
+    nrtri::draw_textured(ctx, tex, b);
+}
+
+// New: draws a textured mesh sampled from `tex` (chosen per draw); a textured colour mesh: modulated by its own
+// vertex colours, unlit.
 void DrawTexturedMesh(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrix16) {
     NR_CHECK(hipSetDevice(ctx->device));
-    if (!check_mesh(ctx, m, true, "DrawTexturedMesh")) return;
+    if (!check_mesh(ctx, m, true, "DrawTexturedMesh", true)) return;
     if (ctx->recording) nr_settle(ctx);   // recorded draws come first
     if (!nrtri::check_texture(ctx, tex, "DrawTexturedMesh")) return;
     ctx->meshLastCount = 0;
     if (m->n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
     Soup s;
+    if (m->mode == nrtri::ATTR_TEXC) {
+        if (!uvc_soup(ctx, m, matrix16, nullptr, &s)) return;
+        ctx->meshLastCount = s.n;
+        if (s.n > 0) draw_uvc_batch(ctx, m, tex, s);
+        return;
+    }
     if (!draw_soup(ctx, m, matrix16, &s)) return;
     ctx->meshLastCount = s.n;
     if (s.n <= 0) return;
@@ -1481,6 +1650,67 @@ Mesh* CreateLitMesh(i64 nv, const f64* pos, const f64* normal, i64 n, const uint
     }
     static const f64 none[3] = {0, 0, 0};
     return create_mesh("CreateLitMesh", nv, pos, n, idx, rgba, gouraud, nullptr, normal ? normal : none);
+}
+
+// ---- textured colour meshes (DESIGN.md §3 "Modulated textured draws") -----------------------------------------
+// New: an indexed mesh with both a texel-unit uv (nv*2) and a colour (nv*4) per vertex, and normals (nv*3) or NULL.
+// It keeps the per-vertex uv and rgba on the device (and the normals, when given: GetMeshLit); its expanded
+// attributes are n*18, per corner (u v | r g | b a).  CreateMesh's checks, and NULL uv or rgba with n > 0.
+Mesh* CreateTexturedColorMesh(i64 nv, const f64* pos, const f64* normal, i64 n, const uint32_t* idx, const f64* uv,
+                              const f64* rgba) {
+    if ((!uv || !rgba) && n > 0) {
+        fail("CreateTexturedColorMesh", !uv ? "NULL uv" : "NULL rgba");
+        return nullptr;
+    }
+    static const f64 none[4] = {0, 0, 0, 0};
+    return create_mesh("CreateTexturedColorMesh", nv, pos, n, idx, rgba ? rgba : none, true, uv ? uv : none, normal);
+}
+
+// New: DrawTexturedMesh of a textured colour mesh with normals, lit: the light pass of DrawMeshLit runs on the
+// vertex colours (the uv untouched) before anything else reads them, and the rest is DrawTexturedMesh's -- every
+// state of it applies.  A mesh of another kind, or one without normals, latches an error and draws nothing (the
+// last count 0).  With the default lights and colours in [0, 1] the frame is DrawTexturedMesh's bit for bit.
+void DrawTexturedMeshLit(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrix16, const f64* normal9) {
+    const char* what = "DrawTexturedMeshLit";
+    NR_CHECK(hipSetDevice(ctx->device));
+    ctx->meshLastCount = 0;
+    if (!m) { fail(what, "NULL mesh"); return; }
+    if (m->mode != nrtri::ATTR_TEXC) { fail(what, "not a textured colour mesh (create it with CreateTexturedColorMesh)"); return; }
+    if (!check_mesh(ctx, m, true, what, true)) return;
+    if (!m->lit) { fail(what, "a mesh without normals"); return; }
+    if (ctx->recording) nr_settle(ctx);   // recorded draws come first
+    if (!nrtri::check_texture(ctx, tex, what)) return;
+    if (m->n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
+    const Mat3 N = mat3_of(normal9);
+    Soup s;
+    if (!uvc_soup(ctx, m, matrix16, &N, &s)) return;
+    ctx->meshLastCount = s.n;
+    if (s.n > 0) draw_uvc_batch(ctx, m, tex, s);
+}
+
+// New: the soup such a draw rasterises -- the draw's own kernels -- in AssembleMeshPerspective's conventions:
+// uvc_out x18, q_out x3 (1.0 with the perspective state off).  lit == false: DrawTexturedMesh's soup, normal9
+// ignored; lit: DrawTexturedMeshLit's (the mesh needs normals).  A sync point.
+bool AssembleTexturedColorMesh(RenderContext* ctx, Mesh* m, const f64* matrix16, const f64* normal9, bool lit, i64 cap,
+                               f64* xy_out, f64* z_out, f64* uvc_out, f64* q_out, i64* n_out) {
+    const char* what = "AssembleTexturedColorMesh";
+    NR_CHECK(hipSetDevice(ctx->device));
+    if (!m) return fail(what, "NULL mesh");
+    if (m->mode != nrtri::ATTR_TEXC) return fail(what, "not a textured colour mesh (create it with CreateTexturedColorMesh)");
+    if (m->device != ctx->device) return fail(what, "mesh on another device");
+    if (!n_out) return fail(what, "NULL output");
+    *n_out = 0;
+    if (cap < 0) return fail(what, "negative capacity");
+    if (cap > 0 && !(xy_out && z_out && uvc_out && q_out)) return fail(what, "NULL output");
+    if (lit && !m->lit) return fail(what, "a mesh without normals");
+    if (m->n <= 0) return true;
+    const Mat3 N = mat3_of(normal9);
+    Soup s;
+    if (!uvc_soup(ctx, m, matrix16, lit ? &N : nullptr, &s)) return false;
+    *n_out = s.n;
+    const size_t k = (size_t)(s.n < cap ? s.n : cap);
+    copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {uvc_out, s.attr, 18}, {q_out, s.q, 3}});
+    return true;
 }
 
 // New: replaces the normals (nv*3) of a lit mesh; UpdateMeshPositions' contract.

@@ -7,7 +7,10 @@
 //   w1,w2 barycentric in f64, attr = a0 + (a1-a0)*w1 + (a2-a0)*w2 (a colour
 //   channel, or a texture coordinate whose texel is then the colour; a
 //   perspective textured batch interpolates u q, v q and q that way and
-//   samples at (U * (1 / Q), V * (1 / Q)));
+//   samples at (U * (1 / Q), V * (1 / Q)); a modulated batch does that and
+//   also interpolates a colour G per corner that way: src_c = T_c * G_c, the
+//   texel times the colour, one rounded product per channel r, g, b, A -- the
+//   alpha of a texture without alpha the literal 1.0);
 //   depth u32 LESS, written only when test+write are on;
 //   blend = ApplyPixel (cpp:515-549) in submission order.
 //
@@ -32,30 +35,45 @@ constexpr int TH = 32;   // tile height
 // with a 1/w per vertex, FrameParams::q (ATTR_TEX_PERSP).  The
 // two _BIL modes are those two with the bilinear filter (SetTriangleTextureFilter,
 // tex_bilinear) in place of the nearest texel: the same batch, record and
-// coordinates, four texels per fragment.
+// coordinates, four texels per fragment.  The two modulated modes (ATTR_TEXC nearest, ATTR_TEXC_BIL
+// bilinear; DESIGN.md §3 "Modulated textured draws") are perspective textured batches that also carry a
+// colour per corner: the fragment's source is the texel times the interpolated colour, channel by channel.
 enum AttrMode {
-    ATTR_FLAT = 0, ATTR_GOURAUD = 1, ATTR_TEX = 2, ATTR_TEX_PERSP = 3, ATTR_TEX_BIL = 4, ATTR_TEX_PERSP_BIL = 5
+    ATTR_FLAT = 0, ATTR_GOURAUD = 1, ATTR_TEX = 2, ATTR_TEX_PERSP = 3, ATTR_TEX_BIL = 4, ATTR_TEX_PERSP_BIL = 5,
+    ATTR_TEXC = 6, ATTR_TEXC_BIL = 7
 };
-// any textured mode: the attribute array is the uv array, the colour a texel (or four, filtered)
-__host__ __device__ constexpr bool attr_textured(int mode) { return mode >= ATTR_TEX && mode <= ATTR_TEX_PERSP_BIL; }
-__host__ __device__ constexpr bool attr_persp(int mode) { return mode == ATTR_TEX_PERSP || mode == ATTR_TEX_PERSP_BIL; }
-__host__ __device__ constexpr bool attr_bilinear(int mode) { return mode == ATTR_TEX_BIL || mode == ATTR_TEX_PERSP_BIL; }
+// any textured mode: the colour is a texel (or four, filtered); the attribute array holds the uv -- alone
+// (n*6), or in a modulated mode interleaved with the corner colours (n*18)
+__host__ __device__ constexpr bool attr_textured(int mode) { return mode >= ATTR_TEX && mode <= ATTR_TEXC_BIL; }
+// texel times interpolated vertex colour
+__host__ __device__ constexpr bool attr_modulated(int mode) { return mode == ATTR_TEXC || mode == ATTR_TEXC_BIL; }
+__host__ __device__ constexpr bool attr_persp(int mode) {
+    return mode == ATTR_TEX_PERSP || mode == ATTR_TEX_PERSP_BIL || attr_modulated(mode);
+}
+__host__ __device__ constexpr bool attr_bilinear(int mode) {
+    return mode == ATTR_TEX_BIL || mode == ATTR_TEX_PERSP_BIL || mode == ATTR_TEXC_BIL;
+}
 // the nearest mode whose per-triangle data (record, setup slots) a textured mode shares
 __host__ __device__ constexpr int attr_unfiltered(int mode) {
-    return mode == ATTR_TEX_BIL ? ATTR_TEX : (mode == ATTR_TEX_PERSP_BIL ? ATTR_TEX_PERSP : mode);
+    return mode == ATTR_TEX_BIL ? ATTR_TEX
+           : (mode == ATTR_TEX_PERSP_BIL ? ATTR_TEX_PERSP : (mode == ATTR_TEXC_BIL ? ATTR_TEXC : mode));
 }
 
 struct TriSrc {
     const f64* xy;    // n*6
     const f64* z;     // n*3 or null
-    const f64* attr;  // by mode: colours n*4 flat / n*12 Gouraud, or uv n*6 textured (u0 v0 u1 v1 u2 v2)
+    const f64* attr;  // by mode: colours n*4 flat / n*12 Gouraud, uv n*6 textured (u0 v0 u1 v1 u2 v2), or
+                      // n*18 modulated: per corner (u v | r g | b a), three 16-byte words
     int mode;         // AttrMode
     i64 n;
     __host__ __device__ const f64* rgba() const { return attr; }   // (flat / Gouraud batches)
-    __host__ __device__ const f64* uv() const { return attr; }     // (textured batches)
+    __host__ __device__ const f64* uv() const { return attr; }     // (textured batches that are not modulated)
+    __host__ __device__ const f64* uvc() const { return attr; }    // (modulated batches)
 };
 // doubles of the attribute array per triangle
-__host__ __device__ inline int attr_stride(int mode) { return mode == ATTR_GOURAUD ? 12 : (attr_textured(mode) ? 6 : 4); }
+__host__ __device__ inline int attr_stride(int mode) {
+    return mode == ATTR_GOURAUD ? 12 : (attr_modulated(mode) ? 18 : (attr_textured(mode) ? 6 : 4));
+}
 
 // The texture a textured batch samples (tex_index, tex_bilinear): texels as the
 // framebuffer stores them, ipp doubles each, w >= 2 and h >= 2 (a side below
@@ -128,7 +146,7 @@ __device__ __forceinline__ void load_tri_xy(const f64* xy, i64 t, f64 (&v)[6]) {
     }
 }
 
-template <int N>   // 4 (flat) or 12 (Gouraud)
+template <int N>   // 4 (flat), 12 (Gouraud) or 18 (modulated: uv and colour interleaved)
 __device__ __forceinline__ void load_tri_rgba(const f64* rgba, i64 t, f64 (&c)[N]) {
     const double2* q = reinterpret_cast<const double2*>(rgba + t * N);
 #pragma unroll
@@ -596,6 +614,7 @@ struct Soup {
 struct Batch {
     TriSrc src;
     const f64* q;                                 // perspective textured batches: the corners' 1/w (else null)
+    bool modulated = false;                       // textured: src.attr is n*18, uv and colour per corner (q is set)
     TexView tex = tex_view(nullptr, 2, 2, false); // textured modes: what draw_textured resolved
     Opacity opq;
     TriangleBuffer* tb;   // non-null: the batch is that (immutable) buffer -- its binning may overlap the previous
@@ -653,7 +672,7 @@ bool key_cache_totals(RenderContext* ctx, i64* out3);      // the key cache's ca
 
 // the batch entry points behind every triangle draw call (nr_tri.hip), shared with the mesh front end
 // (nr_mesh.hip): draw picks the raster; draw_textured first completes the batch from the texture (its view, the
-// mode by b.q, the opacity by the texture's alpha).  check_texture: a texture's preconditions, an error latched
+// mode by b.q and b.modulated, the opacity by the texture's alpha and, modulated, the corner alphas).  check_texture: a texture's preconditions, an error latched
 // under the caller's name `what` when one fails
 void draw(RenderContext* ctx, const Batch& b);
 bool check_texture(RenderContext* ctx, const Texture* tex, const char* what);

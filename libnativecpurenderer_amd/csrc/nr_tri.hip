@@ -157,6 +157,14 @@ Opacity host_opacity(const f64* rgba, i64 n, bool gouraud) {
     return OPQ_OPAQUE;
 }
 
+// A modulated batch's corner alphas: doubles 5, 11, 17 of each triangle's 18 (u v | r g | b a per corner).
+Opacity host_opacity_uvc(const f64* uvc, i64 n) {
+    for (i64 t = 0; t < n; ++t)
+        for (int v = 0; v < 3; ++v)
+            if (uvc[t * 18 + v * 6 + 5] != 1) return OPQ_BLENDED;
+    return OPQ_OPAQUE;
+}
+
 // Opacity of a device-resident batch the host cannot inspect.
 __global__ __launch_bounds__(256) void k_opacity(const f64* __restrict__ rgba, i64 n, int gouraud,
                                                  u32* __restrict__ nonopaque) {
@@ -174,12 +182,28 @@ __global__ __launch_bounds__(256) void k_opacity(const f64* __restrict__ rgba, i
     if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicOr(nonopaque, 1u);
 }
 
+// The same for a modulated batch (a kernel of its own: k_opacity stays as it is).
+__global__ __launch_bounds__(256) void k_opacity_uvc(const f64* __restrict__ uvc, i64 n, u32* __restrict__ nonopaque) {
+    const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
+    bool bad = false;
+    if (t < n) {
+        const f64* a = uvc + t * 18;
+        bad = a[5] != 1 || a[11] != 1 || a[17] != 1;
+    }
+    const unsigned long long m = __ballot(bad);
+    if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicOr(nonopaque, 1u);
+}
+
 Opacity device_opacity(RenderContext* ctx, const TriSrc& src) {
     TriScratch& sc = ctx->tri;
     if (!sc.d_flag) NR_CHECK(hipMalloc(&sc.d_flag, sizeof(u32)));
     NR_CHECK(hipMemsetAsync(sc.d_flag, 0, sizeof(u32), ctx->stream));
-    hipLaunchKernelGGL(k_opacity, dim3((unsigned)((src.n + 255) / 256)), dim3(256), 0, ctx->stream, src.rgba(), src.n,
-                       src.mode == ATTR_GOURAUD ? 1 : 0, sc.d_flag);
+    if (attr_modulated(src.mode))
+        hipLaunchKernelGGL(k_opacity_uvc, dim3((unsigned)((src.n + 255) / 256)), dim3(256), 0, ctx->stream, src.uvc(),
+                           src.n, sc.d_flag);
+    else
+        hipLaunchKernelGGL(k_opacity, dim3((unsigned)((src.n + 255) / 256)), dim3(256), 0, ctx->stream, src.rgba(),
+                           src.n, src.mode == ATTR_GOURAUD ? 1 : 0, sc.d_flag);
     NR_CHECK(hipGetLastError());
     u32* h = reinterpret_cast<u32*>(&sc.totals()[3]);
     NR_CHECK(hipMemcpyAsync(h, sc.d_flag, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
@@ -218,16 +242,21 @@ bool check_texture(RenderContext* ctx, const Texture* tex, const char* what) {
     return false;
 }
 
-// b.q non-null: a perspective textured batch.  The context's filter
+// b.q non-null: a perspective textured batch; b.modulated: one whose attributes also carry the corner colours
+// (src.attr n*18, b.q required).  The context's filter
 // (SetTriangleTextureFilter) is read here, when the draw is issued: the mode is
 // part of the batch's snapshot, so a pending batch or its re-run keeps it.
 void draw_textured(RenderContext* ctx, Texture* tex, Batch& b) {
     settle(ctx);   // (a re-run of the pending batch comes before a snapshot of the target)
     TexSrc ts = nr_tex_source(ctx, tex);
     b.tex = tex_view(ts.ptr, tex->width, tex->height, tex->enableAlpha);
-    if (ctx->texFilter) b.src.mode = b.q ? ATTR_TEX_PERSP_BIL : ATTR_TEX_BIL;
+    if (b.modulated) b.src.mode = ctx->texFilter ? ATTR_TEXC_BIL : ATTR_TEXC;
+    else if (ctx->texFilter) b.src.mode = b.q ? ATTR_TEX_PERSP_BIL : ATTR_TEX_BIL;
     else b.src.mode = b.q ? ATTR_TEX_PERSP : ATTR_TEX;
-    b.opq = tex->enableAlpha ? OPQ_BLENDED : OPQ_OPAQUE;
+    // (modulated: opaque when also every corner alpha is 1 -- b.opq as the caller found it, or OPQ_UNKNOWN: draw
+    // scans the batch on the device, and only when the colour transform and the raster override leave it a choice)
+    if (tex->enableAlpha) b.opq = OPQ_BLENDED;
+    else if (!b.modulated) b.opq = OPQ_OPAQUE;
     draw(ctx, b);
     if (ts.tmp) {   // (rare: the snapshot must outlive the batch and any re-run of it)
         settle(ctx);
@@ -295,19 +324,30 @@ static bool stage_soup(RenderContext* ctx, Soup& s, size_t ncol, bool onDevice, 
     return true;
 }
 
-// The four textured soup entry points, under the caller's name `what`; persp: s.q is required.
-static void draw_textured_soup(RenderContext* ctx, Texture* tex, Soup s, bool persp, bool onDevice, const char* what) {
+// The six textured soup entry points, under the caller's name `what`; persp: s.q is required; modulated (persp
+// too): s.attr is the n*18 uvc array, required.
+static void draw_textured_soup(RenderContext* ctx, Texture* tex, Soup s, bool persp, bool onDevice, const char* what,
+                               bool modulated = false) {
     NR_CHECK(hipSetDevice(ctx->device));
     nr_settle(ctx);   // a pending batch may still read the staging buffer; recorded draws come first
     if (!check_texture(ctx, tex, what)) return;
+    if (modulated && !s.attr) {
+        nr_set_error_msg((std::string(what) + ": NULL uvc").c_str());
+        return;
+    }
     if (persp && !s.q) {
         nr_set_error_msg((std::string(what) + ": NULL q").c_str());
         return;
     }
     if (s.n <= 0) return;
+    // (a host soup's corner alphas are looked at only where the answer can matter: draw_textured)
+    Opacity opq = OPQ_UNKNOWN;
+    if (modulated && !onDevice && !tex->enableAlpha && ctx->ct[3] == 1 && ctx->forceOrdered == 0)
+        opq = host_opacity_uvc(s.attr, s.n);
     bool callerOwned;
-    if (!stage_soup(ctx, s, 6, onDevice, &callerOwned)) return;
-    Batch b = soup_batch(s, ATTR_TEX, OPQ_UNKNOWN, nullptr, callerOwned);   // (mode and opacity: draw_textured)
+    if (!stage_soup(ctx, s, modulated ? 18 : 6, onDevice, &callerOwned)) return;
+    Batch b = soup_batch(s, ATTR_TEX, opq, nullptr, callerOwned);   // (mode and opacity: draw_textured)
+    b.modulated = modulated;
     draw_textured(ctx, tex, b);
 }
 
@@ -403,6 +443,23 @@ void DrawTexturedTrianglesPerspective(RenderContext* ctx, Texture* tex, const f6
 void DrawTexturedTrianglesPerspectiveDevice(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z,
                                             const f64* uv, const f64* q, i64 n) {
     draw_textured_soup(ctx, tex, Soup{xy, z, uv, q, n}, true, true, "DrawTexturedTrianglesPerspectiveDevice");
+}
+
+// New: modulated textured triangles from host arrays (DESIGN.md §3 "Modulated textured draws"): uvc, n*18, is
+// per corner (u, v, r, g, b, a); q as DrawTexturedTrianglesPerspective's (all 1.0 for affine mapping).  The
+// fragment's source is the texel at the perspective-correct (u, v), by the context's filter, times the
+// interpolated corner colour, channel by channel.  A NULL uvc or a NULL q latches an error and draws nothing;
+// otherwise as DrawTexturedTriangles.
+void DrawTexturedTrianglesModulated(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z, const f64* uvc,
+                                    const f64* q, i64 n) {
+    draw_textured_soup(ctx, tex, Soup{xy, z, uvc, q, n}, true, false, "DrawTexturedTrianglesModulated", true);
+}
+
+// New: the same from device-resident arrays (DrawTrianglesDevice's rules: xy and uvc are re-staged when not
+// 16-byte aligned; z and q stay the caller's).
+void DrawTexturedTrianglesModulatedDevice(RenderContext* ctx, Texture* tex, const f64* xy, const f64* z,
+                                          const f64* uvc, const f64* q, i64 n) {
+    draw_textured_soup(ctx, tex, Soup{xy, z, uvc, q, n}, true, true, "DrawTexturedTrianglesModulatedDevice", true);
 }
 
 // New: a device-resident triangle soup (the H2D point; drawn many times).

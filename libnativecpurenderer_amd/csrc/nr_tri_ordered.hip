@@ -104,8 +104,14 @@ enum {
     S_FR = S_D2 + 4, S_FG, S_FB, S_FA,         // src * colourTransform
     S_OM, S_RA, S_GA, S_BA,                    // 1 - a, src * a
     S_SL0, S_SL1, S_SL2,                       // edge slopes (edge_slopes) for the division-free spans
-    S_NSLOT
+    S_NSLOT,
+    // modulated textured: the perspective layout above, the corner alphas A0, A1-A0, A2-A0 in
+    // its three free slots S_C0 + 3, S_D1 + 3, S_D2 + 3 (where Gouraud keeps alpha), and the nine rgb terms
+    // c0 rgb | c1-c0 rgb | c2-c0 rgb in the eight flat-only slots S_FR..S_BA, dead in every textured mode,
+    // and one slot of its own past S_NSLOT (its instances alone stage S_NSLOT + 1 slots)
+    S_MC0 = S_FR, S_MD1 = S_FR + 3, S_MD2 = S_FR + 6, S_MB2 = S_NSLOT, S_NSLOT_MOD
 };
+static_assert(S_MD2 + 1 == S_BA && S_MB2 + 1 == S_NSLOT_MOD, "modulated colours: eight flat-only slots and one more");
 
 __device__ __forceinline__ u64 uniform_u64(u64 v) {   // (a wave-uniform value into scalar registers)
     return ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
@@ -135,13 +141,17 @@ __device__ __forceinline__ u64 window_bits(int xs, int xe) {
 // Q = q in three of those slots and samples at (U / Q, V / Q) (as U * (1 / Q)).
 // A bilinear mode differs in the blend loop only: four texels (tex_bilinear)
 // filtered into R, G, B (and A from an RGBA texture) before ApplyPixel.
+// A modulated mode (ATTR_TEXC, ATTR_TEXC_BIL) is the perspective mode of its
+// filter with the corner colour interpolated beside U, V, Q; the texel is
+// multiplied by it, channel by channel, before ApplyPixel.
 // 4 waves per SIMD (6: 80 VGPRs, 85 spilled -- C5 raster 740 -> 1355 us)
 template <int MODE, bool DEPTH, bool COUNT, bool RGBA, bool BINNED>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_tile_raster(const FrameParams fp, const u32* __restrict__ list,
                                                     const u32* __restrict__ tstart, const u32* __restrict__ tend,
                                                     const f64* __restrict__ rec, const u32* __restrict__ plan) {
     constexpr bool GOURAUD = MODE == ATTR_GOURAUD, TEX = attr_textured(MODE), PERSP = attr_persp(MODE);
-    constexpr bool BIL = attr_bilinear(MODE);
+    constexpr bool BIL = attr_bilinear(MODE), MOD = attr_modulated(MODE);
+    constexpr int NS = MOD ? S_NSLOT_MOD : S_NSLOT;
     constexpr bool FLATC = MODE == ATTR_FLAT;   // one colour per triangle: the per-triangle blend terms apply
     const int tile = blockIdx.x;
     const int tx = tile % fp.tiles_x, ty = tile / fp.tiles_x;
@@ -153,7 +163,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
     if (!owned_row(ty, fp.period, fp.mask)) return;
     const u32 ls = tstart[tile], le = BINNED ? tstart[tile + 1] : tend[tile];
     if (ls == le && !fp.pendColor && !(DEPTH && fp.pendDepth)) return;
-    __shared__ f64 S[2][S_NSLOT][CH];   // (two chunks: one set up while the other is blended)
+    __shared__ f64 S[2][NS][CH];   // (two chunks: one set up while the other is blended)
     // the lane masks of a wave's RPW steps for triangle k (bit l: lane l's
     // pixel of that step is covered), formed by the span phase's 512 threads
     // in VALU: the blend loop only moves them into scalar registers and sets
@@ -246,7 +256,25 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                 zok = !fp.depthWrite && zb < zTileMin;   // zpass_all
                 ZPASS[sb][k] = zok;
             }
-            if (PERSP) {
+            if constexpr (MOD) {
+                f64 a[18];   // per corner (u v | r g | b A)
+                load_tri_rgba<18>(fp.src.uvc(), t, a);
+                const f64* qs = fp.q + t * 3;
+                const f64 q0 = qs[0], q1 = qs[1], q2 = qs[2];
+                const f64 a0 = a[0] * q0, b0 = a[1] * q0, a1 = a[6] * q1, b1 = a[7] * q1;
+                const f64 a2 = a[12] * q2, b2 = a[13] * q2;
+                S[sb][S_C0][k] = a0; S[sb][S_C0 + 1][k] = b0; S[sb][S_C0 + 2][k] = q0;
+                S[sb][S_D1][k] = a1 - a0; S[sb][S_D1 + 1][k] = b1 - b0; S[sb][S_D1 + 2][k] = q1 - q0;
+                S[sb][S_D2][k] = a2 - a0; S[sb][S_D2 + 1][k] = b2 - b0; S[sb][S_D2 + 2][k] = q2 - q0;
+                S[sb][S_C0 + 3][k] = a[5]; S[sb][S_D1 + 3][k] = a[11] - a[5]; S[sb][S_D2 + 3][k] = a[17] - a[5];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    S[sb][S_MC0 + j][k] = a[2 + j];
+                    S[sb][S_MD1 + j][k] = a[8 + j] - a[2 + j];
+                }
+                S[sb][S_MD2][k] = a[14] - a[2]; S[sb][S_MD2 + 1][k] = a[15] - a[3];
+                S[sb][S_MB2][k] = a[16] - a[4];
+            } else if (PERSP) {
                 f64 uv[6];
                 load_tri_xy(fp.src.uv(), t, uv);
                 const f64* qs = fp.q + t * 3;
@@ -481,6 +509,12 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                         R = tq[0]; G = tq[1]; B = tq[2];
                         A = fp.tex.ipp == 4 ? tq[3] : 1.0;
                     }
+                    if constexpr (MOD) {   // texel times the interpolated corner colour, one rounded product per channel
+                        R = R * (S[sb][S_MC0 + 0][k] + S[sb][S_MD1 + 0][k] * w1 + S[sb][S_MD2 + 0][k] * w2);
+                        G = G * (S[sb][S_MC0 + 1][k] + S[sb][S_MD1 + 1][k] * w1 + S[sb][S_MD2 + 1][k] * w2);
+                        B = B * (S[sb][S_MC0 + 2][k] + S[sb][S_MD1 + 2][k] * w1 + S[sb][S_MB2][k] * w2);
+                        A = A * (S[sb][S_C0 + 3][k] + S[sb][S_D1 + 3][k] * w1 + S[sb][S_D2 + 3][k] * w2);
+                    }
                     // ApplyPixel (cpp:529-547) on the register-resident pixel
                     R *= ct0; G *= ct1; B *= ct2; A *= ct3;
                     if (A != 1) {
@@ -606,7 +640,12 @@ void launch_raster_c(const FrameParams& fp, const u32* list, const u32* ts, cons
     const bool g = fp.src.mode == ATTR_GOURAUD, t = fp.src.mode == ATTR_TEX, d = fp.depthTest != 0;
     const bool p = fp.src.mode == ATTR_TEX_PERSP;
     const bool tb = fp.src.mode == ATTR_TEX_BIL, pb = fp.src.mode == ATTR_TEX_PERSP_BIL;
-    if (pb && d) launch_raster<ATTR_TEX_PERSP_BIL, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    const bool mc = fp.src.mode == ATTR_TEXC, mb = fp.src.mode == ATTR_TEXC_BIL;
+    if (mb && d) launch_raster<ATTR_TEXC_BIL, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (mb) launch_raster<ATTR_TEXC_BIL, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (mc && d) launch_raster<ATTR_TEXC, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (mc) launch_raster<ATTR_TEXC, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
+    else if (pb && d) launch_raster<ATTR_TEX_PERSP_BIL, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
     else if (pb) launch_raster<ATTR_TEX_PERSP_BIL, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
     else if (tb && d) launch_raster<ATTR_TEX_BIL, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);
     else if (tb) launch_raster<ATTR_TEX_BIL, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop);

@@ -31,12 +31,14 @@ namespace nrtri {
 // geometry terms | u0 v0 | (u1-u0) (v1-v0) | (u2-u0) (v2-v0): 13 doubles in
 // the Gouraud record's 16-double slot; perspective textured the 7 geometry
 // terms | a0 b0 | (a1-a0) (b1-b0) | (a2-a0) (b2-b0) | q0 (q1-q0) (q2-q0) with
-// a_k = u_k * q_k, b_k = v_k * q_k: all 16.  MODE: AttrMode; a bilinear mode
-// has no record code of its own -- shade_tile stages its batch with the
-// record of its nearest counterpart (attr_unfiltered).
+// a_k = u_k * q_k, b_k = v_k * q_k: all 16; modulated those 16 | c0 rgb |
+// (c1-c0) rgb | (c2-c0) rgb of the corner colours: 25 (an odd stride: the
+// records are read as single doubles, 8-byte aligned).  MODE: AttrMode; a
+// bilinear mode has no record code of its own -- shade_tile stages its batch
+// with the record of its nearest counterpart (attr_unfiltered).
 template <int MODE>
 struct RecLen {
-    static constexpr int REC = MODE != ATTR_FLAT ? 16 : 3;
+    static constexpr int REC = attr_modulated(MODE) ? 25 : (MODE != ATTR_FLAT ? 16 : 3);
 };
 
 // Depth of a shaded pixel (winner kv; (u32)kv == 0: no fragment won it):
@@ -92,8 +94,9 @@ __device__ __forceinline__ void store_clear(const FrameParams& fp, i64 p, i64 px
 template <int MODE>
 struct RecordSrc {
     f64 p[MODE != ATTR_FLAT ? 6 : 1];
-    // textured: the six uv; perspective textured: the six uv, then the three q
-    f64 c[MODE == ATTR_GOURAUD || MODE == ATTR_TEX_PERSP ? 9 : (MODE == ATTR_TEX ? 6 : 3)];
+    // textured: the six uv; perspective textured: the six uv, then the three q; modulated: those nine, then
+    // the rgb of each corner
+    f64 c[MODE == ATTR_TEXC ? 18 : (MODE == ATTR_GOURAUD || MODE == ATTR_TEX_PERSP ? 9 : (MODE == ATTR_TEX ? 6 : 3))];
 };
 
 template <int MODE>
@@ -110,6 +113,18 @@ __device__ __forceinline__ void load_record_src(const FrameParams& fp, i64 t, Re
 #pragma unroll
         for (int k = 0; k < 6; ++k) s.c[k] = uv[k];
         const f64* q = fp.q + t * 3;   // (8-byte aligned only: n*3 doubles per batch, like z)
+        s.c[6] = q[0]; s.c[7] = q[1]; s.c[8] = q[2];
+        return;
+    }
+    if constexpr (MODE == ATTR_TEXC) {
+        f64 a[18];   // per corner (u v | r g | b a)
+        load_tri_rgba<18>(fp.src.uvc(), t, a);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            s.c[2 * k] = a[6 * k]; s.c[2 * k + 1] = a[6 * k + 1];
+            s.c[9 + 3 * k] = a[6 * k + 2]; s.c[10 + 3 * k] = a[6 * k + 3]; s.c[11 + 3 * k] = a[6 * k + 4];
+        }
+        const f64* q = fp.q + t * 3;
         s.c[6] = q[0]; s.c[7] = q[1]; s.c[8] = q[2];
         return;
     }
@@ -135,7 +150,7 @@ __device__ __forceinline__ void build_record(const FrameParams& fp, const Record
         r[7] = s.c[0]; r[8] = s.c[1];
         r[9] = s.c[2] - s.c[0]; r[10] = s.c[3] - s.c[1];
         r[11] = s.c[4] - s.c[0]; r[12] = s.c[5] - s.c[1];
-    } else if constexpr (MODE == ATTR_TEX_PERSP) {
+    } else if constexpr (MODE == ATTR_TEX_PERSP || MODE == ATTR_TEXC) {
         f64 sx[3], sy[3];
 #pragma unroll
         for (int v = 0; v < 3; ++v) nr_xform(fp.m, s.p[2 * v], s.p[2 * v + 1], sx[v], sy[v]);
@@ -150,6 +165,14 @@ __device__ __forceinline__ void build_record(const FrameParams& fp, const Record
         r[9] = a1 - a0; r[10] = b1 - b0;
         r[11] = a2 - a0; r[12] = b2 - b0;
         r[13] = s.c[6]; r[14] = s.c[7] - s.c[6]; r[15] = s.c[8] - s.c[6];
+        if constexpr (MODE == ATTR_TEXC) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                r[16 + k] = s.c[9 + k];
+                r[19 + k] = s.c[12 + k] - s.c[9 + k];
+                r[22 + k] = s.c[15 + k] - s.c[9 + k];
+            }
+        }
     } else if constexpr (MODE == ATTR_GOURAUD) {
         f64 sx[3], sy[3];
 #pragma unroll
@@ -224,6 +247,21 @@ __device__ __forceinline__ void mix_tex_quad(const TexQuad& t, f64 fu, f64 fv, f
     cb = bilinear_mix(t.c[0][2], t.c[1][2], t.c[2][2], t.c[3][2], fu, fv, gu, gv);
 }
 
+// A modulated record's interpolated corner colour G at pixel (px, py), times the texel (or filtered) colour in
+// cr, cg, cb: one rounded product per channel.  The barycentrics are formed again from the record (the same
+// expressions as record_uv, so the same values) rather than kept across the texel gather.  Alpha: the texel's
+// literal 1 times 1 + 0*w1 + 0*w2 -- only batches whose every corner alpha is 1, over a texture without alpha,
+// are routed to the order-free raster.
+__device__ __forceinline__ void record_modulate(const f64* r, i64 px, i64 py, f64& cr, f64& cg, f64& cb, f64& ca) {
+    const f64 dx = (f64)px - r[0], dy = (f64)py - r[1];
+    const f64 w1 = (dx * r[5] - r[4] * dy) * r[6];
+    const f64 w2 = (r[2] * dy - dx * r[3]) * r[6];
+    cr = cr * (r[16] + r[19] * w1 + r[22] * w2);
+    cg = cg * (r[17] + r[20] * w1 + r[23] * w2);
+    cb = cb * (r[18] + r[21] * w1 + r[24] * w2);
+    ca = 1.0 * (1.0 + 0.0 * w1 + 0.0 * w2);
+}
+
 // Colour of pixel (px, py) from a record.  (Textured: the texel's rgb from
 // the view tv, an ordinary cached load -- the filtered rgb of four in a
 // bilinear mode; alpha is the literal 1 -- only textures without alpha are
@@ -238,9 +276,11 @@ __device__ __forceinline__ void record_colour(const TexView& tv, const f64* r, i
         load_tex_quad(tv, tex_bilinear(tv, u, v, fu, fv), t);
         mix_tex_quad(t, fu, fv, cr, cg, cb);
         ca = 1.0;
+        if constexpr (attr_modulated(MODE)) record_modulate(r, px, py, cr, cg, cb, ca);
     } else if constexpr (attr_textured(MODE)) {
         const f64* q = tv.ptr + record_texel_of<MODE>(tv, r, px, py);
         cr = q[0]; cg = q[1]; cb = q[2]; ca = 1.0;
+        if constexpr (attr_modulated(MODE)) record_modulate(r, px, py, cr, cg, cb, ca);
     } else if (MODE == ATTR_GOURAUD) {
         const f64 dx = (f64)px - r[0], dy = (f64)py - r[1];
         const f64 w1 = (dx * r[5] - r[4] * dy) * r[6];

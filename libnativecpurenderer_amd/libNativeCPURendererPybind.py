@@ -47,6 +47,14 @@ def _f64_ptr(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def interleave_uv_colors(uv, colors) -> np.ndarray:
+    """The attribute array of a modulated textured draw: (n, 18), per corner
+    (u, v, r, g, b, a), from uv (n, 6) / (n, 3, 2) and colors (n, 12) / (n, 3, 4)."""
+    uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1, 3, 2)
+    colors = np.ascontiguousarray(colors, dtype=np.float64).reshape(uv.shape[0], 3, 4)
+    return np.ascontiguousarray(np.concatenate([uv, colors], axis=2).reshape(uv.shape[0], 18))
+
+
 class Helpers:
     @staticmethod
     def get_wappered_bytes_data_ptr(bytes: int):
@@ -296,7 +304,7 @@ class RenderContext:
                 raise ValueError("a colour TriangleBuffer takes no texture")
             lib.DrawTriangleBuffer(self._ptr, buf._ptr)
 
-    def draw_textured_triangles(self, tex: "Texture", xy, uv, z=None, q=None):
+    def draw_textured_triangles(self, tex: "Texture", xy, uv, z=None, q=None, colors=None):
         """Draws n textured triangles in the current transform.
 
         xy: (n, 3, 2) or (n, 6) vertex positions; uv: (n, 3, 2) or (n, 6)
@@ -305,7 +313,11 @@ class RenderContext:
         set_triangle_texture_filter(1), bilinearly, tinted by the colour
         transform); z: (n, 3) depths in [0, 1] or None; q: (n, 3)
         per-vertex 1/w for perspective-correct sampling at (U / Q, V / Q) with
-        U, V, Q interpolated from u q, v q, q (None: affine, as before)."""
+        U, V, Q interpolated from u q, v q, q (None: affine, as before);
+        colors: (n, 12) or (n, 3, 4) per-vertex RGBA -- the modulated draw
+        (DrawTexturedTrianglesModulated): every texel is multiplied, channel by
+        channel, by the colour interpolated like a Gouraud draw's (q None:
+        all ones, affine mapping)."""
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 6)
         n = xy.shape[0]
         uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(n, 6)
@@ -313,20 +325,31 @@ class RenderContext:
         if z is not None:
             z = np.ascontiguousarray(z, dtype=np.float64).reshape(n, 3)
             zp = _f64_ptr(z)
+        if colors is not None:
+            uvc = interleave_uv_colors(uv, colors)
+            q = np.ones((n, 3)) if q is None else np.ascontiguousarray(q, dtype=np.float64).reshape(n, 3)
+            lib.DrawTexturedTrianglesModulated(self._ptr, tex._ptr, _f64_ptr(xy), zp, _f64_ptr(uvc), _f64_ptr(q), n)
+            return
         if q is not None:
             q = np.ascontiguousarray(q, dtype=np.float64).reshape(n, 3)
             lib.DrawTexturedTrianglesPerspective(self._ptr, tex._ptr, _f64_ptr(xy), zp, _f64_ptr(uv), _f64_ptr(q), n)
             return
         lib.DrawTexturedTriangles(self._ptr, tex._ptr, _f64_ptr(xy), zp, _f64_ptr(uv), n)
 
-    def draw_textured_triangles_device(self, tex: "Texture", xy, uv, n: int, z=None, q=None):
+    def draw_textured_triangles_device(self, tex: "Texture", xy, uv, n: int, z=None, q=None, colors=None):
         """DrawTexturedTrianglesDevice: xy / uv / z are device addresses or
         objects with .data_ptr(), as for draw_triangles_device; with q (the
-        per-vertex 1/w, n*3) DrawTexturedTrianglesPerspectiveDevice."""
+        per-vertex 1/w, n*3) DrawTexturedTrianglesPerspectiveDevice.  With
+        colors (any value but None), DrawTexturedTrianglesModulatedDevice: `uv`
+        is then the device array of n*18 interleaved doubles (per corner u, v,
+        r, g, b, a: interleave_uv_colors' layout) and q is required."""
         def addr(a):
             if a is None:
                 return None
             return a.data_ptr() if hasattr(a, "data_ptr") else int(a)
+        if colors is not None:
+            lib.DrawTexturedTrianglesModulatedDevice(self._ptr, tex._ptr, addr(xy), addr(z), addr(uv), addr(q), int(n))
+            return
         if q is not None:
             lib.DrawTexturedTrianglesPerspectiveDevice(self._ptr, tex._ptr, addr(xy), addr(z), addr(uv), addr(q), int(n))
             return
@@ -343,7 +366,8 @@ class RenderContext:
         """Draws a Mesh under the row-major 4x4 `matrix` (None: the identity;
         the viewport is baked into it), transformed on the device; then the
         context's transform, depth state and colour transform as for
-        draw_triangles.  A textured mesh (Mesh(..., uv=...)) takes `texture`."""
+        draw_triangles.  A textured mesh (Mesh(..., uv=...)) takes `texture`;
+        one with colours too is drawn modulated by them, unlit."""
         m, mp = self._matrix16(matrix)
         if mesh.textured:
             if texture is None:
@@ -570,14 +594,23 @@ class RenderContext:
                 raise ValueError("normal_matrices must hold one 3x3 per matrix")
         return matrices, normal_matrices, tint
 
-    def draw_mesh_lit(self, mesh: "Mesh", matrix=None, normal_matrix=None):
+    def draw_mesh_lit(self, mesh: "Mesh", matrix=None, normal_matrix=None, texture: typing.Optional["Texture"] = None):
         """draw_mesh of a lit Mesh (Mesh(..., normals=...)) with its vertex
         colours lit on the device under this context's lights; normal_matrix:
         the row-major 3x3 that takes the normals into the lights' space (None:
-        the identity).  Normals are not renormalised."""
-        self._lit_mesh(mesh)
+        the identity).  Normals are not renormalised.  With `texture`, a
+        textured colour mesh (Mesh(..., colors=..., uv=..., normals=...)):
+        DrawTexturedMeshLit, its texels times the lit colours."""
         m, mp = self._matrix16(matrix)
         nm = None if normal_matrix is None else np.ascontiguousarray(normal_matrix, dtype=np.float64).reshape(9)
+        if texture is not None:
+            if not getattr(mesh, "textured_color", False):
+                raise ValueError("a lit textured draw needs a Mesh with both colors and uv")
+            if not mesh.lit:
+                raise ValueError("a lit draw needs a Mesh created with normals")
+            lib.DrawTexturedMeshLit(self._ptr, mesh._ptr, texture._ptr, mp, None if nm is None else _f64_ptr(nm))
+            return
+        self._lit_mesh(mesh)
         lib.DrawMeshLit(self._ptr, mesh._ptr, mp, None if nm is None else _f64_ptr(nm))
 
     def draw_mesh_lit_instanced(self, mesh: "Mesh", matrices, normal_matrices=None, tint=None):
@@ -599,6 +632,26 @@ class RenderContext:
                 return None
             return a.data_ptr() if hasattr(a, "data_ptr") else int(a)
         lib.DrawMeshLitInstancedDevice(self._ptr, mesh._ptr, addr(matrices), addr(normal_matrices), addr(tint), int(k))
+
+    def assemble_textured_color_mesh(self, mesh: "Mesh", matrix=None, normal_matrix=None, lit: bool = True):
+        """(xy (n_out, 6), z (n_out, 3), uvc (n_out, 18), q (n_out, 3)): the
+        soup a draw of a textured colour mesh rasterises under this context's
+        lights, near plane, cull mode and perspective state -- lit:
+        draw_mesh_lit(..., texture=...)'s, else draw_mesh(..., texture=...)'s
+        (normal_matrix ignored); the draw's own kernels (a sync point)."""
+        m, mp = self._matrix16(matrix)
+        nm = None if normal_matrix is None else np.ascontiguousarray(normal_matrix, dtype=np.float64).reshape(9)
+        cap = 2 * mesh.triangle_count
+        xy = np.empty((cap, 6), dtype=np.float64)
+        z = np.empty((cap, 3), dtype=np.float64)
+        uvc = np.empty((cap, 18), dtype=np.float64)
+        q = np.empty((cap, 3), dtype=np.float64)
+        nout = ctypes.c_long(0)
+        if not lib.AssembleTexturedColorMesh(self._ptr, mesh._ptr, mp, None if nm is None else _f64_ptr(nm), bool(lit), cap,
+                                             _f64_ptr(xy), _f64_ptr(z), _f64_ptr(uvc), _f64_ptr(q), ctypes.byref(nout)):
+            raise RuntimeError("AssembleTexturedColorMesh failed: " + _lib.last_error())
+        k = nout.value
+        return xy[:k].copy(), z[:k].copy(), uvc[:k].copy(), q[:k].copy()
 
     def assemble_mesh_lit(self, mesh: "Mesh", matrix=None, normal_matrix=None):
         """(xy (n_out, 6), z (n_out, 3), attr (n_out, 12 Gouraud / 4 flat)):
@@ -1278,13 +1331,15 @@ class Mesh:
     def __init__(self, positions, indices, colors=None, uv=None, gouraud: typing.Optional[bool] = None,
                  normals=None):
         """positions: (nv, 3); indices: (n, 3) integers < nv (stored as
-        uint32); exactly one of colors ((nv, 4) RGBA per vertex; gouraud
-        (default) interpolates them, flat takes each triangle's first index)
-        and uv ((nv, 2) texel coordinates: a textured mesh).  normals ((nv, 3),
-        a colour mesh only): a lit mesh, for RenderContext.draw_mesh_lit."""
-        if (colors is None) == (uv is None):
-            raise ValueError("exactly one of colors and uv")
-        if normals is not None and uv is not None:
+        uint32); colors ((nv, 4) RGBA per vertex; gouraud (default)
+        interpolates them, flat takes each triangle's first index) or uv
+        ((nv, 2) texel coordinates: a textured mesh), or both: a textured
+        colour mesh, whose texels are multiplied by its interpolated colours
+        (always Gouraud).  normals ((nv, 3), a mesh with colours only): a lit
+        mesh, for RenderContext.draw_mesh_lit."""
+        if colors is None and uv is None:
+            raise ValueError("a Mesh needs colors, uv or both")
+        if normals is not None and colors is None:
             raise ValueError("a textured Mesh takes no normals")
         pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
         nv = pos.shape[0]
@@ -1294,9 +1349,17 @@ class Mesh:
         idx = np.ascontiguousarray(ind, dtype=np.uint32).reshape(-1, 3)
         n = idx.shape[0]
         self.textured = uv is not None
+        self.textured_color = uv is not None and colors is not None
         self._can_release = False
         ip = idx.ctypes.data_as(ctypes.c_void_p)
-        if self.textured:
+        if self.textured_color:
+            uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(nv, 2)
+            colors = np.ascontiguousarray(colors, dtype=np.float64).reshape(nv, 4)
+            nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float64).reshape(nv, 3)
+            self.gouraud = True
+            self._ptr = _check(lib.CreateTexturedColorMesh(nv, _f64_ptr(pos), None if nrm is None else _f64_ptr(nrm), n,
+                                                           ip, _f64_ptr(uv), _f64_ptr(colors)), "CreateTexturedColorMesh")
+        elif self.textured:
             uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(nv, 2)
             self.gouraud = False
             self._ptr = _check(lib.CreateTexturedMesh(nv, _f64_ptr(pos), n, ip, _f64_ptr(uv)), "CreateTexturedMesh")
