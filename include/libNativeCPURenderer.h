@@ -200,6 +200,23 @@ void DrawTexturedTriangleBuffer(RenderContext* ctx, TriangleBuffer* tb, Texture*
    Any other mode latches an error, leaves the state unchanged and returns false. */
 bool SetTriangleTextureFilter(RenderContext* ctx, i64 mode);             /* NEW */
 i64 GetTriangleTextureFilter(RenderContext* ctx);                        /* NEW */
+/* NEW: the wrap addressing of the textured triangle draws (DESIGN §3 "Wrap addressing"), per axis: 0 clamp (the
+   default: the samplers above), 1 repeat, 2 mirrored repeat.  Per axis (columns: n = w, x = u; rows: n = h, x = v),
+   with P = (f64)n for repeat and (f64)(2n) for mirror, in f64, every operation rounded in the order written, the
+   divide IEEE:
+       k = floor(x / P);  t = x - k * P;  if !(t >= 0) t = 0;  if (t >= P) t = 0
+       i0 = (i64)t;  f = t - i0;  i1 = i0 + 1, or 0 when that is P
+       c(j) = j (repeat);  c(j) = j < n ? j : 2n - 1 - j (mirror)
+   The nearest filter takes texel c(i0); the bilinear filter c(i0) and c(i1) with weights 1 - f and f.  The axes are
+   independent: one may clamp while the other wraps.  Texel centres stay on the integer lattice (no half-texel
+   offset), so a seamless tile needs no duplicated edge texel.  Every coordinate (NaN, infinite, huge, negative)
+   gives in-range texels; nothing is validated.  For x in [0, n-1) all three modes give the same footprint.  It
+   covers everything SetTriangleTextureFilter covers and the Modulated, MeshInstanced and MeshLit textured draws;
+   colour draws, DrawTexture, DrawSplittedTexture and ResampleTexture are untouched.  Per context, not saved /
+   restored, not recorded; read when a draw is issued (a pending batch keeps its state).  A mode outside 0..2 on
+   either axis latches an error, leaves both axes unchanged and returns false. */
+bool SetTriangleTextureWrap(RenderContext* ctx, i64 modeU, i64 modeV);   /* NEW */
+void GetTriangleTextureWrap(RenderContext* ctx, i64* modeU, i64* modeV); /* NEW */
 /* NEW: indexed 3D meshes (DESIGN §3 "Vertex stage").  nv vertices pos (px, py, pz), n triangles as u32 index
    triples, one per-vertex attribute: RGBA nv*4 (flat = the colour of a triangle's first index, or Gouraud) or
    texel-unit UVs nv*2.  Uploaded once; each draw transforms the vertices on the device by a row-major 4x4

@@ -86,6 +86,8 @@ DEVICE_ABI = {
     "DrawTexturedTriangleBuffer": (None, (P, P, P)),
     "SetTriangleTextureFilter": (B, (P, L)),
     "GetTriangleTextureFilter": (L, (P,)),
+    "SetTriangleTextureWrap": (B, (P, L, L)),
+    "GetTriangleTextureWrap": (None, (P, P, P)),
     "CreateMesh": (P, (L, P, L, P, P, B)),
     "CreateTexturedMesh": (P, (L, P, L, P, P)),
     "DestroyMesh": (None, (P,)),

@@ -422,6 +422,7 @@ struct RenderContext {
     int meshCull = 0;
     bool meshPersp = false;           // textured mesh draws carry 1/cw to the rasters (SetMeshPerspective); same rule
     int texFilter = 0;                // textured triangle draws: 0 nearest, 1 bilinear (SetTriangleTextureFilter); same rule
+    int texWrapU = 0, texWrapV = 0;   // their wrap addressing per axis: 0 clamp, 1 repeat, 2 mirror (SetTriangleTextureWrap); same rule
     i64 meshLastCount = 0;
     MeshLights meshLights;            // lit mesh draws (SetMeshLights): ambient (1, 1, 1), no lights; same rule
     iu8* u8buf = nullptr; size_t u8cap = 0;   // GetBufferAsUInt8 staging

@@ -127,9 +127,11 @@ __device__ __forceinline__ int staged_record(const u32* ht, const unsigned short
 __device__ __forceinline__ void mark_winner(const FrameParams& fp, u32 id) {
     __hip_atomic_fetch_or(&fp.winMask[(id - 1) >> 5], 1u << ((id - 1) & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <int ZMODE, int MODE, int NT, int HS, bool MARK = false>
+template <int ZMODE, int MODEW, int NT, int HS, bool MARK = false>   // MODEW: the AttrMode, with ATTR_WRAPS for a wrapping instance
 __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0, int wlim, int hlim,
                                            const u64* key, unsigned char* lds, u32& nU) {
+    constexpr int MODE = attr_base(MODEW);
+    constexpr bool WRAP = attr_wraps(MODEW);   // (textured instances only: the batch has a wrapped axis, fp.wrap())
     using St = ShadeStage<MODE, HS>;
     constexpr int RM = attr_unfiltered(MODE);   // the mode of the shading records (a bilinear batch: its nearest counterpart's)
     static_assert(St::REC == RecLen<RM>::REC, "the staged slots hold the records build_record<RM> writes");
@@ -273,6 +275,7 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
         for (int k0 = 0; k0 < PPT; k0 += TQ) {
             i64 ti[TQ];   // texel offset, or -1: nothing to fetch
             f64 fu[BIL ? TQ : 1], fv[BIL ? TQ : 1];   // (bilinear: the footprint's fractions)
+            int du[BIL && WRAP ? TQ : 1], dv[BIL && WRAP ? TQ : 1];   // (and under a wrap state the +1 neighbours' steps, in texels)
             int dj[MOD ? TQ : 1];                     // (modulated: the pixel's staged record)
 #pragma unroll
             for (int j = 0; j < TQ; ++j) {
@@ -307,9 +310,11 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                 if constexpr (BIL) {
                     f64 u, v;
                     record_uv<MODE>(rec + d * St::REC, px, py, u, v);
-                    ti[j] = tex_bilinear(tv, u, v, fu[j], fv[j]);
+                    if constexpr (WRAP) ti[j] = tex_bilinear_wrap(tv, fp.wrap(), u, v, fu[j], fv[j], du[j], dv[j]);
+                    else ti[j] = tex_bilinear(tv, u, v, fu[j], fv[j]);
                 } else {
-                    ti[j] = record_texel_of<MODE>(tv, rec + d * St::REC, px, py);
+                    if constexpr (WRAP) ti[j] = record_texel_of_wrap<MODE>(tv, fp.wrap(), rec + d * St::REC, px, py);
+                    else ti[j] = record_texel_of<MODE>(tv, rec + d * St::REC, px, py);
                 }
             }
             f64 c[TQ][3];
@@ -318,7 +323,8 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                 if (ti[j] < 0) continue;
                 if constexpr (BIL) {
                     TexQuad t;
-                    load_tex_quad(tv, ti[j], t);
+                    if constexpr (WRAP) load_tex_quad_wrap(tv, ti[j], du[j], dv[j], t);
+                    else load_tex_quad(tv, ti[j], t);
                     mix_tex_quad(t, fu[j], fv[j], c[j][0], c[j][1], c[j][2]);
                 } else {
                     const f64* q = tv.ptr + ti[j];
@@ -411,7 +417,8 @@ __device__ __forceinline__ void shade_tile(const FrameParams& fp, i64 x0, i64 y0
                 f64 r[St::REC];
                 build_record<RM>(fp, src[j], r);
                 f64 cr, cg, cb, ca;
-                record_colour<MODE>(tv, r, px, py, cr, cg, cb, ca);
+                if constexpr (WRAP) record_colour_wrap<MODE>(tv, fp.wrap(), r, px, py, cr, cg, cb, ca);
+                else record_colour<MODE>(tv, r, px, py, cr, cg, cb, ca);
                 apply_winner(fp, gp, cr, cg, cb, ca);
                 store_colour(fp, gp, px, py, cr, cg, cb, ca);
             }
@@ -516,11 +523,12 @@ __device__ __forceinline__ void capture_keys(const KeyCaptureTable* kc, int tile
 
 // MARK: a marking frame's instance (shade_tile MARK; the visible list, warm_enqueue).
 // KCAP: the key cache's capture frame (capture_keys at the two shade_tile calls).
-template <int ZMODE, bool COUNT, int MODE, bool FLAT, int NT, bool MARK = false, bool KCAP = false>   // ZMODE 0: no test, 1: LESS+write, 2: LESS no write
+template <int ZMODE, bool COUNT, int MODEW, bool FLAT, int NT, bool MARK = false, bool KCAP = false>   // ZMODE 0: no test, 1: LESS+write, 2: LESS no write
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) void k_vis(const FrameParams fp, const uint4* __restrict__ items,
                                              const u32* __restrict__ list,
                                              u64* __restrict__ kslot, u32* __restrict__ done,
                                              const u32* __restrict__ plan, const WarmCheck wc) {
+    constexpr int MODE = attr_base(MODEW);   // (the raster knows nothing of ATTR_WRAPS: only shade_tile samples)
     constexpr bool DEPTH = ZMODE != 0;
     constexpr int NWV = NT / 64;   // waves per workgroup
     // tile keys, rows padded to KS = 65 entries: lanes working on different
@@ -865,7 +873,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         if (!multi) {   // the whole list was in this slice: shade now
             if constexpr (KCAP) capture_keys<NT>(fp.kcap, tile, key);
             if (rlo < rcap)
-                shade_tile<ZMODE, MODE, NT, HS, MARK>(fp, x0, y0 + rlo, wlim, rcap - rlo, key + rlo * KS, lds, nU);
+                shade_tile<ZMODE, MODEW, NT, HS, MARK>(fp, x0, y0 + rlo, wlim, rcap - rlo, key + rlo * KS, lds, nU);
             continue;
         }
         // split tile (a dense tile's slice): the slice's keys go to its own
@@ -935,7 +943,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         __syncthreads();
         NR_PROBE_STAMP(3);
         if constexpr (KCAP) capture_keys<NT>(fp.kcap, tile, key);
-        shade_tile<ZMODE, MODE, NT, HS, MARK>(fp, x0, y0, wlim, hlim, key, lds, nU);
+        shade_tile<ZMODE, MODEW, NT, HS, MARK>(fp, x0, y0, wlim, hlim, key, lds, nU);
     }   // work items
 #if NR_PROBE
     if (tid == 0 && pr_item != ~0u) probe_item(pr_item, pr_d, pr_t0, __builtin_amdgcn_s_memrealtime(), NT);
@@ -963,9 +971,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
 // contiguous bytes), stores them to the LDS keys at stride KS and shades the
 // tile with shade_tile unchanged -- everything colour-side is read live from fp.
 // kplan: {cached tiles, items}.
-template <int ZMODE, int MODE, int NT>
+template <int ZMODE, int MODEW, int NT>
 __global__ __launch_bounds__(NT) void k_keys(const FrameParams fp, const uint4* __restrict__ items,
                                              const u64* __restrict__ kkeys, const u32* __restrict__ kplan) {
+    constexpr int MODE = attr_base(MODEW);
     constexpr int HS = NT > VWG ? HTS_WIDE : HTS;
     constexpr int PPT = TH * TW / NT;
     __shared__ __attribute__((aligned(16))) unsigned char lds[ShadeStage<MODE, HS>::BYTES];
@@ -1029,7 +1038,7 @@ __global__ __launch_bounds__(NT) void k_keys(const FrameParams fp, const uint4* 
         __syncthreads();
         NR_PROBE_STAMP(1);
         NR_PROBE_STAMP(2);
-        shade_tile<ZMODE, MODE, NT, HS>(fp, x0, y0, wlim, hlim, key, lds, nU);
+        shade_tile<ZMODE, MODEW, NT, HS>(fp, x0, y0, wlim, hlim, key, lds, nU);
     }
 #if NR_PROBE
     if (tid == 0 && pr_item != ~0u) probe_item(pr_item, pr_d, pr_t0, __builtin_amdgcn_s_memrealtime(), NT);
@@ -1073,7 +1082,7 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& 
     // cached batch runs k_keys at the workgroup size k_vis would take; the capture frame (one per generation) the
     // narrow capturing instance of its raster shape.
     bool narrow = false;
-    if constexpr (!C && Z != 2 && G != ATTR_TEX_PERSP_BIL && !attr_modulated(G)) {
+    if constexpr (!C && Z != 2 && attr_base(G) != ATTR_TEX_PERSP_BIL && !attr_modulated(attr_base(G))) {
         if (va.kkeys) {
             const bool w = wide || keys_wide_forced();
             hipExtLaunchKernelGGL(w ? k_keys<Z, G, 2 * VWG> : k_keys<Z, G, VWG>, dim3(grid), dim3(w ? 2 * VWG : VWG), 0, s,
@@ -1098,11 +1107,18 @@ int z_mode(const FrameParams& fp) { return fp.depthTest ? (fp.depthWrite ? 1 : 2
 
 void launch_vis_any(const FrameParams& fp, const TriScratch& sc, const BatchTotals& t, const VisArgs& va,
                     u32 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
-    const int zmode = z_mode(fp), mode = fp.src.mode;
+    // (a textured batch with a wrapped axis takes its mode's ATTR_WRAPS instance)
+    const int zmode = z_mode(fp), mode = fp.src.mode | (attr_textured(fp.src.mode) && fp.wrap().any() ? ATTR_WRAPS : 0);
 #define NR_VG(ZM, G) (fp.fragCounter ? launch_vis<ZM, true, G>(fp, sc, t, va, grid, s, start, stop) \
                                      : launch_vis<ZM, false, G>(fp, sc, t, va, grid, s, start, stop))
 #define NR_VZ(ZM)                                            \
-    (mode == ATTR_TEXC_BIL ? NR_VG(ZM, ATTR_TEXC_BIL)        \
+    (mode == (ATTR_TEXC_BIL | ATTR_WRAPS) ? NR_VG(ZM, ATTR_TEXC_BIL | ATTR_WRAPS)        \
+     : mode == (ATTR_TEXC | ATTR_WRAPS)    ? NR_VG(ZM, ATTR_TEXC | ATTR_WRAPS)           \
+     : mode == (ATTR_TEX_PERSP_BIL | ATTR_WRAPS) ? NR_VG(ZM, ATTR_TEX_PERSP_BIL | ATTR_WRAPS) \
+     : mode == (ATTR_TEX_BIL | ATTR_WRAPS) ? NR_VG(ZM, ATTR_TEX_BIL | ATTR_WRAPS)        \
+     : mode == (ATTR_TEX_PERSP | ATTR_WRAPS) ? NR_VG(ZM, ATTR_TEX_PERSP | ATTR_WRAPS)    \
+     : mode == (ATTR_TEX | ATTR_WRAPS)     ? NR_VG(ZM, ATTR_TEX | ATTR_WRAPS)            \
+     : mode == ATTR_TEXC_BIL ? NR_VG(ZM, ATTR_TEXC_BIL)        \
      : mode == ATTR_TEXC    ? NR_VG(ZM, ATTR_TEXC)           \
      : mode == ATTR_TEX_PERSP_BIL ? NR_VG(ZM, ATTR_TEX_PERSP_BIL) \
      : mode == ATTR_TEX_BIL ? NR_VG(ZM, ATTR_TEX_BIL)        \

@@ -92,6 +92,27 @@ inline TexView tex_view(const f64* ptr, i64 w, i64 h, bool alpha) {
     return TexView{ptr, (f64)(w - 2), (f64)(h - 2), (int)w * ipp, ipp};
 }
 
+// The wrap addressing of a textured batch (SetTriangleTextureWrap), per axis: mode 0 clamp (tex_index /
+// tex_bilinear on that axis), 1 repeat, 2 mirrored repeat (wrap_fold).  Run-time data of the batch, not an AttrMode:
+// one int per axis, mode | side << 2 (a side is below 2^29), formed on the host.  They arrive as scalar kernel
+// arguments, so an axis's mode is a wave-uniform scalar branch, and everything the fold needs of them -- the side,
+// the period and the period as an f64 (wrap_period) -- is formed by scalar integer operations (an int converted to
+// f64 in the kernel is a loop-invariant vector value: see TexView).  Only a batch with a wrapped axis (any()) runs
+// the instances that read them (ATTR_WRAPS, below); a (0, 0) batch runs the instances that know no wrap state.
+struct TexWrap {
+    int u, v;   // columns (side w), rows (side h)
+    __host__ __device__ bool any() const { return ((u | v) & 3) != 0; }
+};
+inline TexWrap tex_wrap(i64 w, i64 h, int mu, int mv) { return TexWrap{mu | (int)(w << 2), mv | (int)(h << 2)}; }
+// The rasters' kernels are instantiated per AttrMode.  A textured mode has two instances: the one for batches whose
+// state is (0, 0), whose samplers and code are what they were before there was a wrap state, and one for batches
+// with a wrapped axis, named by this flag beside the AttrMode in the kernel's mode parameter (a flag in that int,
+// not a further template parameter: the symbols of the existing instances stay what they were).  It is no batch
+// mode: TriSrc::mode never carries it; the host adds it at the launch when TexWrap::any().
+constexpr int ATTR_WRAPS = 8;
+__host__ __device__ constexpr int attr_base(int modew) { return modew & (ATTR_WRAPS - 1); }
+__host__ __device__ constexpr bool attr_wraps(int modew) { return (modew & ATTR_WRAPS) != 0; }
+
 struct BinParams {
     TriSrc src;
     f64 m[6];
@@ -399,7 +420,10 @@ struct KeyCaptureTable {
     u32 slot[2];   // (one per tile: the table is allocated to the frame's tiles)
 };
 
-// State snapshot of one draw call (passed by value to the kernels).
+// State snapshot of one draw call (passed by value to the kernels).  The rasters' kernels take it in front of their
+// other arguments, so its size, 304 bytes, is part of every instance's kernarg layout: a new field must fit into
+// padding (or replace a field) and leave sizeof and every existing offset as they are -- the static_assert below
+// the struct guards the size.  Every copy of a snapshot is a struct copy.
 struct FrameParams {
     TriSrc src;
     f64 m[6];
@@ -413,6 +437,7 @@ struct FrameParams {
     u64 mask;
     int depthTest, depthWrite;
     int pendColor;
+    int wrapU;    // textured batches: the wrap state of the columns (TexWrap::u; 0: clamp) -- in what was padding
     f64 pendColorValue;
     int pendDepth;
     u32 pendDepthValue;
@@ -420,6 +445,7 @@ struct FrameParams {
     iu8* frameU8;                      // non-null: resolve also writes the frame output: the u8
                                        // image (cpp:52-57), or with frameYUV its YUV420P planes
     int frameYUV;
+    int wrapV;        // ... and of the rows (TexWrap::v), likewise
     u32* tileStamp;   // non-null: k_vis leaves an empty tile's pending clears pending (stamps it tileEpoch,
     u32 tileEpoch;    // RenderContext::tileStamp) and writes only its frame output
     u64* tstamp;      // non-null (kernel timing): {~first start, last end} of the raster on the device's
@@ -433,7 +459,11 @@ struct FrameParams {
     // so it lives here and not in TriSrc, and last: the binning's BinParams and every offset of the snapshot
     // the existing instances read stay as they were.
     const f64* q;
+    __host__ __device__ TexWrap wrap() const { return TexWrap{wrapU, wrapV}; }
 };
+// (the wrap state sits in the snapshot's padding: the kernels take the snapshot by value in front of their other
+// arguments, so a snapshot of another size would move those arguments for every instance)
+static_assert(sizeof(FrameParams) == 304, "the snapshot's size is part of every raster kernel's argument layout");
 
 // Texel of a fragment's interpolated (u, v), as an offset in doubles: the
 // texel the reference sampler picks (cpp:555-573: x < 0 -> 0, x >= w-1 ->
@@ -477,6 +507,78 @@ __device__ __forceinline__ i64 tex_bilinear(const TexView& tv, f64 x, f64 y, f64
 // build has no FMA contraction).  gu = 1 - fu, gv = 1 - fv.
 __device__ __forceinline__ f64 bilinear_mix(f64 c0, f64 c1, f64 c2, f64 c3, f64 fu, f64 fv, f64 gu, f64 gv) {
     return c0 * gu * gv + c1 * fu * gv + c2 * gu * fv + c3 * fu * fv;
+}
+
+// (f64)p of an integer 2 <= p < 2^30 by integer operations -- exponent from the leading bit, the rest shifted into
+// the mantissa, exact -- so that the period of a batch's fold, uniform over the batch, is formed in scalar registers.
+__device__ __forceinline__ f64 wrap_period(int p) {
+    const int e = 31 - __builtin_clz((u32)p);
+    const u64 bits = ((u64)(1023 + e) << 52) | (((u64)(u32)p << (52 - e)) & 0x000FFFFFFFFFFFFFull);
+    return __longlong_as_double((long long)bits);
+}
+// One axis of a footprint under the batch's wrap state (DESIGN.md §3 "Wrap addressing"; the rule for columns with n =
+// w, x = u and for rows with n = h, x = v): the texel index c0, the signed step d to the bilinear +1 neighbour (c1 -
+// c0) and the fraction f.  Mode 0 is tex_index's / tex_bilinear's axis: (i, +1, f).  Otherwise, with P = (f64)n
+// (repeat) or (f64)(2n) (mirror), in f64, every operation rounded in the order written (no contraction in this
+// build), the divide IEEE:
+//   k = floor(x / P);  t = x - k * P;  !(t >= 0) -> 0 (NaN, inf - inf, a t rounding left negative);  t >= P -> 0 (a t
+//   rounding left at P, the garbage of a huge |x|);  i0 = (int)t in 0 .. P-1, f = t - i0 (exact, in [0, 1));  i1 = i0 +
+//   1, P -> 0;  c(j) = j (repeat), j < n ? j : 2n - 1 - j (mirror).
+// Every input gives indices in [0, n-1].  The step is +1, 0 (a mirror seam: the same texel twice), -1 (the mirror's
+// descending half) or -(n-1) (the repeat seam): a footprint is its base texel and two signed strides, not four offsets.
+// (ax: one axis of the state, mode | n << 2; last: the clamp axis's bound, TexView::xlast / ylast.  On a clamped
+// axis a -0.0 coordinate counts as 0 and its fraction is a zero of either sign, as in tex_bilinear: fmax(-0.0, 0.0)
+// may return either zero; tests/test_wrap_ref.py leaves that one value out of the mode-0 comparison of the forms.)
+__device__ __forceinline__ void wrap_fold(f64 x, int ax, f64 last, int& c0, int& d, f64& f) {
+    const int mode = ax & 3, n = ax >> 2;
+    if (mode == 0) {
+        const f64 xc = fmax(x, 0.0);
+        c0 = (int)fmin(xc, last);
+        const f64 dd = xc - (f64)c0;
+        f = dd < 1.0 ? dd : 0.0;
+        d = 1;
+        return;
+    }
+    const int per = mode == 2 ? 2 * n : n;
+    const f64 P = wrap_period(per);
+    const f64 k = floor(x / P);
+    f64 t = x - k * P;
+    if (!(t >= 0.0)) t = 0.0;
+    if (t >= P) t = 0.0;
+    const int i0 = (int)t;
+    f = t - (f64)i0;
+    int i1 = i0 + 1;
+    if (i1 == per) i1 = 0;
+    if (mode == 2) {
+        c0 = i0 < n ? i0 : per - 1 - i0;
+        d = (i1 < n ? i1 : per - 1 - i1) - c0;
+    } else {
+        c0 = i0;
+        d = i1 - i0;
+    }
+}
+// tex_index under a wrap state: the row term of the offset is 64-bit, as there.  (The step and the fraction
+// wrap_fold also returns are not used here: nothing reads them, and the compiler drops their computation.)
+__device__ __forceinline__ i64 tex_index_wrap(const TexView& tv, const TexWrap& tw, f64 x, f64 y) {
+    int xi, yi, d;
+    f64 f;
+    wrap_fold(x, tw.u, tv.xlast, xi, d, f);
+    wrap_fold(y, tw.v, tv.ylast, yi, d, f);
+    return (i64)yi * tv.pitch + xi * tv.ipp;
+}
+// tex_bilinear under a wrap state: the offset of texel (r(j0), c(i0)) and the steps, in texels, to the +1 column and
+// the +1 row (the clamp path's are +1 and +1: tv.ipp and tv.pitch doubles).  A caller scales them itself (tex_quad_strides): kept
+// in texels they are two ints across a gather; the row stride in doubles can exceed 32 bits for a tall texture.
+__device__ __forceinline__ i64 tex_bilinear_wrap(const TexView& tv, const TexWrap& tw, f64 x, f64 y, f64& fu, f64& fv,
+                                                 int& du, int& dv) {
+    int xi, yi;
+    wrap_fold(x, tw.u, tv.xlast, xi, du, fu);
+    wrap_fold(y, tw.v, tv.ylast, yi, dv, fv);
+    return (i64)yi * tv.pitch + xi * tv.ipp;
+}
+__device__ __forceinline__ void tex_quad_strides(const TexView& tv, int du, int dv, i64& dcol, i64& drow) {
+    dcol = du * tv.ipp;
+    drow = (i64)dv * tv.pitch;
 }
 
 // Kernel timing of the rasters by the device's constant 100 MHz clock
@@ -616,6 +718,7 @@ struct Batch {
     const f64* q;                                 // perspective textured batches: the corners' 1/w (else null)
     bool modulated = false;                       // textured: src.attr is n*18, uv and colour per corner (q is set)
     TexView tex = tex_view(nullptr, 2, 2, false); // textured modes: what draw_textured resolved
+    TexWrap wrap = TexWrap{0, 0};                 // textured modes: the context's wrap state when the draw was issued
     Opacity opq;
     TriangleBuffer* tb;   // non-null: the batch is that (immutable) buffer -- its binning may overlap the previous
                           // raster, and a repeat draw is sized from its known totals

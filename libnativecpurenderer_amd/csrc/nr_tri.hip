@@ -62,6 +62,8 @@ FrameParams frame_params(RenderContext* ctx, const Batch& b) {
     fp.tex = b.tex;
     fp.winMask = nullptr;
     fp.q = b.q;
+    fp.wrapU = b.wrap.u;
+    fp.wrapV = b.wrap.v;
     if (ctx->countFragments) {
         if (!sc.d_frag) NR_CHECK(hipMalloc(&sc.d_frag, sizeof(u64)));
         NR_CHECK(hipMemsetAsync(sc.d_frag, 0, sizeof(u64), ctx->stream));
@@ -245,11 +247,13 @@ bool check_texture(RenderContext* ctx, const Texture* tex, const char* what) {
 // b.q non-null: a perspective textured batch; b.modulated: one whose attributes also carry the corner colours
 // (src.attr n*18, b.q required).  The context's filter
 // (SetTriangleTextureFilter) is read here, when the draw is issued: the mode is
-// part of the batch's snapshot, so a pending batch or its re-run keeps it.
+// part of the batch's snapshot, so a pending batch or its re-run keeps it.  The
+// wrap state (SetTriangleTextureWrap) likewise: read here, carried in the batch.
 void draw_textured(RenderContext* ctx, Texture* tex, Batch& b) {
     settle(ctx);   // (a re-run of the pending batch comes before a snapshot of the target)
     TexSrc ts = nr_tex_source(ctx, tex);
     b.tex = tex_view(ts.ptr, tex->width, tex->height, tex->enableAlpha);
+    b.wrap = tex_wrap(tex->width, tex->height, ctx->texWrapU, ctx->texWrapV);
     if (b.modulated) b.src.mode = ctx->texFilter ? ATTR_TEXC_BIL : ATTR_TEXC;
     else if (ctx->texFilter) b.src.mode = b.q ? ATTR_TEX_PERSP_BIL : ATTR_TEX_BIL;
     else b.src.mode = b.q ? ATTR_TEX_PERSP : ATTR_TEX;
@@ -375,6 +379,26 @@ bool SetTriangleTextureFilter(RenderContext* ctx, i64 mode) {
     return true;
 }
 i64 GetTriangleTextureFilter(RenderContext* ctx) { return ctx->texFilter; }
+
+// New: the wrap addressing of this context's textured triangle draws, per axis
+// (everything SetTriangleTextureFilter covers, and the modulated draws): 0 clamp
+// (the default), 1 repeat, 2 mirrored repeat.  A mode outside
+// 0..2 on either axis latches an error, leaves both axes unchanged and returns
+// false.  The filter's rules: per context; not part of the save / restore
+// stack, not recorded; read when a draw is issued (draw_textured).
+bool SetTriangleTextureWrap(RenderContext* ctx, i64 modeU, i64 modeV) {
+    if (modeU < 0 || modeU > 2 || modeV < 0 || modeV > 2) {
+        nr_set_error_msg("SetTriangleTextureWrap: modes must be 0 (clamp), 1 (repeat) or 2 (mirror)");
+        return false;
+    }
+    ctx->texWrapU = (int)modeU;
+    ctx->texWrapV = (int)modeV;
+    return true;
+}
+void GetTriangleTextureWrap(RenderContext* ctx, i64* modeU, i64* modeV) {
+    if (modeU) *modeU = ctx->texWrapU;
+    if (modeV) *modeV = ctx->texWrapV;
+}
 
 // New: clear the u32 depth buffer (deferred; consumed by the raster).
 void ClearDepth(RenderContext* ctx, u32 value) {

@@ -145,10 +145,14 @@ __device__ __forceinline__ u64 window_bits(int xs, int xe) {
 // filter with the corner colour interpolated beside U, V, Q; the texel is
 // multiplied by it, channel by channel, before ApplyPixel.
 // 4 waves per SIMD (6: 80 VGPRs, 85 spilled -- C5 raster 740 -> 1355 us)
-template <int MODE, bool DEPTH, bool COUNT, bool RGBA, bool BINNED>
+// MODEW: the AttrMode, with ATTR_WRAPS (nr_tri.h) for the instance of a textured batch that has a wrapped axis
+// (fp.wrap(), SetTriangleTextureWrap): it differs in the blend loop's sampling only.
+template <int MODEW, bool DEPTH, bool COUNT, bool RGBA, bool BINNED>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_tile_raster(const FrameParams fp, const u32* __restrict__ list,
                                                     const u32* __restrict__ tstart, const u32* __restrict__ tend,
                                                     const f64* __restrict__ rec, const u32* __restrict__ plan) {
+    constexpr int MODE = attr_base(MODEW);
+    constexpr bool WRAP = attr_wraps(MODEW);
     constexpr bool GOURAUD = MODE == ATTR_GOURAUD, TEX = attr_textured(MODE), PERSP = attr_persp(MODE);
     constexpr bool BIL = attr_bilinear(MODE), MOD = attr_modulated(MODE);
     constexpr int NS = MOD ? S_NSLOT_MOD : S_NSLOT;
@@ -494,10 +498,21 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                     f64 R, G, B, A;
                     if (BIL) {
                         f64 fu, fv;
-                        const f64* t0 = fp.tex.ptr + tex_bilinear(fp.tex, u, v, fu, fv);
-                        const f64* t1 = t0 + fp.tex.ipp;
-                        const f64* t2 = t0 + fp.tex.pitch;
-                        const f64* t3 = t2 + fp.tex.ipp;
+                        const f64 *t0, *t1, *t2, *t3;
+                        if constexpr (WRAP) {   // (the footprint's two signed steps in place of + ipp, + pitch)
+                            int du, dv;
+                            i64 dcol, drow;
+                            t0 = fp.tex.ptr + tex_bilinear_wrap(fp.tex, fp.wrap(), u, v, fu, fv, du, dv);
+                            tex_quad_strides(fp.tex, du, dv, dcol, drow);
+                            t1 = t0 + dcol;
+                            t2 = t0 + drow;
+                            t3 = t2 + dcol;
+                        } else {
+                            t0 = fp.tex.ptr + tex_bilinear(fp.tex, u, v, fu, fv);
+                            t1 = t0 + fp.tex.ipp;
+                            t2 = t0 + fp.tex.pitch;
+                            t3 = t2 + fp.tex.ipp;
+                        }
                         const f64 gu = 1 - fu, gv = 1 - fv;
                         R = bilinear_mix(t0[0], t1[0], t2[0], t3[0], fu, fv, gu, gv);
                         G = bilinear_mix(t0[1], t1[1], t2[1], t3[1], fu, fv, gu, gv);
@@ -505,7 +520,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                         // (a texture without alpha: the literal 1, not a filtered sum of ones)
                         A = fp.tex.ipp == 4 ? bilinear_mix(t0[3], t1[3], t2[3], t3[3], fu, fv, gu, gv) : 1.0;
                     } else {
-                        const f64* tq = fp.tex.ptr + tex_index(fp.tex, u, v);
+                        const f64* tq;
+                        if constexpr (WRAP) tq = fp.tex.ptr + tex_index_wrap(fp.tex, fp.wrap(), u, v);
+                        else tq = fp.tex.ptr + tex_index(fp.tex, u, v);
                         R = tq[0]; G = tq[1]; B = tq[2];
                         A = fp.tex.ipp == 4 ? tq[3] : 1.0;
                     }
@@ -637,6 +654,22 @@ template <bool C, bool B>
 void launch_raster_c(const FrameParams& fp, const u32* list, const u32* ts, const u32* te, int ntiles,
                      hipStream_t s, const f64* rec, const u32* plan = nullptr, hipEvent_t start = nullptr,
                      hipEvent_t stop = nullptr) {
+    if (attr_textured(fp.src.mode) && fp.wrap().any()) {   // a wrapped axis: the mode's ATTR_WRAPS instance
+        const bool d = fp.depthTest != 0;
+#define NR_OW(G)                                                                                          \
+    (d ? launch_raster<(G) | ATTR_WRAPS, true, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop) \
+       : launch_raster<(G) | ATTR_WRAPS, false, C, B>(fp, list, ts, te, ntiles, s, rec, plan, start, stop))
+        switch (fp.src.mode) {
+            case ATTR_TEX: NR_OW(ATTR_TEX); break;
+            case ATTR_TEX_PERSP: NR_OW(ATTR_TEX_PERSP); break;
+            case ATTR_TEX_BIL: NR_OW(ATTR_TEX_BIL); break;
+            case ATTR_TEX_PERSP_BIL: NR_OW(ATTR_TEX_PERSP_BIL); break;
+            case ATTR_TEXC: NR_OW(ATTR_TEXC); break;
+            default: NR_OW(ATTR_TEXC_BIL); break;
+        }
+#undef NR_OW
+        return;
+    }
     const bool g = fp.src.mode == ATTR_GOURAUD, t = fp.src.mode == ATTR_TEX, d = fp.depthTest != 0;
     const bool p = fp.src.mode == ATTR_TEX_PERSP;
     const bool tb = fp.src.mode == ATTR_TEX_BIL, pb = fp.src.mode == ATTR_TEX_PERSP_BIL;

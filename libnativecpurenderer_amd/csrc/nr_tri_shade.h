@@ -225,6 +225,14 @@ __device__ __forceinline__ i64 record_texel_of(const TexView& tv, const f64* r, 
     record_uv<MODE>(r, px, py, u, v);
     return tex_index(tv, u, v);
 }
+// ... under a wrap state (the ATTR_WRAPS instances): tex_index_wrap.
+template <int MODE>
+__device__ __forceinline__ i64 record_texel_of_wrap(const TexView& tv, const TexWrap& tw, const f64* r, i64 px,
+                                                    i64 py) {
+    f64 u, v;
+    record_uv<MODE>(r, px, py, u, v);
+    return tex_index_wrap(tv, tw, u, v);
+}
 
 // The four texels of a bilinear footprint at offset ti (tex_bilinear), rgb each: texels (iy, ix) and (iy, ix + 1)
 // are adjacent, the second row tv.pitch further.  Ordinary cached loads, like the nearest texel's.
@@ -238,6 +246,19 @@ __device__ __forceinline__ void load_tex_quad(const TexView& tv, i64 ti, TexQuad
     for (int k = 0; k < 3; ++k) {
         t.c[0][k] = q0[k]; t.c[1][k] = q0[tv.ipp + k];
         t.c[2][k] = q1[k]; t.c[3][k] = q1[tv.ipp + k];
+    }
+}
+// ... of a wrapped footprint (tex_bilinear_wrap): the +1 column du texels and the +1 row dv texels from the base,
+// either way.
+__device__ __forceinline__ void load_tex_quad_wrap(const TexView& tv, i64 ti, int du, int dv, TexQuad& t) {
+    i64 dcol, drow;
+    tex_quad_strides(tv, du, dv, dcol, drow);
+    const f64* q0 = tv.ptr + ti;
+    const f64* q1 = q0 + drow;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        t.c[0][k] = q0[k]; t.c[1][k] = q0[dcol + k];
+        t.c[2][k] = q1[k]; t.c[3][k] = q1[dcol + k];
     }
 }
 __device__ __forceinline__ void mix_tex_quad(const TexQuad& t, f64 fu, f64 fv, f64& cr, f64& cg, f64& cb) {
@@ -292,6 +313,27 @@ __device__ __forceinline__ void record_colour(const TexView& tv, const f64* r, i
     } else {
         cr = r[0]; cg = r[1]; cb = r[2]; ca = 1.0;
     }
+}
+// ... from a textured record under a wrap state (the ATTR_WRAPS instances): the same with tex_index_wrap /
+// tex_bilinear_wrap, the four texels of a footprint by its two signed steps.
+template <int MODE>
+__device__ __forceinline__ void record_colour_wrap(const TexView& tv, const TexWrap& tw, const f64* r, i64 px, i64 py,
+                                                   f64& cr, f64& cg, f64& cb, f64& ca) {
+    static_assert(attr_textured(MODE), "textured modes only");
+    if constexpr (attr_bilinear(MODE)) {
+        f64 u, v, fu, fv;
+        int du, dv;
+        record_uv<MODE>(r, px, py, u, v);
+        TexQuad t;
+        const i64 ti = tex_bilinear_wrap(tv, tw, u, v, fu, fv, du, dv);
+        load_tex_quad_wrap(tv, ti, du, dv, t);
+        mix_tex_quad(t, fu, fv, cr, cg, cb);
+    } else {
+        const f64* q = tv.ptr + record_texel_of_wrap<MODE>(tv, tw, r, px, py);
+        cr = q[0]; cg = q[1]; cb = q[2];
+    }
+    ca = 1.0;
+    if constexpr (attr_modulated(MODE)) record_modulate(r, px, py, cr, cg, cb, ca);
 }
 
 // Depth (quantised) of one covered fragment at pixel x = X of a row dy below

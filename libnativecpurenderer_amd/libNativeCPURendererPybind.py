@@ -449,6 +449,24 @@ class RenderContext:
     def get_triangle_texture_filter(self) -> int:
         return lib.GetTriangleTextureFilter(self._ptr)
 
+    # wrap addressing of the textured triangle draws: the filter's rules
+    def set_triangle_texture_wrap(self, u: int, v=None):
+        """Per axis 0 clamp (the default), 1 repeat, 2 mirrored repeat; v=None
+        means v = u.  Covers what set_triangle_texture_filter covers and the
+        modulated, instanced and lit textured draws.  A mode outside 0..2 on
+        either axis raises (the error stays latched) and leaves both axes
+        unchanged."""
+        if v is None:
+            v = u
+        if not lib.SetTriangleTextureWrap(self._ptr, int(u), int(v)):
+            raise RuntimeError("SetTriangleTextureWrap failed: " + _lib.last_error())
+
+    def get_triangle_texture_wrap(self):
+        """(u, v)"""
+        u, v = ctypes.c_long(0), ctypes.c_long(0)
+        lib.GetTriangleTextureWrap(self._ptr, ctypes.byref(u), ctypes.byref(v))
+        return u.value, v.value
+
     # perspective-correct texture mapping of textured mesh draws: per context,
     # not saved / restored, not recorded; colour meshes ignore it
     def set_mesh_perspective(self, on: bool):
