@@ -569,11 +569,18 @@ __device__ __forceinline__ void nr_apply_pixel(f64* p, int ipp, f64 r, f64 g, f6
 
 // cpp:555-573 nearest-texel sampler (clamp to [0,w-2]x[0,h-2]); alpha of an RGB
 // texture is uninitialised in the reference (Appendix A.2) and defined as 1.
+// Two inputs on which the reference is undefined are defined here (DESIGN.md §2,
+// "Sampler deviations"): a NaN coordinate, which passes the
+// reference's `< 0` clamp into an undefined (i64) cast, counts as 0 (the
+// negated comparison below differs from `x < 0` for NaN only); and a texel
+// index below 0, which only a texture 1 texel wide or high gives, reads
+// texel 0.  After the clamps every coordinate lies in [-1, tw-2] x
+// [-1, th-2], so both casts are defined.
 __device__ __forceinline__ void nr_sample(const f64* tb, i64 tw, i64 th, bool talpha, f64 x, f64 y,
                                           f64& r, f64& g, f64& b, f64& a) {
-    if (x < 0) x = 0;
+    if (!(x >= 0)) x = 0;
     if (x >= (f64)(tw - 1)) x = (f64)(tw - 2);
-    if (y < 0) y = 0;
+    if (!(y >= 0)) y = 0;
     if (y >= (f64)(th - 1)) y = (f64)(th - 2);
     i64 ipp = talpha ? 4 : 3;
     i64 index = (i64)y * tw * ipp + (i64)x * ipp;

@@ -156,7 +156,7 @@ class RenderContext:
         lib.SaveContextState(self._ptr)
 
     def restore_state(self):
-        lib.RestoreContextState(self._ptr)
+        return lib.RestoreContextState(self._ptr)
 
     def draw_line(self, x0: float, y0: float, x1: float, y1: float, width: float,
                   r: float, g: float, b: float, a: float):
@@ -176,7 +176,7 @@ class RenderContext:
         return tuple(out)
 
     def apply_pixel(self, x: int, y: int, r: float, g: float, b: float, a: float):
-        lib.ApplyPixel(self._ptr, x, y, r, g, b, a)
+        return lib.ApplyPixel(self._ptr, x, y, r, g, b, a)
 
     def draw_circle(self, x: float, y: float, radius: float, r: float, g: float, b: float, a: float):
         lib.DrawCircle(self._ptr, x, y, radius, r, g, b, a)
@@ -191,7 +191,7 @@ class RenderContext:
         lib.ApplyColorTransform(self._ptr, r, g, b, a)
 
     def set_pixel(self, x: int, y: int, r: float, g: float, b: float, a: float):
-        lib.SetPixel(self._ptr, x, y, r, g, b, a)
+        return lib.SetPixel(self._ptr, x, y, r, g, b, a)
 
     def set_color(self, r: float, g: float, b: float, a: float):
         lib.SetColor(self._ptr, r, g, b, a)

@@ -282,14 +282,19 @@ static bool IsNoTransform(const f64 m[6]) {
 }
 
 /* cpp:555-573 — nearest texel; clamp to [0, w-2] x [0, h-2] (Appendix A.3).
- * RGB textures leave alpha uninitialised in the reference (A.2); defined 1. */
+ * RGB textures leave alpha uninitialised in the reference (A.2); defined 1.
+ * Defined by this project where the reference is undefined (DESIGN.md §2,
+ * "Sampler deviations"): a NaN coordinate counts as 0 (the
+ * reference casts it to i64), and a texel index below 0 (textures 1 texel
+ * wide or high, cpp:560-563 clamp to -1) reads texel 0. */
 static inline void sample(const Texture *t, f64 x, f64 y, f64 *r, f64 *g, f64 *b, f64 *a) {
-    if (x < 0) x = 0;
+    if (!(x >= 0)) x = 0;
     if (x >= t->width - 1) x = t->width - 2;
-    if (y < 0) y = 0;
+    if (!(y >= 0)) y = 0;
     if (y >= t->height - 1) y = t->height - 2;
     i64 ipp = t->enableAlpha ? 4 : 3;
     i64 index = (i64)y * t->width * ipp + (i64)x * ipp;
+    if (index < 0) index = 0;
     *r = t->buffer[index + 0];
     *g = t->buffer[index + 1];
     *b = t->buffer[index + 2];

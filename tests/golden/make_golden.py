@@ -12,6 +12,8 @@ build container; /root/reference does not exist on the GPU box).
 2. scenes.npz — oracle outputs of every scene in tests/scenes.py, so later
    oracle edits are caught (and so the GPU tests have a fixed target besides
    the live oracle).
+2b. prim_fuzz.sha256 — oracle digests of every output of every case of
+   tests/prim_fuzz.py (the primitive edge fuzz), for the same reason.
 3. image_png_rgba.npy — the reference's test asset test_files/image.png
    (Pybind.py:701) decoded to a 128x128x4 u8 array (data, used by config C1).
 
@@ -96,6 +98,16 @@ def ref_binding_scenes():
     }
 
 
+def write_prim_fuzz_digests(of):
+    import prim_fuzz
+    lines = []
+    for case in prim_fuzz.all_cases():
+        lines += prim_fuzz.golden_lines(case, prim_fuzz.run(case, of))
+    with open(os.path.join(HERE, "prim_fuzz.sha256"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("prim_fuzz", len(lines), "digests")
+
+
 def main():
     out = {}
     # 1. reference binding -> oracle
@@ -122,6 +134,9 @@ def main():
     with open(os.path.join(HERE, "scenes.sha256"), "w") as f:
         f.write("\n".join(digests) + "\n")
     print("scenes", len(out), "arrays")
+
+    # 2b. oracle digests of every case of the primitive edge fuzz (tests/prim_fuzz.py)
+    write_prim_fuzz_digests(of)
 
     # 3. the reference's test image as data
     if os.path.exists(REF_IMG):
