@@ -1,8 +1,30 @@
 // nr_mesh.h — what the mesh front end (nr_mesh.hip) and the skin pass
-// (nr_skin.hip) share: the Mesh handle and the pinned hand-off buffers of a
-// host call's small per-draw arrays.
+// (nr_skin.hip) share: the Mesh handle, the pinned hand-off buffers of a
+// host call's small per-draw arrays, the timed launch of a pass and the
+// error latch of an entry point.
 #pragma once
 #include "nr_tri.h"
+
+#include <string>
+
+// Latches "<what>: <why>" and returns false.
+inline bool fail(const char* what, const char* why) {
+    nr_set_error_msg((std::string(what) + ": " + why).c_str());
+    return false;
+}
+
+inline unsigned blocks_for(i64 threads) { return (unsigned)((threads + 255) / 256); }
+
+// One pass of a mesh call: `kernel` over `threads` threads in blocks of 256 on the context's stream, reported
+// under the timing id `kid`.
+template <class K, class... A>
+void mesh_launch(RenderContext* ctx, int kid, K kernel, i64 threads, A... args) {
+    hipEvent_t a, b;
+    nr_timing_begin(ctx, kid, &a, &b);
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(threads)), dim3(256), 0, ctx->stream, args...);
+    NR_CHECK(hipGetLastError());
+    nr_timing_end(ctx, kid, a, b);
+}
 
 struct Mesh {
     i64 nv = 0, n = 0;

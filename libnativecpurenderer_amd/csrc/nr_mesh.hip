@@ -55,7 +55,14 @@
 // on the colours and gathers the corner words from the mesh's uv and the colour
 // table; the clip stage emits three words per corner; every draw has a q (1.0
 // without the perspective state).
+//
+// The host half, at the end of the file: every entry point describes its draw once (MeshDraw: the mesh, one matrix
+// by value or K instances, the light input, where q comes from) and build_soup turns the description into a soup
+// through one of two builders, soup_unclipped and soup_clipped.  Single and instanced draws differ only in the
+// kernels chosen and in their counts (K*nv, K*n).  Every staging layout is carved by nr_mesh_stage.h, every timed
+// pass goes through mesh_launch (nr_mesh.h), and the entry points end in submit (draws) or copy_soup (Assemble*).
 #include "nr_mesh.h"
+#include "nr_mesh_stage.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -713,23 +720,24 @@ __global__ __launch_bounds__(256) void k_mesh_unit_q(f64* __restrict__ q, i64 co
     if (c < count) q[c] = 1.0;
 }
 
-unsigned blocks_for(i64 threads) { return (unsigned)((threads + 255) / 256); }
-
-void unit_q(RenderContext* ctx, f64* q, i64 count) {
+// ---- host side --------------------------------------------------------------------------------------------------
+void unit_q(RenderContext* ctx, f64* q, i64 count) {   // (untimed)
     hipLaunchKernelGGL(k_mesh_unit_q, dim3(blocks_for(count)), dim3(256), 0, ctx->stream, q, count);
     NR_CHECK(hipGetLastError());
 }
 
-bool fail(const char* what, const char* why) {
-    nr_set_error_msg((std::string(what) + ": " + why).c_str());
-    return false;
+// The mesh's device arrays, then the mesh.
+void free_mesh(Mesh* m) {
+    for (void* p : {(void*)m->pos, (void*)m->idx, (void*)m->attr, (void*)m->rgba, (void*)m->uv, (void*)m->normal})
+        if (p) NR_CHECK(hipFree(p));
+    delete m;
 }
 
 // uv: texel coordinates nv*2 (a textured mesh) or null (rgba nv*4, flat or Gouraud); both uv and rgba: a textured
 // colour mesh (ATTR_TEXC), which keeps its per-vertex uv and rgba on the device beside the expansion
 // normal: nv*3, a lit colour mesh (the per-vertex colours stay on the device beside it), or null
 Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* idx, const f64* rgba, bool gouraud,
-                  const f64* uv, const f64* normal = nullptr) {
+                  const f64* uv, const f64* normal) {
     const f64* vattr = uv ? uv : rgba;   // (both: the interleaved array below)
     const char* why = nullptr;
     if (nv < 0 || n < 0) why = "negative count";
@@ -784,13 +792,7 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
         (void)hipGetLastError();
         fail(what, "hipMalloc failed");
         if (dv) NR_CHECK(hipFree(dv));
-        if (m->pos) NR_CHECK(hipFree(m->pos));
-        if (m->idx) NR_CHECK(hipFree(m->idx));
-        if (m->attr) NR_CHECK(hipFree(m->attr));
-        if (m->normal) NR_CHECK(hipFree(m->normal));
-        if (m->uv) NR_CHECK(hipFree(m->uv));
-        if (m->rgba) NR_CHECK(hipFree(m->rgba));
-        delete m;
+        free_mesh(m);
         return nullptr;
     }
     NR_CHECK(hipMemcpyAsync(m->pos, pos, (size_t)nv * 3 * sizeof(f64), hipMemcpyHostToDevice, s));
@@ -804,6 +806,7 @@ Mesh* create_mesh(const char* what, i64 nv, const f64* pos, i64 n, const u32* id
         }
         const int perTri = m->mode == nrtri::ATTR_FLAT ? 1 : 3;
         const i64 nout = n * perTri;
+        // (on the device's stream, with no context: a plain launch)
         hipLaunchKernelGGL(k_mesh_attr, dim3(blocks_for(nout)), dim3(256), 0, s, m->idx, nout, perTri, w2,
                            reinterpret_cast<const double2*>(dv), reinterpret_cast<double2*>(m->attr));
         NR_CHECK(hipGetLastError());
@@ -822,39 +825,6 @@ Mat4 mat4_of(const f64* matrix) {
     return M;
 }
 
-// The vertex stage and the assembly of `m` under `matrix` into ctx's mesh
-// staging, on the context's stream (m->n > 0): *out is the soup with the mesh's
-// own attributes.  False: the staging could not be grown (error latched).
-// persp: the q-writing instances (out->q, else null).
-bool assemble(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out, bool persp) {
-    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
-    TriScratch& sc = ctx->tri;
-    const size_t nv = (size_t)m->nv, n = (size_t)m->n;
-    const size_t vzn = (nv + 1) & ~(size_t)1;   // keeps the soup's xy 16-byte aligned
-    if (!sc.mstage.ensure(nv * 2 + vzn + n * 9 + (persp ? vzn + n * 3 : 0))) return false;
-    f64* vxy = sc.mstage;
-    f64* vz = vxy + nv * 2;
-    f64* vq = persp ? vz + vzn : nullptr;   // (padded like vz: the soup's xy stays 16-byte aligned)
-    f64* xy = vz + vzn + (persp ? vzn : 0);
-    f64* z = xy + n * 6;
-    f64* q = persp ? z + n * 3 : nullptr;
-    const auto vertex = persp ? k_mesh_vertex<true> : k_mesh_vertex<false>;
-    const auto gather = persp ? k_mesh_assemble<true> : k_mesh_assemble<false>;
-    hipEvent_t a, b;
-    nr_timing_begin(ctx, NRK_MESH_VERTEX, &a, &b);
-    hipLaunchKernelGGL(vertex, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv, mat4_of(matrix),
-                       reinterpret_cast<double2*>(vxy), vz, vq);
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_VERTEX, a, b);
-    nr_timing_begin(ctx, NRK_MESH_ASSEMBLE, &a, &b);
-    hipLaunchKernelGGL(gather, dim3(blocks_for(m->n * 3)), dim3(256), 0, ctx->stream, m->idx, m->n * 3,
-                       reinterpret_cast<const double2*>(vxy), vz, reinterpret_cast<double2*>(xy), z, vq, q);
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_ASSEMBLE, a, b);
-    *out = Soup{xy, z, m->attr, q, m->n};
-    return true;
-}
-
 // `normal9`, or the identity for null.
 Mat3 mat3_of(const f64* normal9) {
     Mat3 N = {{1, 0, 0, 0, 1, 0, 0, 0, 1}};
@@ -863,219 +833,270 @@ Mat3 mat3_of(const f64* normal9) {
     return N;
 }
 
-// The light pass of a single lit draw of `m` under the context's lights, as they are now, into `table` (nv*4).
-void light_pass(RenderContext* ctx, const Mesh* m, const Mat3& N, f64* table) {
-    hipEvent_t a, b;
-    nr_timing_begin(ctx, NRK_MESH_LIGHT, &a, &b);
-    hipLaunchKernelGGL(k_mesh_light, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->normal,
-                       reinterpret_cast<const double2*>(m->rgba), m->nv, N, ctx->meshLights,
-                       reinterpret_cast<double2*>(table));
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_LIGHT, a, b);
-}
-
-// assemble() for a lit colour mesh (m->lit, m->n > 0): the light pass beside the vertex stage, then the assembly
-// gathering the soup's attributes from the colour table -- vertices | table nv*4 | xy n*6 | z n*3 (padded to an
-// even count) | attributes n*stride, all in ctx's mesh staging.
-bool assemble_lit(RenderContext* ctx, const Mesh* m, const f64* matrix, const Mat3& N, Soup* out) {
-    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
-    TriScratch& sc = ctx->tri;
-    const size_t nv = (size_t)m->nv, n = (size_t)m->n;
-    const size_t vzn = (nv + 1) & ~(size_t)1, zn = (n * 3 + 1) & ~(size_t)1;   // keep the table, xy and the attributes 16-byte aligned
-    const size_t stride = (size_t)nrtri::attr_stride(m->mode);
-    if (!sc.mstage.ensure(nv * 2 + vzn + nv * 4 + n * 6 + zn + n * stride)) return false;
-    f64* vxy = sc.mstage;
-    f64* vz = vxy + nv * 2;
-    f64* table = vz + vzn;
-    f64* xy = table + nv * 4;
-    f64* z = xy + n * 6;
-    f64* attr = z + zn;
-    hipEvent_t a, b;
-    nr_timing_begin(ctx, NRK_MESH_VERTEX, &a, &b);
-    hipLaunchKernelGGL(k_mesh_vertex<false>, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv,
-                       mat4_of(matrix), reinterpret_cast<double2*>(vxy), vz, nullptr);
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_VERTEX, a, b);
-    light_pass(ctx, m, N, table);
-    const auto gather = m->mode == nrtri::ATTR_GOURAUD ? k_mesh_lit_assemble<2> : k_mesh_lit_assemble<0>;
-    nr_timing_begin(ctx, NRK_MESH_ASSEMBLE, &a, &b);
-    hipLaunchKernelGGL(gather, dim3(blocks_for(m->n * 3)), dim3(256), 0, ctx->stream, m->idx, m->n * 3,
-                       reinterpret_cast<const double2*>(vxy), vz, reinterpret_cast<const double2*>(table),
-                       reinterpret_cast<double2*>(xy), z, reinterpret_cast<double2*>(attr));
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_ASSEMBLE, a, b);
-    *out = Soup{xy, z, attr, nullptr, m->n};
-    return true;
-}
-
-// A textured mesh (or a textured colour mesh) drawn with the context's perspective state on; colour meshes ignore
-// the state.
-inline bool persp_draw(const RenderContext* ctx, const Mesh* m) {
-    return ctx->meshPersp && (m->mode == ATTR_TEX || m->mode == ATTR_TEXC);
-}
-
-// The unclipped soup of a textured colour mesh (m->mode == ATTR_TEXC, m->n > 0): assemble() with a q for every
-// draw -- 1 / cw under the perspective state, else 1.0 -- and, lit (the normal matrix, else null), the light pass
-// beside the vertex stage and the attributes gathered from the uv and the colour table: vertices | table nv*4 |
-// xy n*6 | z n*3 | q n*3 (each padded to an even count) | attributes n*18, all in ctx's mesh staging.
-bool assemble_uvc(RenderContext* ctx, const Mesh* m, const f64* matrix, const Mat3* lit, Soup* out) {
-    const bool persp = persp_draw(ctx, m);
-    if (!lit) {
-        if (persp) return assemble(ctx, m, matrix, out, true);
-        nrtri::settle(ctx);
-        TriScratch& sc = ctx->tri;
-        const size_t nv = (size_t)m->nv, n = (size_t)m->n, vzn = (nv + 1) & ~(size_t)1;
-        if (!sc.mstage.ensure(nv * 2 + vzn + n * 12)) return false;   // (assemble: nv*2 + vzn + n*9, then q n*3)
-        if (!assemble(ctx, m, matrix, out, false)) return false;      // (settled already; the staging is large enough)
-        f64* q = const_cast<f64*>(out->z) + n * 3;
-        unit_q(ctx, q, (i64)n * 3);
-        out->q = q;
-        return true;
-    }
-    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
-    TriScratch& sc = ctx->tri;
-    const size_t nv = (size_t)m->nv, n = (size_t)m->n;
-    const size_t vzn = (nv + 1) & ~(size_t)1, zn = (n * 3 + 1) & ~(size_t)1;
-    if (!sc.mstage.ensure(nv * 2 + 2 * vzn + nv * 4 + n * 6 + 2 * zn + n * 18)) return false;
-    f64* vxy = sc.mstage;
-    f64* vz = vxy + nv * 2;
-    f64* vq = vz + vzn;
-    f64* table = vq + vzn;
-    f64* xy = table + nv * 4;
-    f64* z = xy + n * 6;
-    f64* q = z + zn;
-    f64* attr = q + zn;
-    hipEvent_t a, b;
-    nr_timing_begin(ctx, NRK_MESH_VERTEX, &a, &b);
-    hipLaunchKernelGGL(persp ? k_mesh_vertex<true> : k_mesh_vertex<false>, dim3(blocks_for(m->nv)), dim3(256), 0,
-                       ctx->stream, m->pos, m->nv, mat4_of(matrix), reinterpret_cast<double2*>(vxy), vz, vq);
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_VERTEX, a, b);
-    light_pass(ctx, m, *lit, table);
-    nr_timing_begin(ctx, NRK_MESH_ASSEMBLE, &a, &b);
-    hipLaunchKernelGGL(persp ? k_mesh_uvc_assemble<true> : k_mesh_uvc_assemble<false>, dim3(blocks_for(m->n * 3)),
-                       dim3(256), 0, ctx->stream, m->idx, m->n * 3, reinterpret_cast<const double2*>(vxy), vz, vq,
-                       reinterpret_cast<const double2*>(m->uv), reinterpret_cast<const double2*>(table),
-                       reinterpret_cast<double2*>(xy), z, q, reinterpret_cast<double2*>(attr));
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_ASSEMBLE, a, b);
-    if (!persp) unit_q(ctx, q, (i64)n * 3);
-    *out = Soup{xy, z, attr, q, m->n};
-    return true;
-}
-
 inline bool clip_stage_on(const RenderContext* ctx) { return ctx->meshNear > 0 || ctx->meshCull != 0; }
 
-// The clip stage of `m` under `matrix` and the context's near plane and cull
-// mode (one of them on; m->n > 0): clip coordinates, count, scan, then -- after
-// the total n_out has been read back, the one wait of such a draw -- the emit
-// pass into ctx's mesh staging, sized to n_out.  out->n == 0: nothing is left
-// to draw (no staging is touched).  False: scratch could not be grown (latched).
-// lit (a lit colour mesh under that normal matrix, else null): the light pass and k_mesh_attr's expansion of its
-// colour table run before the emit pass, behind the soup in the staging, and the emit pass reads that expansion
-// where it reads the mesh's own attributes otherwise.
-bool assemble_clipped(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out, bool persp,
-                      const Mat3* lit = nullptr) {
-    if (m->n > (i64)INT_MAX) return fail("mesh clip stage", "more than 2^31 - 1 triangles");
+// ---- one draw description, two soup builders --------------------------------------------------------------------
+// The K matrices (K*16) and tints (K*4, or null) of an instanced draw, on the device; a lit draw's normal
+// matrices (K*9, or null: the identity for every instance).
+struct Instances { const f64* mats; const f64* tint; i64 K; const f64* normals; };
+
+// Where the soup's 1/w comes from: no q at all; 1 / cw from the vertex stage (a textured or textured colour mesh
+// under the context's perspective state -- colour meshes ignore the state); or 1.0 everywhere (a textured colour
+// mesh without the state: a modulated batch always has a q).
+enum QSource { Q_NONE, Q_INV_CW, Q_UNIT };
+
+// What a draw is, for every pass that builds its soup (m->n > 0; instanced: K > 0, K*n and K*nv below 2^31).
+struct MeshDraw {
+    const Mesh* m;
+    Mat4 M;                  // a single draw's matrix, handed to its kernels by value ...
+    const Instances* inst;   // ... or the instances (null: a single draw)
+    bool lit;                // a light pass comes first: under *N (a single draw), under inst->normals
+    const Mat3* N;
+    QSource q;
+    bool persp() const { return q == Q_INV_CW; }
+    bool tint() const { return inst && inst->tint; }
+};
+
+QSource q_source(const RenderContext* ctx, const Mesh* m) {
+    if (ctx->meshPersp && (m->mode == ATTR_TEX || m->mode == ATTR_TEXC)) return Q_INV_CW;
+    return m->mode == ATTR_TEXC ? Q_UNIT : Q_NONE;
+}
+// lit: the normal matrix of a lit draw, else null
+MeshDraw single_draw(const RenderContext* ctx, const Mesh* m, const f64* matrix16, const Mat3* lit) {
+    return MeshDraw{m, mat4_of(matrix16), nullptr, lit != nullptr, lit, q_source(ctx, m)};
+}
+MeshDraw instanced_draw(const RenderContext* ctx, const Mesh* m, const Instances* in, bool lit) {
+    return MeshDraw{m, Mat4{}, in, lit, nullptr, q_source(ctx, m)};
+}
+
+// The draw as the staging layouts see it (nr_mesh_stage.h): a lit or an instanced soup has attributes of its own.
+nrmesh::StageNeeds stage_needs(const MeshDraw& d) {
+    const size_t K = d.inst ? (size_t)d.inst->K : 1;
+    return nrmesh::StageNeeds{K * (size_t)d.m->nv, K * (size_t)d.m->n, d.persp(), d.lit, d.q == Q_UNIT,
+                              d.lit || d.inst, (size_t)nrtri::attr_stride(d.m->mode)};
+}
+
+// A layout's regions in the staging, resolved once mstage.ensure() has returned.
+struct StagePtrs {
+    double2* vxy; f64* vz; f64* vq;
+    double2* table;
+    double2* xy; f64* z; double2* attr; f64* q;
+    double2* expanded;
+};
+StagePtrs stage_ptrs(f64* base, const nrmesh::Stage& s) {
+    const auto w = [&](nrmesh::Region k) { return reinterpret_cast<double2*>(s.at(base, k)); };
+    return StagePtrs{w(nrmesh::R_VXY), s.at(base, nrmesh::R_VZ), s.at(base, nrmesh::R_VQ), w(nrmesh::R_TABLE),
+                     w(nrmesh::R_XY), s.at(base, nrmesh::R_Z), w(nrmesh::R_ATTR), s.at(base, nrmesh::R_Q),
+                     w(nrmesh::R_EXPANDED)};
+}
+// ... as the soup handed on: its own attributes, else the mesh's expanded ones.
+Soup stage_soup(const StagePtrs& p, const Mesh* m, size_t count) {
+    return Soup{reinterpret_cast<const f64*>(p.xy), p.z, p.attr ? reinterpret_cast<const f64*>(p.attr) : m->attr, p.q,
+                (i64)count};
+}
+
+inline const double2* words(const f64* p) { return reinterpret_cast<const double2*>(p); }
+
+// The kernel instance of each pass: one selection per pass and draw form.
+auto vertex_kernel(const MeshDraw& d) { return d.persp() ? k_mesh_vertex<true> : k_mesh_vertex<false>; }
+auto inst_vertex_kernel(const MeshDraw& d) { return d.persp() ? k_minst_vertex<true> : k_minst_vertex<false>; }
+auto assemble_kernel(const MeshDraw& d) { return d.persp() ? k_mesh_assemble<true> : k_mesh_assemble<false>; }
+auto uvc_assemble_kernel(const MeshDraw& d) { return d.persp() ? k_mesh_uvc_assemble<true> : k_mesh_uvc_assemble<false>; }
+auto lit_assemble_kernel(const MeshDraw& d) {
+    return d.m->mode == ATTR_GOURAUD ? k_mesh_lit_assemble<2> : k_mesh_lit_assemble<0>;
+}
+auto inst_assemble_kernel(const MeshDraw& d) {
+    const bool tint = d.tint();
+    return d.m->mode == ATTR_GOURAUD ? (tint ? k_minst_assemble<2, false, true> : k_minst_assemble<2, false, false>)
+           : d.m->mode != ATTR_TEX   ? (tint ? k_minst_assemble<0, false, true> : k_minst_assemble<0, false, false>)
+           : d.persp()               ? k_minst_assemble<1, true, false>
+                                     : k_minst_assemble<1, false, false>;
+}
+auto inst_lit_assemble_kernel(const MeshDraw& d) {
+    const bool tint = d.tint();
+    return d.m->mode == ATTR_GOURAUD ? (tint ? k_minst_lit_assemble<2, true> : k_minst_lit_assemble<2, false>)
+                                     : (tint ? k_minst_lit_assemble<0, true> : k_minst_lit_assemble<0, false>);
+}
+auto emit_kernel(const MeshDraw& d) {
+    return d.m->mode == ATTR_TEXC      ? (d.persp() ? k_mesh_clip_emit<3, true> : k_mesh_clip_emit<3>)
+           : d.m->mode == ATTR_GOURAUD ? k_mesh_clip_emit<2>
+           : d.m->mode != ATTR_TEX     ? k_mesh_clip_emit<0>
+           : d.persp()                 ? k_mesh_clip_emit<1, true>
+                                       : k_mesh_clip_emit<1>;
+}
+auto inst_emit_kernel(const MeshDraw& d) {
+    const bool tint = d.tint();
+    return d.m->mode == ATTR_GOURAUD ? (tint ? k_minst_clip_emit<2, false, true> : k_minst_clip_emit<2, false, false>)
+           : d.m->mode != ATTR_TEX   ? (tint ? k_minst_clip_emit<0, false, true> : k_minst_clip_emit<0, false, false>)
+           : d.persp()               ? k_minst_clip_emit<1, true, false>
+                                     : k_minst_clip_emit<1, false, false>;
+}
+auto inst_lit_emit_kernel(const MeshDraw& d) {
+    const bool tint = d.tint();
+    return d.m->mode == ATTR_GOURAUD ? (tint ? k_minst_lit_clip_emit<2, true> : k_minst_lit_clip_emit<2, false>)
+                                     : (tint ? k_minst_lit_clip_emit<0, true> : k_minst_lit_clip_emit<0, false>);
+}
+
+// The light pass of a lit draw under the context's lights, as they are now, into `table` (NV*4).
+void light_pass(RenderContext* ctx, const MeshDraw& d, i64 NV, double2* table) {
+    const Mesh* m = d.m;
+    if (d.inst)
+        mesh_launch(ctx, NRK_MESH_INST_LIGHT, k_minst_light, NV, m->normal, words(m->rgba), (u32)m->nv, (u32)NV,
+                    d.inst->normals, ctx->meshLights, table);
+    else
+        mesh_launch(ctx, NRK_MESH_LIGHT, k_mesh_light, NV, m->normal, words(m->rgba), m->nv, *d.N, ctx->meshLights, table);
+}
+
+// The soup of a draw with the clip state off, in ctx's mesh staging, on the context's stream: the vertex stage
+// over all NV vertices, a lit draw's light pass beside it, the assembly of the N triangles -- which also gathers,
+// copies or tints the attributes of a lit or an instanced soup -- and a unit q where the draw needs one.
+// False: the staging could not be grown (error latched).
+bool soup_unclipped(RenderContext* ctx, const MeshDraw& d, Soup* out) {
+    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
+    const Mesh* m = d.m;
+    const nrmesh::StageNeeds need = stage_needs(d);
+    const nrmesh::Stage lay = nrmesh::stage_unclipped(need);
+    if (!ctx->tri.mstage.ensure(lay.total)) return false;
+    const StagePtrs p = stage_ptrs(ctx->tri.mstage, lay);
+    const i64 NV = (i64)need.NV, C = (i64)need.N * 3;   // vertices and corners in all
+    const u32 nv = (u32)m->nv, per = (u32)(m->n * 3);
+    if (d.inst)
+        mesh_launch(ctx, NRK_MESH_INST_VERTEX, inst_vertex_kernel(d), NV, m->pos, nv, (u32)NV, d.inst->mats, p.vxy, p.vz,
+                    p.vq);
+    else
+        mesh_launch(ctx, NRK_MESH_VERTEX, vertex_kernel(d), NV, m->pos, NV, d.M, p.vxy, p.vz, p.vq);
+    if (d.lit) light_pass(ctx, d, NV, p.table);
+    if (d.inst && d.lit)
+        mesh_launch(ctx, NRK_MESH_INST_ASSEMBLE, inst_lit_assemble_kernel(d), C, m->idx, per, (u32)C, nv, p.vxy, p.vz,
+                    p.table, d.inst->tint, p.xy, p.z, p.attr);
+    else if (d.inst)
+        mesh_launch(ctx, NRK_MESH_INST_ASSEMBLE, inst_assemble_kernel(d), C, m->idx, per, (u32)C, nv, p.vxy, p.vz, p.vq,
+                    words(m->attr), d.inst->tint, p.xy, p.z, p.q, p.attr);
+    else if (d.lit && m->mode == ATTR_TEXC)
+        mesh_launch(ctx, NRK_MESH_ASSEMBLE, uvc_assemble_kernel(d), C, m->idx, C, p.vxy, p.vz, p.vq, words(m->uv),
+                    p.table, p.xy, p.z, p.q, p.attr);
+    else if (d.lit)
+        mesh_launch(ctx, NRK_MESH_ASSEMBLE, lit_assemble_kernel(d), C, m->idx, C, p.vxy, p.vz, p.table, p.xy, p.z, p.attr);
+    else
+        mesh_launch(ctx, NRK_MESH_ASSEMBLE, assemble_kernel(d), C, m->idx, C, p.vxy, p.vz, p.xy, p.z, p.vq, p.q);
+    if (d.q == Q_UNIT) unit_q(ctx, p.q, C);
+    *out = stage_soup(p, m, need.N);
+    return true;
+}
+
+// The front half of a draw with the clip state on, under the context's near plane and cull mode: clip coordinates
+// per vertex (TriScratch::mclip), a keep mask and a count per triangle, the exclusive scan of the counts (mscan),
+// and the total nout read back -- the one host wait of such a draw.  An instanced draw runs each pass once over
+// all K*nv vertices or K*n triangles, so the instances' outputs follow each other in instance order.
+// False: scratch could not be grown, or the read-back failed (latched).
+struct ClipFront { const double2* clip; const u32* keep; const u32* off; size_t nout; };
+bool clip_front(RenderContext* ctx, const MeshDraw& d, const nrmesh::StageNeeds& need, ClipFront* f) {
+    const Mesh* m = d.m;
+    const size_t NV = need.NV, N = need.N;
+    if (N > (size_t)INT_MAX) return fail("mesh clip stage", "more than 2^31 - 1 triangles");
     nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
     TriScratch& sc = ctx->tri;
-    const size_t nv = (size_t)m->nv, n = (size_t)m->n;
-    if (!sc.mclip.ensure(nv * 4) || !sc.mscan.ensure(n * 3)) return false;
+    if (!sc.mclip.ensure(NV * 4) || !sc.mscan.ensure(N * 3)) return false;
     u32* keep = sc.mscan;
-    u32* cnt = keep + n;
-    u32* off = cnt + n;
-    size_t need = 0;
-    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, cnt, off, (int)m->n, ctx->stream));
-    if (!grow_temp(sc, need > 0 ? need : 1)) return false;
+    u32* cnt = keep + N;
+    u32* off = cnt + N;
+    size_t temp = 0;
+    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, temp, cnt, off, (int)N, ctx->stream));
+    if (!grow_temp(sc, temp > 0 ? temp : 1)) return false;
     u32* h = reinterpret_cast<u32*>(sc.totals());
     if (!h) return fail("mesh clip stage", "hipHostMalloc failed");
     const f64 wNear = ctx->meshNear;
-    const double2* clip = reinterpret_cast<const double2*>(sc.mclip.p);
-    hipEvent_t a, b;
-    nr_timing_begin(ctx, NRK_MESH_CLIP_VERTEX, &a, &b);
-    hipLaunchKernelGGL(k_mesh_clip_vertex, dim3(blocks_for(m->nv)), dim3(256), 0, ctx->stream, m->pos, m->nv,
-                       mat4_of(matrix), reinterpret_cast<double2*>(sc.mclip.p));
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_CLIP_VERTEX, a, b);
-    nr_timing_begin(ctx, NRK_MESH_CLIP_COUNT, &a, &b);
-    hipLaunchKernelGGL(k_mesh_clip_count, dim3(blocks_for(m->n)), dim3(256), 0, ctx->stream, m->idx, m->n, clip, wNear,
-                       ctx->meshCull, keep, cnt);
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_CLIP_COUNT, a, b);
-    nr_timing_begin(ctx, NRK_MESH_CLIP_SCAN, &a, &b);
-    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(sc.temp, need, cnt, off, (int)m->n, ctx->stream));
-    nr_timing_end(ctx, NRK_MESH_CLIP_SCAN, a, b);
-    // n_out = the last offset + the last count (at most 2n < 2^32): the sync point of a clipped or culled draw
-    NR_CHECK(hipMemcpyAsync(&h[0], off + (n - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    NR_CHECK(hipMemcpyAsync(&h[1], cnt + (n - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("mesh clip stage", "the count could not be read back");
-    const size_t nout = (size_t)h[0] + (size_t)h[1];
-    *out = Soup{nullptr, nullptr, nullptr, nullptr, (i64)nout};
-    if (nout == 0) return true;
-    if (nout > 2 * n) return fail("mesh clip stage", "inconsistent triangle count");   // (never: the counts are 0, 1 or 2)
-    const size_t stride = (size_t)nrtri::attr_stride(m->mode);
-    const size_t zn = (nout * 3 + 1) & ~(size_t)1;   // keeps the attributes 16-byte aligned
-    const bool uvc = m->mode == nrtri::ATTR_TEXC;    // (a textured colour mesh has a q in every draw: 1.0 without the state)
-    // (a lit colour draw has no q, a lit textured colour draw a padded one: even, what follows stays 16-byte aligned)
-    const size_t soup = nout * 6 + zn + nout * stride + (uvc ? zn : (persp ? nout * 3 : 0));
-    if (!sc.mstage.ensure(soup + (lit ? nv * 4 + n * stride : 0))) return false;
-    f64* xy = sc.mstage;
-    f64* z = xy + nout * 6;
-    f64* attr = z + zn;
-    f64* q = persp || uvc ? attr + nout * stride : nullptr;
-    const f64* src = m->attr;
-    if (lit && uvc) {
-        f64* table = xy + soup;
-        f64* expanded = table + nv * 4;
-        light_pass(ctx, m, *lit, table);
-        nr_timing_begin(ctx, NRK_MESH_LIT_ATTR, &a, &b);
-        hipLaunchKernelGGL(k_mesh_uvc_attr, dim3(blocks_for(m->n * 3)), dim3(256), 0, ctx->stream, m->idx, m->n * 3,
-                           reinterpret_cast<const double2*>(m->uv), reinterpret_cast<const double2*>(table),
-                           reinterpret_cast<double2*>(expanded));
-        NR_CHECK(hipGetLastError());
-        nr_timing_end(ctx, NRK_MESH_LIT_ATTR, a, b);
-        src = expanded;
-    } else if (lit) {
-        f64* table = xy + soup;
-        f64* expanded = table + nv * 4;
-        light_pass(ctx, m, *lit, table);
-        const int perTri = m->mode == nrtri::ATTR_FLAT ? 1 : 3;
-        nr_timing_begin(ctx, NRK_MESH_LIT_ATTR, &a, &b);
-        hipLaunchKernelGGL(k_mesh_attr, dim3(blocks_for(m->n * perTri)), dim3(256), 0, ctx->stream, m->idx,
-                           m->n * perTri, perTri, 2, reinterpret_cast<const double2*>(table),
-                           reinterpret_cast<double2*>(expanded));
-        NR_CHECK(hipGetLastError());
-        nr_timing_end(ctx, NRK_MESH_LIT_ATTR, a, b);
-        src = expanded;
+    double2* clip = reinterpret_cast<double2*>(sc.mclip.p);
+    if (d.inst) {
+        mesh_launch(ctx, NRK_MESH_INST_CLIP_VERTEX, k_minst_clip_vertex, (i64)NV, m->pos, (u32)m->nv, (u32)NV,
+                    d.inst->mats, clip);
+        mesh_launch(ctx, NRK_MESH_INST_CLIP_COUNT, k_minst_clip_count, (i64)N, m->idx, (u32)m->n, (u32)N, (u32)m->nv,
+                    clip, wNear, ctx->meshCull, keep, cnt);
+    } else {
+        mesh_launch(ctx, NRK_MESH_CLIP_VERTEX, k_mesh_clip_vertex, m->nv, m->pos, m->nv, d.M, clip);
+        mesh_launch(ctx, NRK_MESH_CLIP_COUNT, k_mesh_clip_count, m->n, m->idx, m->n, clip, wNear, ctx->meshCull, keep, cnt);
     }
-    const auto emit = uvc                            ? (persp ? k_mesh_clip_emit<3, true> : k_mesh_clip_emit<3>)
-                      : m->mode == nrtri::ATTR_GOURAUD ? k_mesh_clip_emit<2>
-                      : m->mode != nrtri::ATTR_TEX   ? k_mesh_clip_emit<0>
-                      : persp                        ? k_mesh_clip_emit<1, true>
-                                                     : k_mesh_clip_emit<1>;
-    nr_timing_begin(ctx, NRK_MESH_CLIP_EMIT, &a, &b);
-    hipLaunchKernelGGL(emit, dim3(blocks_for(m->n)), dim3(256), 0, ctx->stream, m->idx, m->n, clip,
-                       reinterpret_cast<const double2*>(src), wNear, keep, off, reinterpret_cast<double2*>(xy), z,
-                       reinterpret_cast<double2*>(attr), q);
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_CLIP_EMIT, a, b);
-    if (uvc && !persp) unit_q(ctx, q, (i64)nout * 3);
-    *out = Soup{xy, z, attr, q, (i64)nout};
+    const int scan = d.inst ? NRK_MESH_INST_CLIP_SCAN : NRK_MESH_CLIP_SCAN;
+    hipEvent_t a, b;
+    nr_timing_begin(ctx, scan, &a, &b);
+    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(sc.temp, temp, cnt, off, (int)N, ctx->stream));
+    nr_timing_end(ctx, scan, a, b);
+    // nout = the last offset + the last count (at most 2N < 2^32): the sync point of a clipped or culled draw
+    NR_CHECK(hipMemcpyAsync(&h[0], off + (N - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    NR_CHECK(hipMemcpyAsync(&h[1], cnt + (N - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("mesh clip stage", "the count could not be read back");
+    *f = ClipFront{clip, keep, off, (size_t)h[0] + (size_t)h[1]};
     return true;
 }
 
-// The soup a draw of `m` rasterises under the context's clip state: the unclipped
-// path's (vertex stage + assembly, the mesh's own attributes) when it is off.
-bool draw_soup(RenderContext* ctx, const Mesh* m, const f64* matrix, Soup* out) {
-    const bool persp = persp_draw(ctx, m);
-    return clip_stage_on(ctx) ? assemble_clipped(ctx, m, matrix, out, persp) : assemble(ctx, m, matrix, out, persp);
+// The soup of a draw with the clip state on: the front half, then -- in ctx's mesh staging, carved for nout
+// triangles -- the emit pass at the scanned offsets and a unit q where the draw needs one.  A lit draw's light
+// pass and the expansion of its colour table through the indices (k_mesh_attr's, per instance) run before the
+// emit pass, behind the soup in the staging, and the emit pass reads that expansion where it reads the mesh's
+// own attributes otherwise.  out->n == 0: nothing is left to draw (no staging is touched).
+bool soup_clipped(RenderContext* ctx, const MeshDraw& d, Soup* out) {
+    const Mesh* m = d.m;
+    const nrmesh::StageNeeds need = stage_needs(d);
+    ClipFront f;
+    if (!clip_front(ctx, d, need, &f)) return false;
+    *out = Soup{nullptr, nullptr, nullptr, nullptr, (i64)f.nout};
+    if (f.nout == 0) return true;
+    if (f.nout > 2 * need.N) return fail("mesh clip stage", "inconsistent triangle count");   // (never: the counts are 0, 1 or 2)
+    const nrmesh::Stage lay = nrmesh::stage_clipped(need, f.nout);
+    if (!ctx->tri.mstage.ensure(lay.total)) return false;
+    const StagePtrs p = stage_ptrs(ctx->tri.mstage, lay);
+    const i64 NV = (i64)need.NV, N = (i64)need.N;
+    const u32 nv = (u32)m->nv, n = (u32)m->n;
+    const f64 wNear = ctx->meshNear;
+    const double2* src = words(m->attr);
+    if (d.lit) {
+        light_pass(ctx, d, NV, p.table);
+        const int perTri = m->mode == ATTR_FLAT ? 1 : 3;
+        if (d.inst)
+            mesh_launch(ctx, NRK_MESH_INST_LIT_ATTR, k_minst_lit_attr, N * perTri, m->idx, n * (u32)perTri,
+                        (u32)(N * perTri), nv, perTri, p.table, p.expanded);
+        else if (m->mode == ATTR_TEXC)
+            mesh_launch(ctx, NRK_MESH_LIT_ATTR, k_mesh_uvc_attr, N * 3, m->idx, N * 3, words(m->uv), p.table, p.expanded);
+        else
+            mesh_launch(ctx, NRK_MESH_LIT_ATTR, k_mesh_attr, N * perTri, m->idx, N * perTri, perTri, 2, p.table, p.expanded);
+        src = p.expanded;
+    }
+    if (d.inst && d.lit)   // (the emit pass that reads instance k's own attributes)
+        mesh_launch(ctx, NRK_MESH_INST_CLIP_EMIT, inst_lit_emit_kernel(d), N, m->idx, n, (u32)N, nv, f.clip, src,
+                    d.inst->tint, wNear, f.keep, f.off, p.xy, p.z, p.attr);
+    else if (d.inst)
+        mesh_launch(ctx, NRK_MESH_INST_CLIP_EMIT, inst_emit_kernel(d), N, m->idx, n, (u32)N, nv, f.clip, src,
+                    d.inst->tint, wNear, f.keep, f.off, p.xy, p.z, p.attr, p.q);
+    else
+        mesh_launch(ctx, NRK_MESH_CLIP_EMIT, emit_kernel(d), N, m->idx, N, f.clip, src, wNear, f.keep, f.off, p.xy, p.z,
+                    p.attr, p.q);
+    if (d.q == Q_UNIT) unit_q(ctx, p.q, (i64)f.nout * 3);
+    *out = stage_soup(p, m, f.nout);
+    return true;
 }
 
-// ---- instanced draws: host side ---------------------------------------------------
-// The K matrices (K*16) and tints (K*4, or null) of an instanced draw, on the device; a lit draw's normal
-// matrices (K*9, or null: the identity for every instance).
-struct Instances { const f64* mats; const f64* tint; i64 K; const f64* normals = nullptr; };
-bool check_mesh(RenderContext* ctx, const Mesh* m, bool textured, const char* what, bool uvcOk = false);
+// The soup a draw rasterises under the context's clip state.
+bool build_soup(RenderContext* ctx, const MeshDraw& d, Soup* out) {
+    return clip_stage_on(ctx) ? soup_clipped(ctx, d, out) : soup_unclipped(ctx, d, out);
+}
+
+// ---- what the entry points share ----------------------------------------------------------------------------------
+// The checks every mesh draw shares (in the style of check_texture).
+// uvcOk: the call also draws a textured colour mesh (as a textured one); every other call rejects that kind.
+bool check_mesh(RenderContext* ctx, const Mesh* m, bool textured, bool uvcOk, const char* what) {
+    if (!m) return fail(what, "NULL mesh");
+    if (m->mode == nrtri::ATTR_TEXC) {
+        if (!uvcOk) return fail(what, "not supported for a textured colour mesh");
+    } else if ((m->mode == nrtri::ATTR_TEX) != textured)
+        return fail(what, textured ? "a colour mesh (use DrawMesh)" : "a textured mesh (use DrawTexturedMesh)");
+    if (m->device != ctx->device) return fail(what, "mesh on another device");
+    return true;
+}
+
+// What a *Lit call needs of its mesh, after check_mesh(textured = false).
+bool check_lit(const Mesh* m, const char* what) {
+    return m->lit ? true : fail(what, "a mesh without normals (create it with CreateLitMesh)");
+}
 
 // The argument checks every instanced entry point shares, after the mesh's own: false with an error latched under
 // `what`, or *empty when there is nothing to draw (no error).  Nothing is allocated or read before them.
@@ -1093,13 +1114,34 @@ bool check_instances(const RenderContext* ctx, const Mesh* m, const f64* matrice
     return true;
 }
 
+// The checks the Assemble* calls with a capacity share (textured: a textured mesh only), in their order; *n_out is
+// zeroed once it is known to be there.  outputs: every output array is there.
+bool check_assemble(RenderContext* ctx, const Mesh* m, bool textured, i64 cap, bool outputs, i64* n_out,
+                    const char* what) {
+    if (!m) return fail(what, "NULL mesh");
+    if (m->mode == nrtri::ATTR_TEXC) return fail(what, "not supported for a textured colour mesh");
+    if (textured && m->mode != nrtri::ATTR_TEX) return fail(what, "a colour mesh");
+    if (m->device != ctx->device) return fail(what, "mesh on another device");
+    if (!n_out) return fail(what, "NULL output");
+    *n_out = 0;
+    if (cap < 0) return fail(what, "negative capacity");
+    if (cap > 0 && !outputs) return fail(what, "NULL output");
+    return true;
+}
+
+// The mesh checks of the two lit Assemble calls, after check_assemble.
+bool check_assemble_lit(const Mesh* m, const char* what) {
+    if (m->mode == nrtri::ATTR_TEX) return fail(what, "a textured mesh");
+    return check_lit(m, what);
+}
+
 // A host call's matrices and tints onto the device (TriScratch::minst), through the context's pinned buffer by
 // one asynchronous copy: the caller's arrays are free when this returns and the host waits for nothing but an
 // earlier such copy (of the draw before last), long done.  (The copy-and-wait of DrawTriangles' staging would add a host wait to every
 // draw, which is what an instanced draw is there to avoid.)  Settles first: minst follows mstage's rule.
 // normals (a lit draw's, or null) travel behind the tints in the same copy.
-bool upload_instances(RenderContext* ctx, const f64* matrices, const f64* tint, i64 K, Instances* out,
-                      const f64* normals = nullptr) {
+bool upload_instances(RenderContext* ctx, const f64* matrices, const f64* tint, i64 K, const f64* normals,
+                      Instances* out) {
     nrtri::settle(ctx);
     TriScratch& sc = ctx->tri;
     const size_t k = (size_t)K, ntint = tint ? k * 4 : 0, need = k * 16 + ntint + (normals ? k * 9 : 0);
@@ -1117,266 +1159,59 @@ bool upload_instances(RenderContext* ctx, const f64* matrices, const f64* tint, 
     return true;
 }
 
-// assemble() for K instances (m->n > 0, K > 0, K*n and K*nv below 2^31): the vertex table of all instances, then
-// the soup and its attributes -- xy N*6 | z N*3 (padded to an even count) | attributes N*stride | q N*3, the
-// clipped soup's layout -- in ctx's mesh staging, N = K*n.
-bool assemble_instanced(RenderContext* ctx, const Mesh* m, const Instances& in, Soup* out, bool persp) {
-    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
-    TriScratch& sc = ctx->tri;
-    const size_t NV = (size_t)in.K * (size_t)m->nv, N = (size_t)in.K * (size_t)m->n;
-    const size_t vzn = (NV + 1) & ~(size_t)1, zn = (N * 3 + 1) & ~(size_t)1;   // keep xy and the attributes 16-byte aligned
-    const size_t stride = (size_t)nrtri::attr_stride(m->mode);
-    if (!sc.mstage.ensure(NV * 2 + vzn + (persp ? vzn : 0) + N * 6 + zn + N * stride + (persp ? N * 3 : 0))) return false;
-    f64* vxy = sc.mstage;
-    f64* vz = vxy + NV * 2;
-    f64* vq = persp ? vz + vzn : nullptr;
-    f64* xy = vz + vzn + (persp ? vzn : 0);
-    f64* z = xy + N * 6;
-    f64* attr = z + zn;
-    f64* q = persp ? attr + N * stride : nullptr;
-    const bool tint = in.tint != nullptr;
-    const auto vertex = persp ? k_minst_vertex<true> : k_minst_vertex<false>;
-    const auto gather = m->mode == nrtri::ATTR_GOURAUD ? (tint ? k_minst_assemble<2, false, true> : k_minst_assemble<2, false, false>)
-                        : m->mode != nrtri::ATTR_TEX   ? (tint ? k_minst_assemble<0, false, true> : k_minst_assemble<0, false, false>)
-                        : persp                        ? k_minst_assemble<1, true, false>
-                                                       : k_minst_assemble<1, false, false>;
-    hipEvent_t a, b;
-    nr_timing_begin(ctx, NRK_MESH_INST_VERTEX, &a, &b);
-    hipLaunchKernelGGL(vertex, dim3(blocks_for((i64)NV)), dim3(256), 0, ctx->stream, m->pos, (u32)m->nv, (u32)NV, in.mats,
-                       reinterpret_cast<double2*>(vxy), vz, vq);
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_INST_VERTEX, a, b);
-    nr_timing_begin(ctx, NRK_MESH_INST_ASSEMBLE, &a, &b);
-    hipLaunchKernelGGL(gather, dim3(blocks_for((i64)N * 3)), dim3(256), 0, ctx->stream, m->idx, (u32)(m->n * 3),
-                       (u32)(N * 3), (u32)m->nv, reinterpret_cast<const double2*>(vxy), vz, vq,
-                       reinterpret_cast<const double2*>(m->attr), in.tint, reinterpret_cast<double2*>(xy), z, q,
-                       reinterpret_cast<double2*>(attr));
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_INST_ASSEMBLE, a, b);
-    *out = Soup{xy, z, attr, q, (i64)N};
-    return true;
-}
+inline nrtri::Opacity mesh_opacity(const Mesh* m) { return m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED; }
 
-// The light pass of an instanced lit draw: the colour table of all K*nv (instance, vertex) pairs.
-void light_pass_instanced(RenderContext* ctx, const Mesh* m, const Instances& in, f64* table) {
-    const size_t NV = (size_t)in.K * (size_t)m->nv;
-    hipEvent_t a, b;
-    nr_timing_begin(ctx, NRK_MESH_INST_LIGHT, &a, &b);
-    hipLaunchKernelGGL(k_minst_light, dim3(blocks_for((i64)NV)), dim3(256), 0, ctx->stream, m->normal,
-                       reinterpret_cast<const double2*>(m->rgba), (u32)m->nv, (u32)NV, in.normals, ctx->meshLights,
-                       reinterpret_cast<double2*>(table));
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_INST_LIGHT, a, b);
-}
-
-// assemble_instanced() for a lit colour mesh: the colour table K*nv*4 behind the vertex table, and the assembly
-// gathering instance k's attributes from its part of it.
-bool assemble_instanced_lit(RenderContext* ctx, const Mesh* m, const Instances& in, Soup* out) {
-    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
-    TriScratch& sc = ctx->tri;
-    const size_t NV = (size_t)in.K * (size_t)m->nv, N = (size_t)in.K * (size_t)m->n;
-    const size_t vzn = (NV + 1) & ~(size_t)1, zn = (N * 3 + 1) & ~(size_t)1;   // keep the table, xy and the attributes 16-byte aligned
-    const size_t stride = (size_t)nrtri::attr_stride(m->mode);
-    if (!sc.mstage.ensure(NV * 2 + vzn + NV * 4 + N * 6 + zn + N * stride)) return false;
-    f64* vxy = sc.mstage;
-    f64* vz = vxy + NV * 2;
-    f64* table = vz + vzn;
-    f64* xy = table + NV * 4;
-    f64* z = xy + N * 6;
-    f64* attr = z + zn;
-    const bool tint = in.tint != nullptr;
-    const auto gather = m->mode == nrtri::ATTR_GOURAUD ? (tint ? k_minst_lit_assemble<2, true> : k_minst_lit_assemble<2, false>)
-                                                       : (tint ? k_minst_lit_assemble<0, true> : k_minst_lit_assemble<0, false>);
-    hipEvent_t a, b;
-    nr_timing_begin(ctx, NRK_MESH_INST_VERTEX, &a, &b);
-    hipLaunchKernelGGL(k_minst_vertex<false>, dim3(blocks_for((i64)NV)), dim3(256), 0, ctx->stream, m->pos, (u32)m->nv,
-                       (u32)NV, in.mats, reinterpret_cast<double2*>(vxy), vz, nullptr);
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_INST_VERTEX, a, b);
-    light_pass_instanced(ctx, m, in, table);
-    nr_timing_begin(ctx, NRK_MESH_INST_ASSEMBLE, &a, &b);
-    hipLaunchKernelGGL(gather, dim3(blocks_for((i64)N * 3)), dim3(256), 0, ctx->stream, m->idx, (u32)(m->n * 3),
-                       (u32)(N * 3), (u32)m->nv, reinterpret_cast<const double2*>(vxy), vz,
-                       reinterpret_cast<const double2*>(table), in.tint, reinterpret_cast<double2*>(xy), z,
-                       reinterpret_cast<double2*>(attr));
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_INST_ASSEMBLE, a, b);
-    *out = Soup{xy, z, attr, nullptr, (i64)N};
-    return true;
-}
-
-// assemble_clipped() for K instances: the count, the scan and the emit run once over all K*n triangles, with one
-// read-back of the total, so the instances' clipped soups follow each other in instance order.
-// lit (a lit colour mesh): as in assemble_clipped -- the light pass and the expansion of the colour table, K*n
-// triangles' worth, behind the soup; the emit pass is then the one that reads instance k's own attributes.
-bool assemble_instanced_clipped(RenderContext* ctx, const Mesh* m, const Instances& in, Soup* out, bool persp,
-                                bool lit = false) {
-    nrtri::settle(ctx);   // a pending batch may still read the staging (its re-run comes first)
-    TriScratch& sc = ctx->tri;
-    const size_t NV = (size_t)in.K * (size_t)m->nv, N = (size_t)in.K * (size_t)m->n;
-    if (!sc.mclip.ensure(NV * 4) || !sc.mscan.ensure(N * 3)) return false;
-    u32* keep = sc.mscan;
-    u32* cnt = keep + N;
-    u32* off = cnt + N;
-    size_t need = 0;
-    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, cnt, off, (int)N, ctx->stream));
-    if (!grow_temp(sc, need > 0 ? need : 1)) return false;
-    u32* h = reinterpret_cast<u32*>(sc.totals());
-    if (!h) return fail("mesh clip stage", "hipHostMalloc failed");
-    const f64 wNear = ctx->meshNear;
-    const double2* clip = reinterpret_cast<const double2*>(sc.mclip.p);
-    const u32 nv = (u32)m->nv, n = (u32)m->n;
-    hipEvent_t a, b;
-    nr_timing_begin(ctx, NRK_MESH_INST_CLIP_VERTEX, &a, &b);
-    hipLaunchKernelGGL(k_minst_clip_vertex, dim3(blocks_for((i64)NV)), dim3(256), 0, ctx->stream, m->pos, nv, (u32)NV,
-                       in.mats, reinterpret_cast<double2*>(sc.mclip.p));
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_INST_CLIP_VERTEX, a, b);
-    nr_timing_begin(ctx, NRK_MESH_INST_CLIP_COUNT, &a, &b);
-    hipLaunchKernelGGL(k_minst_clip_count, dim3(blocks_for((i64)N)), dim3(256), 0, ctx->stream, m->idx, n, (u32)N, nv,
-                       clip, wNear, ctx->meshCull, keep, cnt);
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_INST_CLIP_COUNT, a, b);
-    nr_timing_begin(ctx, NRK_MESH_INST_CLIP_SCAN, &a, &b);
-    NR_CHECK(hipcub::DeviceScan::ExclusiveSum(sc.temp, need, cnt, off, (int)N, ctx->stream));
-    nr_timing_end(ctx, NRK_MESH_INST_CLIP_SCAN, a, b);
-    // n_out = the last offset + the last count (at most 2N < 2^32): the one sync point of the draw
-    NR_CHECK(hipMemcpyAsync(&h[0], off + (N - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    NR_CHECK(hipMemcpyAsync(&h[1], cnt + (N - 1), sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("mesh clip stage", "the count could not be read back");
-    const size_t nout = (size_t)h[0] + (size_t)h[1];
-    *out = Soup{nullptr, nullptr, nullptr, nullptr, (i64)nout};
-    if (nout == 0) return true;
-    if (nout > 2 * N) return fail("mesh clip stage", "inconsistent triangle count");   // (never: the counts are 0, 1 or 2)
-    const size_t stride = (size_t)nrtri::attr_stride(m->mode);
-    const size_t zn = (nout * 3 + 1) & ~(size_t)1;   // keeps the attributes 16-byte aligned
-    const size_t soup = nout * 6 + zn + nout * stride + (persp ? nout * 3 : 0);   // (a lit draw has no q: even)
-    if (!sc.mstage.ensure(soup + (lit ? NV * 4 + N * stride : 0))) return false;
-    f64* xy = sc.mstage;
-    f64* z = xy + nout * 6;
-    f64* attr = z + zn;
-    f64* q = persp ? attr + nout * stride : nullptr;
-    const bool tint = in.tint != nullptr;
-    if (lit) {
-        f64* table = xy + soup;
-        f64* expanded = table + NV * 4;
-        light_pass_instanced(ctx, m, in, table);
-        const int perTri = m->mode == nrtri::ATTR_FLAT ? 1 : 3;
-        nr_timing_begin(ctx, NRK_MESH_INST_LIT_ATTR, &a, &b);
-        hipLaunchKernelGGL(k_minst_lit_attr, dim3(blocks_for((i64)N * perTri)), dim3(256), 0, ctx->stream, m->idx,
-                           n * (u32)perTri, (u32)(N * perTri), nv, perTri, reinterpret_cast<const double2*>(table),
-                           reinterpret_cast<double2*>(expanded));
-        NR_CHECK(hipGetLastError());
-        nr_timing_end(ctx, NRK_MESH_INST_LIT_ATTR, a, b);
-        const auto lemit = m->mode == nrtri::ATTR_GOURAUD ? (tint ? k_minst_lit_clip_emit<2, true> : k_minst_lit_clip_emit<2, false>)
-                                                          : (tint ? k_minst_lit_clip_emit<0, true> : k_minst_lit_clip_emit<0, false>);
-        nr_timing_begin(ctx, NRK_MESH_INST_CLIP_EMIT, &a, &b);
-        hipLaunchKernelGGL(lemit, dim3(blocks_for((i64)N)), dim3(256), 0, ctx->stream, m->idx, n, (u32)N, nv, clip,
-                           reinterpret_cast<const double2*>(expanded), in.tint, wNear, keep, off,
-                           reinterpret_cast<double2*>(xy), z, reinterpret_cast<double2*>(attr));
-        NR_CHECK(hipGetLastError());
-        nr_timing_end(ctx, NRK_MESH_INST_CLIP_EMIT, a, b);
-        *out = Soup{xy, z, attr, nullptr, (i64)nout};
-        return true;
-    }
-    const auto emit = m->mode == nrtri::ATTR_GOURAUD ? (tint ? k_minst_clip_emit<2, false, true> : k_minst_clip_emit<2, false, false>)
-                      : m->mode != nrtri::ATTR_TEX   ? (tint ? k_minst_clip_emit<0, false, true> : k_minst_clip_emit<0, false, false>)
-                      : persp                        ? k_minst_clip_emit<1, true, false>
-                                                     : k_minst_clip_emit<1, false, false>;
-    nr_timing_begin(ctx, NRK_MESH_INST_CLIP_EMIT, &a, &b);
-    hipLaunchKernelGGL(emit, dim3(blocks_for((i64)N)), dim3(256), 0, ctx->stream, m->idx, n, (u32)N, nv, clip,
-                       reinterpret_cast<const double2*>(m->attr), in.tint, wNear, keep, off,
-                       reinterpret_cast<double2*>(xy), z, reinterpret_cast<double2*>(attr), q);
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_INST_CLIP_EMIT, a, b);
-    *out = Soup{xy, z, attr, q, (i64)nout};
-    return true;
-}
-
-// The soup an instanced draw rasterises under the context's clip and perspective state; lit: a lit draw's,
-// also under the context's lights.
-bool instanced_soup(RenderContext* ctx, const Mesh* m, const Instances& in, Soup* out, bool lit = false) {
-    const bool persp = persp_draw(ctx, m);
-    if (lit) return clip_stage_on(ctx) ? assemble_instanced_clipped(ctx, m, in, out, false, true)
-                                       : assemble_instanced_lit(ctx, m, in, out);
-    return clip_stage_on(ctx) ? assemble_instanced_clipped(ctx, m, in, out, persp)
-                              : assemble_instanced(ctx, m, in, out, persp);
-}
-
-// What a *Lit call needs of its mesh, after check_mesh(textured = false).
-bool check_lit(const Mesh* m, const char* what) {
-    return m->lit ? true : fail(what, "a mesh without normals (create it with CreateLitMesh)");
+// The tail of every mesh draw: the soup's count is the context's last count, and what is left of it goes to the
+// rasters as one batch -- of the mesh's own mode, or sampled from `tex` (modulated: a textured colour mesh's, the
+// texel times the interpolated colour; s.q: the perspective state, or the unit q).
+void submit(RenderContext* ctx, const Mesh* m, Texture* tex, const Soup& s, nrtri::Opacity opq, bool modulated) {
+    ctx->meshLastCount = s.n;
+    if (s.n <= 0) return;   // (clipped or culled away)
+    Batch b = soup_batch(s, tex ? nrtri::ATTR_TEX : m->mode, opq, nullptr, false);
+    b.modulated = modulated;
+    if (tex) nrtri::draw_textured(ctx, tex, b);
+    else nrtri::draw(ctx, b);
 }
 
 // The instanced draw entry points under the caller's name `what`.  onDevice: matrices, tint and normals are device
 // arrays, read only by the vertex, light and assembly kernels launched here; the batch reads the context's staging.
 // lit: a lit draw (a colour mesh with normals), `normals` its K*9 normal matrices or null.
 void draw_instanced(RenderContext* ctx, Mesh* m, Texture* tex, bool textured, const f64* matrices, const f64* tint,
-                    i64 K, bool onDevice, const char* what, bool lit = false, const f64* normals = nullptr) {
+                    i64 K, bool onDevice, const char* what, bool lit, const f64* normals) {
     NR_CHECK(hipSetDevice(ctx->device));
     ctx->meshLastCount = 0;
-    if (!check_mesh(ctx, m, textured, what) || (lit && !check_lit(m, what))) return;
+    if (!check_mesh(ctx, m, textured, false, what) || (lit && !check_lit(m, what))) return;
     if (ctx->recording) nr_settle(ctx);   // recorded draws come first
     if (textured && !nrtri::check_texture(ctx, tex, what)) return;
     bool empty;
     if (!check_instances(ctx, m, matrices, tint, K, true, &empty, what) || empty) return;
     Instances in{matrices, tint, K, normals};
-    if (!onDevice && !upload_instances(ctx, matrices, tint, K, &in, normals)) return;
+    if (!onDevice && !upload_instances(ctx, matrices, tint, K, normals, &in)) return;
     Soup s;
-    if (!instanced_soup(ctx, m, in, &s, lit)) return;
-    ctx->meshLastCount = s.n;
-    if (s.n <= 0) return;   // (clipped or culled away)
-    if (textured) {
-        Batch b = soup_batch(s, nrtri::ATTR_TEX, nrtri::OPQ_UNKNOWN, nullptr, false);   // (s.q: the perspective state)
-        nrtri::draw_textured(ctx, tex, b);
-        return;
-    }
-    // opaque: an opaque mesh under no tint or tints of alpha 1 (a device tint: the batch's own device scan)
-    nrtri::Opacity opq = m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED;
+    if (!build_soup(ctx, instanced_draw(ctx, m, &in, lit), &s)) return;
+    // opaque: an opaque mesh under no tint or tints of alpha 1 (a device tint: the batch's own device scan); a
+    // textured batch: decided by the texture
+    nrtri::Opacity opq = textured ? nrtri::OPQ_UNKNOWN : mesh_opacity(m);
     if (tint && m->opaque) {
         if (onDevice) opq = nrtri::OPQ_UNKNOWN;
         else
             for (i64 k = 0; k < K; ++k)
                 if (tint[k * 4 + 3] != 1) { opq = nrtri::OPQ_BLENDED; break; }
     }
-    nrtri::draw(ctx, soup_batch(s, m->mode, opq, nullptr, false));
+    submit(ctx, m, textured ? tex : nullptr, s, opq, false);
 }
 
-// Copy-out of the Assemble* entry points: the first k triangles of each part (`per` doubles a triangle; a null
-// source is skipped) to the host, then the wait.
-struct CopyOut { f64* dst; const f64* src; size_t per; };
-void copy_out(RenderContext* ctx, size_t k, std::initializer_list<CopyOut> parts) {
-    for (const CopyOut& c : parts)
-        if (k > 0 && c.src)
+// The tail of the Assemble* entry points: *n_out (where the call has one) is the full count, and the first
+// k = min(cap, count) triangles of each part that is there on both sides go to the host, then the wait.
+size_t copy_soup(RenderContext* ctx, const Soup& s, i64 cap, i64* n_out, f64* xy, f64* z, f64* attr, int stride, f64* q) {
+    struct Part { f64* dst; const f64* src; size_t per; };
+    if (n_out) *n_out = s.n;
+    const size_t k = (size_t)(s.n < cap ? s.n : cap);
+    for (const Part& c : {Part{xy, s.xy, 6}, Part{z, s.z, 3}, Part{attr, s.attr, (size_t)stride}, Part{q, s.q, 3}})
+        if (k > 0 && c.dst && c.src)
             NR_CHECK(hipMemcpyAsync(c.dst, c.src, k * c.per * sizeof(f64), hipMemcpyDeviceToHost, ctx->stream));
     NR_CHECK(hipStreamSynchronize(ctx->stream));
-}
-
-// The checks AssembleMeshClipped and AssembleMeshPerspective (textured: a textured mesh only) share, in their
-// order; *n_out is zeroed once it is known to be there.  outputs: every output array is there.
-bool check_assemble(RenderContext* ctx, const Mesh* m, bool textured, i64 cap, bool outputs, i64* n_out,
-                    const char* what) {
-    if (!m) return fail(what, "NULL mesh");
-    if (m->mode == nrtri::ATTR_TEXC) return fail(what, "not supported for a textured colour mesh");
-    if (textured && m->mode != nrtri::ATTR_TEX) return fail(what, "a colour mesh");
-    if (m->device != ctx->device) return fail(what, "mesh on another device");
-    if (!n_out) return fail(what, "NULL output");
-    *n_out = 0;
-    if (cap < 0) return fail(what, "negative capacity");
-    if (cap > 0 && !outputs) return fail(what, "NULL output");
-    return true;
-}
-
-// The checks every mesh draw shares (in the style of check_texture).
-// uvcOk: the call also draws a textured colour mesh (as a textured one); every other call rejects that kind.
-bool check_mesh(RenderContext* ctx, const Mesh* m, bool textured, const char* what, bool uvcOk) {
-    if (!m) return fail(what, "NULL mesh");
-    if (m->mode == nrtri::ATTR_TEXC) {
-        if (!uvcOk) return fail(what, "not supported for a textured colour mesh");
-    } else if ((m->mode == nrtri::ATTR_TEX) != textured)
-        return fail(what, textured ? "a colour mesh (use DrawMesh)" : "a textured mesh (use DrawTexturedMesh)");
-    if (m->device != ctx->device) return fail(what, "mesh on another device");
-    return true;
+    return k;
 }
 
 // Every context that may have a pending batch reading the mesh's arrays is
@@ -1386,6 +1221,18 @@ void quiesce(const Mesh* m) {
     NR_CHECK(hipSetDevice(m->device));
     NR_CHECK(hipStreamSynchronize(nr_stream_for(m->device)));
     NR_CHECK(hipStreamSynchronize(nr_bin_stream_for(m->device)));
+}
+
+// UpdateMeshPositions and UpdateMeshNormals: nv*3 doubles from the host into `dst`, once nothing reads it any more.
+bool update_array(const Mesh* m, f64* dst, const f64* src) {
+    int prev = 0;
+    NR_CHECK(hipGetDevice(&prev));
+    quiesce(m);
+    hipStream_t s = nr_stream_for(m->device);
+    NR_CHECK(hipMemcpyAsync(dst, src, (size_t)m->nv * 3 * sizeof(f64), hipMemcpyHostToDevice, s));
+    NR_CHECK(hipStreamSynchronize(s));   // caller may reuse its array on return
+    NR_CHECK(hipSetDevice(prev));
+    return true;
 }
 
 }  // namespace
@@ -1399,7 +1246,7 @@ extern "C" {
 // triangle's first index) or Gouraud.  One H2D upload; NULL + error on an index
 // >= nv, NULL rgba with n > 0, or nv beyond 32 bits.  n == 0 is a valid mesh.
 Mesh* CreateMesh(i64 nv, const f64* pos, i64 n, const uint32_t* idx, const f64* rgba, bool gouraud) {
-    return create_mesh("CreateMesh", nv, pos, n, idx, rgba, gouraud, nullptr);
+    return create_mesh("CreateMesh", nv, pos, n, idx, rgba, gouraud, nullptr, nullptr);
 }
 
 // New: an indexed mesh with per-vertex texture coordinates (nv*2, texel units).
@@ -1409,7 +1256,7 @@ Mesh* CreateTexturedMesh(i64 nv, const f64* pos, i64 n, const uint32_t* idx, con
         return nullptr;
     }
     static const f64 none[2] = {0, 0};
-    return create_mesh("CreateTexturedMesh", nv, pos, n, idx, nullptr, false, uv ? uv : none);
+    return create_mesh("CreateTexturedMesh", nv, pos, n, idx, nullptr, false, uv ? uv : none, nullptr);
 }
 
 void DestroyMesh(Mesh* m) {
@@ -1417,14 +1264,8 @@ void DestroyMesh(Mesh* m) {
     int prev = 0;
     NR_CHECK(hipGetDevice(&prev));
     quiesce(m);
-    if (m->pos) NR_CHECK(hipFree(m->pos));
-    if (m->idx) NR_CHECK(hipFree(m->idx));
-    if (m->attr) NR_CHECK(hipFree(m->attr));
-    if (m->rgba) NR_CHECK(hipFree(m->rgba));
-    if (m->uv) NR_CHECK(hipFree(m->uv));
-    if (m->normal) NR_CHECK(hipFree(m->normal));
+    free_mesh(m);
     NR_CHECK(hipSetDevice(prev));
-    delete m;
 }
 
 i64 GetMeshVertexCount(Mesh* m) { return m->nv; }
@@ -1436,14 +1277,7 @@ bool UpdateMeshPositions(Mesh* m, const f64* pos) {
     if (!m) return fail("UpdateMeshPositions", "NULL mesh");
     if (m->nv == 0) return true;
     if (!pos) return fail("UpdateMeshPositions", "NULL positions");
-    int prev = 0;
-    NR_CHECK(hipGetDevice(&prev));
-    quiesce(m);
-    hipStream_t s = nr_stream_for(m->device);
-    NR_CHECK(hipMemcpyAsync(m->pos, pos, (size_t)m->nv * 3 * sizeof(f64), hipMemcpyHostToDevice, s));
-    NR_CHECK(hipStreamSynchronize(s));   // caller may reuse its array on return
-    NR_CHECK(hipSetDevice(prev));
-    return true;
+    return update_array(m, m->pos, pos);
 }
 
 // New: draws a colour mesh under the row-major 4x4 `matrix16` (NULL: the
@@ -1451,52 +1285,29 @@ bool UpdateMeshPositions(Mesh* m, const f64* pos) {
 // for DrawTriangles.
 void DrawMesh(RenderContext* ctx, Mesh* m, const f64* matrix16) {
     NR_CHECK(hipSetDevice(ctx->device));
-    if (!check_mesh(ctx, m, false, "DrawMesh")) return;
+    if (!check_mesh(ctx, m, false, false, "DrawMesh")) return;
     if (ctx->recording) nr_settle(ctx);   // recorded draws come first
     ctx->meshLastCount = 0;
     if (m->n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
     Soup s;
-    if (!draw_soup(ctx, m, matrix16, &s)) return;
-    ctx->meshLastCount = s.n;
-    if (s.n <= 0) return;   // (clipped or culled away)
-    nrtri::draw(ctx, soup_batch(s, m->mode, m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED, nullptr, false));
-}
-
-// The soup a draw of the textured colour mesh `m` rasterises: lit (its normal matrix) or not (null).
-static bool uvc_soup(RenderContext* ctx, const Mesh* m, const f64* matrix16, const Mat3* lit, Soup* s) {
-    return clip_stage_on(ctx) ? assemble_clipped(ctx, m, matrix16, s, persp_draw(ctx, m), lit)
-                              : assemble_uvc(ctx, m, matrix16, lit, s);
-}
-
-// ... and its modulated batch: opaque when the texture has no alpha (draw_textured) and every vertex alpha is 1
-// (the light pass copies alpha; a cut vertex's is 1 + 0 * t).
-static void draw_uvc_batch(RenderContext* ctx, const Mesh* m, Texture* tex, const Soup& s) {
-    Batch b = soup_batch(s, nrtri::ATTR_TEX, m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED, nullptr, false);
-    b.modulated = true;
-    nrtri::draw_textured(ctx, tex, b);
+    if (!build_soup(ctx, single_draw(ctx, m, matrix16, nullptr), &s)) return;
+    submit(ctx, m, nullptr, s, mesh_opacity(m), false);
 }
 
 // New: draws a textured mesh sampled from `tex` (chosen per draw); a textured colour mesh: modulated by its own
-// vertex colours, unlit.
+// vertex colours, unlit -- opaque when the texture has no alpha (draw_textured) and every vertex alpha is 1 (a cut
+// vertex's is 1 + 0 * t).
 void DrawTexturedMesh(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrix16) {
     NR_CHECK(hipSetDevice(ctx->device));
-    if (!check_mesh(ctx, m, true, "DrawTexturedMesh", true)) return;
+    if (!check_mesh(ctx, m, true, true, "DrawTexturedMesh")) return;
     if (ctx->recording) nr_settle(ctx);   // recorded draws come first
     if (!nrtri::check_texture(ctx, tex, "DrawTexturedMesh")) return;
     ctx->meshLastCount = 0;
     if (m->n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
+    const bool uvc = m->mode == nrtri::ATTR_TEXC;
     Soup s;
-    if (m->mode == nrtri::ATTR_TEXC) {
-        if (!uvc_soup(ctx, m, matrix16, nullptr, &s)) return;
-        ctx->meshLastCount = s.n;
-        if (s.n > 0) draw_uvc_batch(ctx, m, tex, s);
-        return;
-    }
-    if (!draw_soup(ctx, m, matrix16, &s)) return;
-    ctx->meshLastCount = s.n;
-    if (s.n <= 0) return;
-    Batch b = soup_batch(s, nrtri::ATTR_TEX, nrtri::OPQ_UNKNOWN, nullptr, false);   // (s.q: the perspective state)
-    nrtri::draw_textured(ctx, tex, b);
+    if (!build_soup(ctx, single_draw(ctx, m, matrix16, nullptr), &s)) return;
+    submit(ctx, m, tex, s, uvc ? mesh_opacity(m) : nrtri::OPQ_UNKNOWN, uvc);
 }
 
 // New: the vertex stage and the assembly alone -- exactly the kernels DrawMesh
@@ -1508,9 +1319,11 @@ bool AssembleMesh(RenderContext* ctx, Mesh* m, const f64* matrix16, f64* xy_out,
     if (m->device != ctx->device) return fail("AssembleMesh", "mesh on another device");
     if (m->n <= 0) return true;
     if (!xy_out || !z_out) return fail("AssembleMesh", "NULL output");
+    MeshDraw d = single_draw(ctx, m, matrix16, nullptr);
+    d.q = Q_NONE;   // (the clip and perspective state are ignored)
     Soup s;
-    if (!assemble(ctx, m, matrix16, &s, false)) return false;   // (the clip and perspective state are ignored)
-    copy_out(ctx, (size_t)s.n, {{xy_out, s.xy, 6}, {z_out, s.z, 3}});
+    if (!soup_unclipped(ctx, d, &s)) return false;
+    copy_soup(ctx, s, s.n, nullptr, xy_out, z_out, nullptr, 0, nullptr);
     return true;
 }
 
@@ -1560,10 +1373,8 @@ bool AssembleMeshPerspective(RenderContext* ctx, Mesh* m, const f64* matrix16, i
     if (!check_assemble(ctx, m, true, cap, outputs, n_out, "AssembleMeshPerspective")) return false;
     if (m->n <= 0) return true;
     Soup s;
-    if (!draw_soup(ctx, m, matrix16, &s)) return false;
-    *n_out = s.n;
-    const size_t k = (size_t)(s.n < cap ? s.n : cap);
-    copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {uv_out, s.attr, 6}, {q_out, s.q, 3}});
+    if (!build_soup(ctx, single_draw(ctx, m, matrix16, nullptr), &s)) return false;
+    const size_t k = copy_soup(ctx, s, cap, n_out, xy_out, z_out, uv_out, 6, q_out);
     if (!s.q)
         for (size_t i = 0; i < k * 3; ++i) q_out[i] = 1.0;
     return true;
@@ -1583,10 +1394,8 @@ bool AssembleMeshClipped(RenderContext* ctx, Mesh* m, const f64* matrix16, i64 c
     if (!check_assemble(ctx, m, false, cap, xy_out && z_out && attr_out, n_out, "AssembleMeshClipped")) return false;
     if (m->n <= 0) return true;
     Soup s;
-    if (!draw_soup(ctx, m, matrix16, &s)) return false;
-    *n_out = s.n;
-    const size_t k = (size_t)(s.n < cap ? s.n : cap);
-    copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {attr_out, s.attr, (size_t)nrtri::attr_stride(m->mode)}});
+    if (!build_soup(ctx, single_draw(ctx, m, matrix16, nullptr), &s)) return false;
+    copy_soup(ctx, s, cap, n_out, xy_out, z_out, attr_out, nrtri::attr_stride(m->mode), nullptr);
     return true;
 }
 
@@ -1597,21 +1406,21 @@ bool AssembleMeshClipped(RenderContext* ctx, Mesh* m, const f64* matrix16, i64 c
 // Host arrays, free again on return.  K == 0 draws nothing; K < 0, NULL matrices with K > 0, or more than
 // 2^31 - 1 triangles or vertices in all latch an error and draw nothing.
 void DrawMeshInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* tint, i64 K) {
-    draw_instanced(ctx, m, nullptr, false, matrices, tint, K, false, "DrawMeshInstanced");
+    draw_instanced(ctx, m, nullptr, false, matrices, tint, K, false, "DrawMeshInstanced", false, nullptr);
 }
 
 // New: the same for a textured mesh sampled from `tex` (no tint).
 void DrawTexturedMeshInstanced(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrices, i64 K) {
-    draw_instanced(ctx, m, tex, true, matrices, nullptr, K, false, "DrawTexturedMeshInstanced");
+    draw_instanced(ctx, m, tex, true, matrices, nullptr, K, false, "DrawTexturedMeshInstanced", false, nullptr);
 }
 
 // New: the same from device-resident matrices and tint (as DrawTrianglesDevice: valid and unchanged until the
 // draw has executed).  Only the vertex and assembly kernels launched in the call read them.
 void DrawMeshInstancedDevice(RenderContext* ctx, Mesh* m, const f64* matrices, const f64* tint, i64 K) {
-    draw_instanced(ctx, m, nullptr, false, matrices, tint, K, true, "DrawMeshInstancedDevice");
+    draw_instanced(ctx, m, nullptr, false, matrices, tint, K, true, "DrawMeshInstancedDevice", false, nullptr);
 }
 void DrawTexturedMeshInstancedDevice(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrices, i64 K) {
-    draw_instanced(ctx, m, tex, true, matrices, nullptr, K, true, "DrawTexturedMeshInstancedDevice");
+    draw_instanced(ctx, m, tex, true, matrices, nullptr, K, true, "DrawTexturedMeshInstancedDevice", false, nullptr);
 }
 
 // New: the soup an instanced draw of `m` rasterises under the context's near plane, cull mode and perspective
@@ -1622,7 +1431,7 @@ bool AssembleMeshInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, con
                            f64* xy_out, f64* z_out, f64* attr_out, f64* q_out, i64* n_out) {
     const char* what = "AssembleMeshInstanced";
     NR_CHECK(hipSetDevice(ctx->device));
-    const bool persp = m && persp_draw(ctx, m);
+    const bool persp = m && q_source(ctx, m) == Q_INV_CW;
     const bool outputs = xy_out && z_out && attr_out && (q_out || !persp);
     if (!check_assemble(ctx, m, false, cap, outputs, n_out, what)) return false;
     bool empty;
@@ -1630,11 +1439,9 @@ bool AssembleMeshInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, con
     if (empty) return true;
     Instances in;
     Soup s;
-    if (!upload_instances(ctx, matrices, tint, K, &in) || !instanced_soup(ctx, m, in, &s)) return false;
-    *n_out = s.n;
-    const size_t k = (size_t)(s.n < cap ? s.n : cap);
-    copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {attr_out, s.attr, (size_t)nrtri::attr_stride(m->mode)},
-                      {q_out, s.q, 3}});
+    if (!upload_instances(ctx, matrices, tint, K, nullptr, &in) || !build_soup(ctx, instanced_draw(ctx, m, &in, false), &s))
+        return false;
+    copy_soup(ctx, s, cap, n_out, xy_out, z_out, attr_out, nrtri::attr_stride(m->mode), q_out);
     return true;
 }
 
@@ -1667,25 +1474,25 @@ Mesh* CreateTexturedColorMesh(i64 nv, const f64* pos, const f64* normal, i64 n, 
 }
 
 // New: DrawTexturedMesh of a textured colour mesh with normals, lit: the light pass of DrawMeshLit runs on the
-// vertex colours (the uv untouched) before anything else reads them, and the rest is DrawTexturedMesh's -- every
-// state of it applies.  A mesh of another kind, or one without normals, latches an error and draws nothing (the
-// last count 0).  With the default lights and colours in [0, 1] the frame is DrawTexturedMesh's bit for bit.
+// vertex colours (the uv untouched; alpha is copied) before anything else reads them, and the rest is
+// DrawTexturedMesh's -- every state of it applies.  A mesh of another kind, or one without normals, latches an
+// error and draws nothing (the last count 0).  With the default lights and colours in [0, 1] the frame is
+// DrawTexturedMesh's bit for bit.
 void DrawTexturedMeshLit(RenderContext* ctx, Mesh* m, Texture* tex, const f64* matrix16, const f64* normal9) {
     const char* what = "DrawTexturedMeshLit";
     NR_CHECK(hipSetDevice(ctx->device));
     ctx->meshLastCount = 0;
     if (!m) { fail(what, "NULL mesh"); return; }
     if (m->mode != nrtri::ATTR_TEXC) { fail(what, "not a textured colour mesh (create it with CreateTexturedColorMesh)"); return; }
-    if (!check_mesh(ctx, m, true, what, true)) return;
+    if (!check_mesh(ctx, m, true, true, what)) return;
     if (!m->lit) { fail(what, "a mesh without normals"); return; }
     if (ctx->recording) nr_settle(ctx);   // recorded draws come first
     if (!nrtri::check_texture(ctx, tex, what)) return;
     if (m->n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
     const Mat3 N = mat3_of(normal9);
     Soup s;
-    if (!uvc_soup(ctx, m, matrix16, &N, &s)) return;
-    ctx->meshLastCount = s.n;
-    if (s.n > 0) draw_uvc_batch(ctx, m, tex, s);
+    if (!build_soup(ctx, single_draw(ctx, m, matrix16, &N), &s)) return;
+    submit(ctx, m, tex, s, mesh_opacity(m), true);
 }
 
 // New: the soup such a draw rasterises -- the draw's own kernels -- in AssembleMeshPerspective's conventions:
@@ -1695,6 +1502,7 @@ bool AssembleTexturedColorMesh(RenderContext* ctx, Mesh* m, const f64* matrix16,
                                f64* xy_out, f64* z_out, f64* uvc_out, f64* q_out, i64* n_out) {
     const char* what = "AssembleTexturedColorMesh";
     NR_CHECK(hipSetDevice(ctx->device));
+    // (check_assemble's checks but for the kind of mesh, which it would reject)
     if (!m) return fail(what, "NULL mesh");
     if (m->mode != nrtri::ATTR_TEXC) return fail(what, "not a textured colour mesh (create it with CreateTexturedColorMesh)");
     if (m->device != ctx->device) return fail(what, "mesh on another device");
@@ -1706,10 +1514,8 @@ bool AssembleTexturedColorMesh(RenderContext* ctx, Mesh* m, const f64* matrix16,
     if (m->n <= 0) return true;
     const Mat3 N = mat3_of(normal9);
     Soup s;
-    if (!uvc_soup(ctx, m, matrix16, lit ? &N : nullptr, &s)) return false;
-    *n_out = s.n;
-    const size_t k = (size_t)(s.n < cap ? s.n : cap);
-    copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {uvc_out, s.attr, 18}, {q_out, s.q, 3}});
+    if (!build_soup(ctx, single_draw(ctx, m, matrix16, lit ? &N : nullptr), &s)) return false;
+    copy_soup(ctx, s, cap, n_out, xy_out, z_out, uvc_out, 18, q_out);
     return true;
 }
 
@@ -1719,14 +1525,7 @@ bool UpdateMeshNormals(Mesh* m, const f64* normal) {
     if (!m->lit) return fail("UpdateMeshNormals", "a mesh without normals (create it with CreateLitMesh)");
     if (m->nv == 0) return true;
     if (!normal) return fail("UpdateMeshNormals", "NULL normals");
-    int prev = 0;
-    NR_CHECK(hipGetDevice(&prev));
-    quiesce(m);
-    hipStream_t s = nr_stream_for(m->device);
-    NR_CHECK(hipMemcpyAsync(m->normal, normal, (size_t)m->nv * 3 * sizeof(f64), hipMemcpyHostToDevice, s));
-    NR_CHECK(hipStreamSynchronize(s));   // caller may reuse its array on return
-    NR_CHECK(hipSetDevice(prev));
-    return true;
+    return update_array(m, m->normal, normal);
 }
 
 bool GetMeshLit(Mesh* m) { return m->lit; }
@@ -1753,16 +1552,13 @@ i64 GetMeshLightCount(RenderContext* ctx) { return ctx->meshLights.nl; }
 void DrawMeshLit(RenderContext* ctx, Mesh* m, const f64* matrix16, const f64* normal9) {
     NR_CHECK(hipSetDevice(ctx->device));
     ctx->meshLastCount = 0;
-    if (!check_mesh(ctx, m, false, "DrawMeshLit") || !check_lit(m, "DrawMeshLit")) return;
+    if (!check_mesh(ctx, m, false, false, "DrawMeshLit") || !check_lit(m, "DrawMeshLit")) return;
     if (ctx->recording) nr_settle(ctx);   // recorded draws come first
     if (m->n <= 0 || ctx->width <= 0 || ctx->height <= 0) return;
     const Mat3 N = mat3_of(normal9);
     Soup s;
-    if (!(clip_stage_on(ctx) ? assemble_clipped(ctx, m, matrix16, &s, false, &N) : assemble_lit(ctx, m, matrix16, N, &s)))
-        return;
-    ctx->meshLastCount = s.n;
-    if (s.n <= 0) return;   // (clipped or culled away)
-    nrtri::draw(ctx, soup_batch(s, m->mode, m->opaque ? nrtri::OPQ_OPAQUE : nrtri::OPQ_BLENDED, nullptr, false));
+    if (!build_soup(ctx, single_draw(ctx, m, matrix16, &N), &s)) return;
+    submit(ctx, m, nullptr, s, mesh_opacity(m), false);
 }
 
 // New: DrawMeshInstanced of a lit mesh: instance k under matrices[k] and the normal matrix normals[k] (K*9; NULL:
@@ -1778,12 +1574,6 @@ void DrawMeshLitInstancedDevice(RenderContext* ctx, Mesh* m, const f64* matrices
     draw_instanced(ctx, m, nullptr, false, matrices, tint, K, true, "DrawMeshLitInstancedDevice", true, normals);
 }
 
-// The mesh checks of the two lit Assemble calls, after check_assemble.
-static bool check_assemble_lit(const Mesh* m, const char* what) {
-    if (m->mode == nrtri::ATTR_TEX) return fail(what, "a textured mesh");
-    return check_lit(m, what);
-}
-
 // New: the soup a DrawMeshLit rasterises under the context's lights, near plane and cull mode -- the draw's own
 // kernels -- in AssembleMeshClipped's conventions (attr x12 Gouraud, x4 flat).  A sync point.
 bool AssembleMeshLit(RenderContext* ctx, Mesh* m, const f64* matrix16, const f64* normal9, i64 cap, f64* xy_out,
@@ -1795,11 +1585,8 @@ bool AssembleMeshLit(RenderContext* ctx, Mesh* m, const f64* matrix16, const f64
     if (m->n <= 0) return true;
     const Mat3 N = mat3_of(normal9);
     Soup s;
-    if (!(clip_stage_on(ctx) ? assemble_clipped(ctx, m, matrix16, &s, false, &N) : assemble_lit(ctx, m, matrix16, N, &s)))
-        return false;
-    *n_out = s.n;
-    const size_t k = (size_t)(s.n < cap ? s.n : cap);
-    copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {attr_out, s.attr, (size_t)nrtri::attr_stride(m->mode)}});
+    if (!build_soup(ctx, single_draw(ctx, m, matrix16, &N), &s)) return false;
+    copy_soup(ctx, s, cap, n_out, xy_out, z_out, attr_out, nrtri::attr_stride(m->mode), nullptr);
     return true;
 }
 
@@ -1815,11 +1602,11 @@ bool AssembleMeshLitInstanced(RenderContext* ctx, Mesh* m, const f64* matrices, 
     if (empty) return true;
     Instances in;
     Soup s;
-    if (!upload_instances(ctx, matrices, tint, K, &in, normals) || !instanced_soup(ctx, m, in, &s, true)) return false;
-    *n_out = s.n;
-    const size_t k = (size_t)(s.n < cap ? s.n : cap);
-    copy_out(ctx, k, {{xy_out, s.xy, 6}, {z_out, s.z, 3}, {attr_out, s.attr, (size_t)nrtri::attr_stride(m->mode)}});
+    if (!upload_instances(ctx, matrices, tint, K, normals, &in) || !build_soup(ctx, instanced_draw(ctx, m, &in, true), &s))
+        return false;
+    copy_soup(ctx, s, cap, n_out, xy_out, z_out, attr_out, nrtri::attr_stride(m->mode), nullptr);
     return true;
 }
 
 }  // extern "C"
+

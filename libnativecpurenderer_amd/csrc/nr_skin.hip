@@ -28,7 +28,6 @@
 
 #include <cstdint>
 #include <cstring>
-#include <string>
 
 struct MeshSkin {
     i64 nv = 0, nb = 0;
@@ -134,11 +133,6 @@ __global__ __launch_bounds__(256) void k_mesh_skin(const f64* __restrict__ bpos,
     }
 }
 
-bool fail(const char* what, const char* why) {
-    nr_set_error_msg((std::string(what) + ": " + why).c_str());
-    return false;
-}
-
 void free_skin(MeshSkin* s) {
     for (void* p : {(void*)s->pos, (void*)s->normal, (void*)s->joints, (void*)s->weights, (void*)s->palette})
         if (p) NR_CHECK(hipFree(p));
@@ -175,13 +169,9 @@ bool pose(RenderContext* ctx, Mesh* m, MeshSkin* s, const f64* palette, bool onD
     const bool lds = s->variant != 1 && s->nb <= (i64)SKIN_LDS_MAX_BONES;
     const auto kernel = lds ? (nrm ? k_mesh_skin<true, true> : k_mesh_skin<false, true>)
                             : (nrm ? k_mesh_skin<true, false> : k_mesh_skin<false, false>);
-    hipEvent_t a, b;
-    nr_timing_begin(ctx, NRK_MESH_SKIN, &a, &b);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((s->nv + 255) / 256)), dim3(256), 0, ctx->stream, s->pos, s->normal,
-                       reinterpret_cast<const uint4*>(s->joints), reinterpret_cast<const double2*>(s->weights),
-                       reinterpret_cast<const double2*>(dpal), (u32)s->nb, s->nv, m->pos, m->normal);
-    NR_CHECK(hipGetLastError());
-    nr_timing_end(ctx, NRK_MESH_SKIN, a, b);
+    mesh_launch(ctx, NRK_MESH_SKIN, kernel, s->nv, s->pos, s->normal, reinterpret_cast<const uint4*>(s->joints),
+                reinterpret_cast<const double2*>(s->weights), reinterpret_cast<const double2*>(dpal), (u32)s->nb, s->nv,
+                m->pos, m->normal);
     return true;
 }
 
