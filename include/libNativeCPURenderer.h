@@ -420,6 +420,14 @@ i64 GetKeyCachedBatchCount(RenderContext* ctx);                          /* NEW 
 bool GetKeyCacheTotals(RenderContext* ctx, i64* out3);                   /* NEW (testing): the key cache's cached tiles, key
                                                                             items, bytes of keys; false: none.  Waits for
                                                                             the device */
+void SetKeyIndex(RenderContext* ctx, i64 mode);                          /* NEW: a cached Gouraud draw shaded from its tiles'
+                                                                            winner index, 0 auto (on), 2 off (the cached keys
+                                                                            alone; the index is kept) */
+i64 GetKeyIndexedBatchCount(RenderContext* ctx);                         /* NEW (testing): of the cached batches, shaded from
+                                                                            the key index */
+bool GetKeyIndexTotals(RenderContext* ctx, i64* out4);                   /* NEW (testing): the key index's tiles, staged
+                                                                            winners, directly loaded pixels, bytes; false:
+                                                                            none.  Waits for the device */
 bool GetScheduleTotals(RenderContext* ctx, i64* out4);                   /* NEW (testing): the warm schedule's pairs, work
                                                                             items, split-tile slices, dense tiles; false: none */
 void SetWarmFaultInjection(RenderContext* ctx, i64 mode);                /* NEW (testing): fault in the next warm batch

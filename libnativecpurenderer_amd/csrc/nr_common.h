@@ -294,11 +294,18 @@ struct TriScratch {
         KeyStage keyState = KeyStage::None;
         u32 ktiles = 0, knitems = 0;                     // (Slotted and later) cached tiles, items
         hipEvent_t evKey = nullptr;                      // the capture frame is done (main stream)
-        void drop_visible() { visState = VisStage::None; replanState = ReplanStage::None; keyState = KeyStage::None; }
+        // key index (nr_free.h KeyIndex): per cached slot the pixels' dense winner numbers, the staged winners
+        // and their count, built once right after the capture frame (k_key_index; evKey covers it) -- cached
+        // Gouraud batches are then shaded by k_keys_idx.  No memory: the generation stays on k_keys
+        DevArray<unsigned char> kindex;                  // ktiles x (u16 idx[TH*TW]) | ktiles x (u32 win[KI_RT]) | ktiles x (u32 cnt[2])
+        bool kindexed = false;                           // this generation's index is enqueued (with its capture frame)
+        void drop_visible() {
+            visState = VisStage::None; replanState = ReplanStage::None; keyState = KeyStage::None; kindexed = false;
+        }
         void release() {
             off.release(); items.release(); off2.release();
             vlist.release(); vcnt.release(); vmask.release(); vitems.release();
-            kkeys.release(); kitems.release(); ktile.release();
+            kkeys.release(); kitems.release(); ktile.release(); kindex.release();
             if (kplan) NR_CHECK(hipFree(kplan));
             hkplan.release();
             if (evKey) NR_CHECK(hipEventDestroy(evKey));
@@ -321,6 +328,8 @@ struct TriScratch {
     int replanMode = 0;                     // visible plan: 0 automatic (on), 2 off (SetVisibleReplan)
     u64 keyCachedBatches = 0;               // of the pruned ones, shaded from the key cache (GetKeyCachedBatchCount)
     int keyMode = 0;                        // key cache: 0 automatic (on), 2 off (SetKeyCache)
+    u64 keyIndexedBatches = 0;              // of the cached ones, shaded from the key index (GetKeyIndexedBatchCount)
+    int keyIndexMode = 0;                   // key index: 0 automatic (on), 2 off (SetKeyIndex)
     std::vector<u64> looseBanned;           // buffers whose loose binning overflowed a tile: not binned loose again
     // warm-batch checks (k_vis WarmCheck): host-mapped word a raster sets when
     // a warm batch failed them (1 binning check, 2 token timeout), read by

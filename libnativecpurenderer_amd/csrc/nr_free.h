@@ -128,6 +128,20 @@ struct WarmCheck {
 // from 512 to 320.
 constexpr u32 WIDE_HEAVY = 320;
 
+// The key index of a key cache (k_key_index, once per generation, right after the capture frame): per cached
+// slot s the dense number of every pixel's winner among the tile's staged winners, those winners' ids and their
+// count -- a function of the slot's keys alone, so k_keys_idx (cached Gouraud batches) neither de-duplicates a
+// tile's winners nor probes for a pixel's record.
+constexpr int KI_RT = 280;                   // staged winners per tile (whatever the attribute mode)
+constexpr unsigned short KI_NONE = 0xFFFF;   // the pixel has no winner ((u32)key == 0, or it lies past the frame edge)
+constexpr unsigned short KI_DIRECT = 0xFFFE; // its winner is not staged: the record is loaded directly
+struct KeyIndex {
+    const unsigned short* idx = nullptr;   // [s][TH * TW], p = ly * TW + lx: d < cnt[2 s], KI_NONE or KI_DIRECT
+    const u32* win = nullptr;              // [s][KI_RT]: the staged winners' ids (1-based, as the keys'), dense order
+    const u32* cnt = nullptr;              // [s][2]: min(distinct winners, KI_RT), KI_DIRECT pixels
+};
+constexpr size_t KI_SLOT_BYTES = (size_t)TH * TW * 2 + (size_t)KI_RT * 4 + 8;   // of the index, per cached tile
+
 // The k_vis inputs of one batch: its work items, pair list and plan totals
 // (a binning set's, or the warm schedule's).
 struct VisArgs {
@@ -141,6 +155,8 @@ struct VisArgs {
     const u64* kkeys = nullptr;
     const uint4* kitems = nullptr;
     const u32* kplan = nullptr;
+    // key index (below): non-null, a cached Gouraud batch is shaded by k_keys_idx from the slots' winner index
+    KeyIndex kindex;
 };
 
 // ---- launch functions ---------------------------------------------------
@@ -174,9 +190,12 @@ void launch_key_plan(const u32* vcnt, int ntiles, int tiles_x, int period, u64 m
                      u32* totals, u64* host_totals, u32 seq, hipStream_t s, hipEvent_t stop);
 
 // nr_free_vis.hip
+// the key index of `tiles` cached slots (one workgroup each) from their captured keys; W, H, tiles_x: the frame's
+void launch_key_index(const uint4* kitems, const u64* kkeys, u32 tiles, unsigned short* idx, u32* win, u32* cnt, i64 W,
+                      i64 H, int tiles_x, hipStream_t s);
 // k_vis' ZMODE of a batch: 0 no test, 1 LESS + write, 2 LESS without write
 int z_mode(const FrameParams& fp);
-// k_vis (or, for a batch shaded from the key cache, k_keys) over `grid` workgroups
+// k_vis (or, for a batch shaded from the key cache, k_keys / k_keys_idx) over `grid` workgroups
 void launch_vis_any(const FrameParams& fp, const TriScratch& sc, const BatchTotals& t, const VisArgs& va, u32 grid,
                     hipStream_t s, hipEvent_t start, hipEvent_t stop);
 

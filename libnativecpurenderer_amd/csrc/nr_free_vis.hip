@@ -1046,6 +1046,278 @@ __global__ __launch_bounds__(NT) void k_keys(const FrameParams fp, const uint4* 
     raster_stamp_end(fp);
 }
 
+// ---- key index ----------------------------------------------------------------
+// What shade_tile's pass 1 finds out about a tile -- its distinct winners, a
+// dense number for each -- depends on the tile's keys alone, and a key cache's
+// keys never change.  k_key_index finds it once per generation, right after the
+// capture frame (one 256-thread workgroup per cached slot), and k_keys_idx then
+// shades a cached Gouraud tile without a hash table: keys and index entries
+// loaded together, depths stored from the keys in registers, one record per
+// staged winner (ids from the slot's winner list), one barrier, and every pixel
+// reads its record by the dense number the index gives it.
+//
+// The build is deterministic: the winners are numbered by their first pixel in
+// p order (p = ly * TW + lx), so the staged ones of a tile with more than KI_RT
+// are those whose first pixel comes first.  The table has two slots per pixel
+// and is probed without a limit, so cnt is exactly min(distinct, KI_RT).
+constexpr int KI_HS = 2 * TH * TW;   // hash slots of k_key_index (power of two)
+constexpr int KI_NT = 256;           // its workgroup: thread t numbers pixels [t * KI_PPT, (t + 1) * KI_PPT)
+constexpr int KI_PPT = TH * TW / KI_NT;
+static_assert(TH * TW < KI_DIRECT, "a dense number fits the index entry");
+
+__global__ __launch_bounds__(KI_NT) void k_key_index(const uint4* __restrict__ items, const u64* __restrict__ kkeys,
+                                                     u32 tiles, unsigned short* __restrict__ kidx, u32* __restrict__ kwin,
+                                                     u32* __restrict__ kcnt, i64 W, i64 H, int tiles_x) {
+    __shared__ u32 ht[KI_HS];               // winner ids (0: free)
+    __shared__ u32 hfirst[KI_HS];           // per table slot: the winner's first pixel
+    __shared__ unsigned short hd[KI_HS];    // ... and then its dense number
+    __shared__ u32 scan[KI_NT];
+    __shared__ u32 nDirect;
+    const u32 slot = blockIdx.x;
+    if (slot >= tiles) return;
+    const int tid = threadIdx.x;
+    const int tile = (int)items[slot].x;    // (a cached item's slot is its index, k_key_plan)
+    const int tx = tile % tiles_x, ty = tile / tiles_x;
+    const i64 x0 = (i64)tx * TW, y0 = (i64)ty * TH;
+    const int wlim = (int)(W - x0 < TW ? W - x0 : TW);
+    const int hlim = (int)(H - y0 < TH ? H - y0 : TH);
+    for (int i = tid; i < KI_HS; i += KI_NT) { ht[i] = 0; hfirst[i] = ~0u; }
+    if (tid == 0) nDirect = 0;
+    __syncthreads();
+    const u64* const src = kkeys + (size_t)slot * (TH * TW);
+    u32 id[KI_PPT], hs[KI_PPT];
+#pragma unroll
+    for (int k = 0; k < KI_PPT; ++k) {
+        const int p = tid * KI_PPT + k, lx = p & (TW - 1), ly = p / TW;
+        id[k] = lx < wlim && ly < hlim ? (u32)src[p] : 0u;
+        hs[k] = 0;
+        if (!id[k]) continue;
+        u32 h = (id[k] * 2654435761u) >> (32 - __builtin_ctz(KI_HS));
+        for (;; h = (h + 1) & (KI_HS - 1)) {   // (ends: at most TH * TW ids in twice as many slots)
+            const u32 cur = ht[h];
+            if (cur == id[k]) break;
+            if (cur == 0) {
+                const u32 old = atomicCAS(&ht[h], 0u, id[k]);
+                if (old == 0 || old == id[k]) break;
+            }
+        }
+        hs[k] = h;
+        atomicMin(&hfirst[h], (u32)p);
+    }
+    __syncthreads();
+    // the winners' dense numbers: the rank of their first pixels
+    u32 mine = 0;
+#pragma unroll
+    for (int k = 0; k < KI_PPT; ++k)
+        if (id[k] && hfirst[hs[k]] == (u32)(tid * KI_PPT + k)) ++mine;
+    scan[tid] = mine;
+    __syncthreads();
+    for (int o = 1; o < KI_NT; o <<= 1) {   // inclusive scan
+        const u32 v = tid >= o ? scan[tid - o] : 0u;
+        __syncthreads();
+        scan[tid] += v;
+        __syncthreads();
+    }
+    u32 d = scan[tid] - mine;
+    const u32 distinct = scan[KI_NT - 1];
+#pragma unroll
+    for (int k = 0; k < KI_PPT; ++k) {
+        if (!id[k] || hfirst[hs[k]] != (u32)(tid * KI_PPT + k)) continue;
+        hd[hs[k]] = (unsigned short)d;
+        if (d < (u32)KI_RT) kwin[(size_t)slot * KI_RT + d] = id[k];
+        ++d;
+    }
+    __syncthreads();
+    u32 direct = 0;
+#pragma unroll
+    for (int k = 0; k < KI_PPT; ++k) {
+        unsigned short v = KI_NONE;
+        if (id[k]) {
+            v = hd[hs[k]];
+            if (v >= KI_RT) { v = KI_DIRECT; ++direct; }
+        }
+        kidx[(size_t)slot * (TH * TW) + tid * KI_PPT + k] = v;
+    }
+    if (direct) atomicAdd(&nDirect, direct);
+    __syncthreads();
+    if (tid == 0) {
+        kcnt[2 * (size_t)slot] = distinct < (u32)KI_RT ? distinct : (u32)KI_RT;
+        kcnt[2 * (size_t)slot + 1] = nDirect;
+    }
+}
+
+// The steady kernel of a cached Gouraud batch whose generation has its index
+// (launch_vis): k_keys' items, grid and empty-tile path; a cached item as the
+// head comment above says.  Every value is formed by nr_tri_shade.h's helpers
+// as shade_tile forms it, so a frame is the one k_keys gives, bit for bit.
+// LDS: the KI_RT records alone (35 KB: four 256-thread workgroups per CU).
+constexpr int KI_OVF_Q = 1;   // directly loaded records in flight per thread (their ids come from the keys again)
+template <int ZMODE, int MODEW, int NT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) void k_keys_idx(
+    const FrameParams fp, const uint4* __restrict__ items, const u64* __restrict__ kkeys, const u32* __restrict__ kplan,
+    const unsigned short* __restrict__ kidx, const u32* __restrict__ kwin, const u32* __restrict__ kcnt) {
+    constexpr int MODE = attr_base(MODEW);
+    static_assert(MODE == ATTR_GOURAUD && !attr_wraps(MODEW), "Gouraud batches only");
+    constexpr int REC = RecLen<MODE>::REC;
+    constexpr int PPT = TH * TW / NT;
+    static_assert(PPT <= 32, "overflow bitmask");
+    __shared__ __attribute__((aligned(16))) f64 rec[KI_RT * REC];
+    raster_stamp_begin(fp);
+    const u32 nitems = kplan[1];
+    uint4 dnext = blockIdx.x < nitems ? items[blockIdx.x] : make_uint4(0, 0, 0, 0);
+#if NR_PROBE
+    const int tid = threadIdx.x;
+    u64 pr_t0 = 0;
+    u32 pr_item = ~0u;
+    uint4 pr_d = make_uint4(0, 0, 0, 0);
+#endif
+    for (u32 item = blockIdx.x; item < nitems; item += gridDim.x) {
+        const uint4 d = dnext;
+        if (item + gridDim.x < nitems) dnext = items[item + gridDim.x];
+#if NR_PROBE
+        if (tid == 0) {   // (the record's list range: [0, kept pairs))
+            const u64 now = __builtin_amdgcn_s_memrealtime();
+            if (pr_item != ~0u) probe_item(pr_item, pr_d, pr_t0, now, NT);
+            pr_t0 = now; pr_item = item; pr_d = make_uint4(d.x, 0u, d.z, 1u);
+        }
+#endif
+        __syncthreads();   // (the last item's pixels have read its records)
+        const int itid = opaque_tid();
+        const int tile = (int)d.x;
+        const int tx = tile % fp.tiles_x, ty = tile / fp.tiles_x;
+        const i64 x0 = (i64)tx * TW, y0 = (i64)ty * TH;
+        const int wlim = (int)(fp.W - x0 < TW ? fp.W - x0 : TW);
+        const int hlim = (int)(fp.H - y0 < TH ? fp.H - y0 : TH);
+        if (d.y == ~0u) {   // no kept pair: only the pending clears (as k_vis)
+            if (fp.tileStamp) {
+                if (fp.frameU8 && fp.pendColor) {
+                    const f64 v = fp.pendColorValue;
+                    for (int p = itid; p < TH * TW; p += NT) {
+                        const int lx = p & (TW - 1), ly = p / TW;
+                        if (lx < wlim && ly < hlim)
+                            store_frame_out(fp, (y0 + ly) * fp.W + x0 + lx, x0 + lx, y0 + ly, v, v, v, v);
+                    }
+                }
+                if (itid == 0) fp.tileStamp[tile] = fp.tileEpoch;
+                continue;
+            }
+            for (int p = itid; p < TH * TW; p += NT) {
+                const int lx = p & (TW - 1), ly = p / TW;
+                if (lx < wlim && ly < hlim)
+                    store_clear<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, x0 + lx, y0 + ly);
+            }
+            continue;
+        }
+        // every load of the item's first round in flight together: the keys, the
+        // two winners whose records this thread builds, the index entries
+        const size_t slot = (u32)__builtin_amdgcn_readfirstlane((int)d.y);   // (uniform: the count is a scalar load)
+        const u64* const src = kkeys + slot * (TH * TW);
+        const unsigned short* const six = kidx + slot * (TH * TW);
+        const u32* const swin = kwin + slot * KI_RT;
+        u64 kv[PPT];
+        unsigned short di[PPT];
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) kv[k] = src[itid + k * NT];
+        // (unconditional loads from in-range addresses, as k_vis' chunk loads: a conditional load makes the
+        // compiler wait for everything in flight on the spot.  Entries past the slot's count are never used)
+        const u32 w0 = swin[itid < KI_RT ? itid : 0];
+        const u32 w1 = swin[itid + NT < KI_RT ? itid + NT : 0];
+        const u32 U = min(kcnt[2 * slot], (u32)KI_RT);
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) di[k] = six[itid + k * NT];
+        NR_PROBE_STAMP(1);
+        NR_PROBE_STAMP(2);
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) {
+            const int p = itid + k * NT, lx = p & (TW - 1), ly = p / TW;
+            if (lx >= wlim || ly >= hlim) continue;
+            store_depth<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, kv[k]);
+        }
+        NR_PROBE_STAMP(4);
+        static_assert(KI_RT <= 2 * NT, "two winners per thread cover the staged records");
+        {   // one record per staged winner, every thread's loads issued (a thread past the count reads triangle
+            // 0's data and builds nothing); the few winners past NT (a 256-thread workgroup's last 24) in a
+            // second round
+            const u32 u = (u32)itid;
+            RecordSrc<MODE> s0;
+            load_record_src<MODE>(fp, u < U ? (i64)w0 - 1 : 0, s0);
+            if (u < U) build_record<MODE>(fp, s0, rec + u * REC);
+            if (U > (u32)NT && u + NT < U) {
+                RecordSrc<MODE> s1;
+                load_record_src<MODE>(fp, (i64)w1 - 1, s1);
+                build_record<MODE>(fp, s1, rec + (u + NT) * REC);
+            }
+        }
+        __syncthreads();
+        NR_PROBE_STAMP(5);
+        const TexView& tv = fp.tex;
+        u32 ovf = 0;   // bit k: pixel k's winner is not staged
+#pragma unroll 1
+        for (int k = 0; k < PPT; ++k) {
+            const int p = itid + k * NT, lx = p & (TW - 1), ly = p / TW;
+            if (lx >= wlim || ly >= hlim) continue;
+            const i64 px = x0 + lx, py = y0 + ly;
+            const i64 gp = py * fp.W + px;
+            u32 dn = KI_NONE;
+#pragma unroll
+            for (int q = 0; q < PPT; ++q)
+                if (q == k) dn = di[q];   // static register index
+            if (dn == KI_NONE) {
+                if (fp.pendColor) {
+                    const f64 v = fp.pendColorValue;
+                    store_colour(fp, gp, px, py, v, v, v, v);
+                }
+                continue;
+            }
+            if (dn >= U) {   // KI_DIRECT
+                ovf |= 1u << k;
+                continue;
+            }
+            f64 cr, cg, cb, ca;
+            record_colour<MODE>(tv, rec + dn * REC, px, py, cr, cg, cb, ca);
+            apply_winner(fp, gp, cr, cg, cb, ca);
+            store_colour(fp, gp, px, py, cr, cg, cb, ca);
+        }
+        // pixels whose winner is not staged (shade_tile's pass 3b), KI_OVF_Q at
+        // a time: their ids' loads in flight together, then their records'
+#pragma unroll 1
+        while (ovf) {
+            int kq[KI_OVF_Q];
+            u32 wid[KI_OVF_Q];
+            RecordSrc<MODE> rs[KI_OVF_Q];
+#pragma unroll
+            for (int j = 0; j < KI_OVF_Q; ++j) {
+                kq[j] = -1;
+                wid[j] = 0;
+                if (!ovf) continue;
+                kq[j] = __builtin_ctz(ovf);
+                ovf &= ovf - 1;
+                wid[j] = (u32)src[itid + kq[j] * NT];   // (the key again: eight ids kept live measured no faster)
+            }
+#pragma unroll
+            for (int j = 0; j < KI_OVF_Q; ++j)
+                if (kq[j] >= 0) load_record_src<MODE>(fp, (i64)wid[j] - 1, rs[j]);
+#pragma unroll
+            for (int j = 0; j < KI_OVF_Q; ++j) {
+                if (kq[j] < 0) continue;
+                const int p = itid + kq[j] * NT, lx = p & (TW - 1), ly = p / TW;
+                const i64 px = x0 + lx, py = y0 + ly;
+                const i64 gp = py * fp.W + px;
+                f64 r[REC];
+                build_record<MODE>(fp, rs[j], r);
+                f64 cr, cg, cb, ca;
+                record_colour<MODE>(tv, r, px, py, cr, cg, cb, ca);
+                apply_winner(fp, gp, cr, cg, cb, ca);
+                store_colour(fp, gp, px, py, cr, cg, cb, ca);
+            }
+        }
+    }
+#if NR_PROBE
+    if (tid == 0 && pr_item != ~0u) probe_item(pr_item, pr_d, pr_t0, __builtin_amdgcn_s_memrealtime(), NT);
+#endif
+    raster_stamp_end(fp);
+}
+
 // The instance of a batch among its four shapes -- wide workgroups (never a counting batch) or not, the flattened
 // raster or not -- MARK: a marking frame's.
 template <int Z, bool C, int G, bool MARK>
@@ -1085,6 +1357,14 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& 
     if constexpr (!C && Z != 2 && attr_base(G) != ATTR_TEX_PERSP_BIL && !attr_modulated(attr_base(G))) {
         if (va.kkeys) {
             const bool w = wide || keys_wide_forced();
+            if constexpr (G == ATTR_GOURAUD) {
+                if (va.kindex.idx) {   // (the generation has its index, and SetKeyIndex is on: pruned_enqueue)
+                    hipExtLaunchKernelGGL(w ? k_keys_idx<Z, G, 2 * VWG> : k_keys_idx<Z, G, VWG>, dim3(grid),
+                                          dim3(w ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.kitems, va.kkeys, va.kplan,
+                                          va.kindex.idx, va.kindex.win, va.kindex.cnt);
+                    return;
+                }
+            }
             hipExtLaunchKernelGGL(w ? k_keys<Z, G, 2 * VWG> : k_keys<Z, G, VWG>, dim3(grid), dim3(w ? 2 * VWG : VWG), 0, s,
                                   start, stop, 0, fp, va.kitems, va.kkeys, va.kplan);
             return;
@@ -1104,6 +1384,12 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& 
 
 // k_vis' ZMODE of a batch: 0 no test, 1 LESS + write, 2 LESS without write
 int z_mode(const FrameParams& fp) { return fp.depthTest ? (fp.depthWrite ? 1 : 2) : 0; }
+
+void launch_key_index(const uint4* kitems, const u64* kkeys, u32 tiles, unsigned short* idx, u32* win, u32* cnt, i64 W,
+                      i64 H, int tiles_x, hipStream_t s) {
+    if (!tiles) return;
+    hipLaunchKernelGGL(k_key_index, dim3(tiles), dim3(KI_NT), 0, s, kitems, kkeys, tiles, idx, win, cnt, W, H, tiles_x);
+}
 
 void launch_vis_any(const FrameParams& fp, const TriScratch& sc, const BatchTotals& t, const VisArgs& va,
                     u32 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop) {

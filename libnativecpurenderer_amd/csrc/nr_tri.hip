@@ -651,6 +651,21 @@ bool GetKeyCacheTotals(RenderContext* ctx, i64* out) {
     NR_CHECK(hipSetDevice(ctx->device));
     return nrtri::key_cache_totals(ctx, out);
 }
+// New (testing / A-B measurement): the key index -- a cached Gouraud draw shaded
+// from the per-tile winner index built with the capture frame (k_keys_idx) -- 0
+// automatic (on), 2 off (such draws run k_keys; the index is kept and used again
+// at once after a switch back to 0).
+void SetKeyIndex(RenderContext* ctx, i64 mode) { ctx->tri.keyIndexMode = mode == 2 ? 2 : 0; }
+// New (testing): of the cached batches, those shaded from the key index.
+i64 GetKeyIndexedBatchCount(RenderContext* ctx) { return (i64)ctx->tri.keyIndexedBatches; }
+// New (testing): totals of the current key index -- out[0..3] = indexed tiles,
+// staged winners (the sum of the tiles' counts), pixels whose winner is not
+// staged, bytes of the index; false (and zeros) while the generation has none.
+// Waits for the device.
+bool GetKeyIndexTotals(RenderContext* ctx, i64* out) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    return nrtri::key_index_totals(ctx, out);
+}
 // New (testing): totals of the context's warm schedule -- out[0..3] = (tile,
 // triangle) pairs, k_vis work items, slices of split tiles, dense tiles;
 // false (and zeros) when it has none.

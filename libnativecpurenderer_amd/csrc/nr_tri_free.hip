@@ -697,6 +697,27 @@ static bool key_totals_seen(const TriScratch::Schedule& S, u32* tiles, u32* item
     return true;
 }
 
+// Does a cached Gouraud batch run k_keys_idx?  SetKeyIndex 2: no; 0 (the default): yes, unless NR_KEY_INDEX=2 in
+// the environment (A/B runs against k_keys in one build, profiles/key_index/bench_py_ab.txt).
+static bool key_index_wanted(int mode) {
+    static const bool envOff = [] {
+        const char* e = getenv("NR_KEY_INDEX");
+        return e && atoi(e) == 2;
+    }();
+    return mode != 2 && !envOff;
+}
+
+// The three arrays of the generation's key index in S.kindex (ktiles slots each).
+static KeyIndex key_index_view(const TriScratch::Schedule& S) {
+    const size_t tiles = std::max<size_t>(S.ktiles, 1);
+    unsigned char* const b = S.kindex.p;
+    KeyIndex ki;
+    ki.idx = reinterpret_cast<const unsigned short*>(b);
+    ki.win = reinterpret_cast<const u32*>(b + tiles * (size_t)(TH * TW) * 2);
+    ki.cnt = ki.win + tiles * (size_t)KI_RT;
+    return ki;
+}
+
 static void key_plan(RenderContext* ctx, const FrameParams& fp, int ntiles) {
     auto& S = ctx->tri.sched;
     const size_t tn = std::max<size_t>((size_t)ntiles, 1);
@@ -738,6 +759,20 @@ static int key_cache_step(RenderContext* ctx, const FrameParams& fp, int zm, int
             }
             S.kkeys.cap = need;
         }
+        // the key index beside the keys.  No room: not an error and nothing latched -- the generation's cached
+        // batches run k_keys
+        S.kindexed = false;
+        const size_t ineed = std::max<size_t>(S.ktiles, 1) * KI_SLOT_BYTES;
+        if (S.kindex.needs(ineed)) {
+            NR_CHECK(hipStreamSynchronize(ctx->stream));   // (as key_plan)
+            S.kindex.release();
+            if (hipMalloc((void**)&S.kindex.p, ineed) == hipSuccess) {
+                S.kindex.cap = ineed;
+            } else {
+                (void)hipGetLastError();
+                S.kindex.p = nullptr;
+            }
+        }
         // the slots' address into the capture table, in stream order before the capture frame (an 8-byte copy
         // from pageable memory is staged before the call returns)
         NR_CHECK(hipMemcpyAsync(S.ktile.p, &S.kkeys.p, sizeof(u64*), hipMemcpyHostToDevice, ctx->stream));
@@ -761,6 +796,9 @@ static int key_cache_step(RenderContext* ctx, const FrameParams& fp, int zm, int
     va.kkeys = S.kkeys;
     va.kitems = S.kitems;
     va.kplan = S.kplan;
+    // a Gouraud batch of a generation that has its index: k_keys_idx, when SetKeyIndex says so
+    if (S.kindexed && fp.src.mode == ATTR_GOURAUD && key_index_wanted(sc.keyIndexMode))
+        va.kindex = key_index_view(S);
     return 2;
 }
 
@@ -814,6 +852,14 @@ static void pruned_enqueue(RenderContext* ctx, const FrameParams& fp, TriScratch
     if (kstep == 1) fpk.kcap = reinterpret_cast<const KeyCaptureTable*>(S.ktile.p);
     vis_tail(ctx, F, fpk, va, grid);
     if (kstep == 1) {   // the capture frame: its end, for key_cache_step
+        if (S.kindex.p && S.kindex.cap >= std::max<size_t>(S.ktiles, 1) * KI_SLOT_BYTES) {
+            // the key index from the keys just captured, in stream order: the event below covers both
+            const KeyIndex ki = key_index_view(S);
+            launch_key_index(S.kitems, S.kkeys, S.ktiles, const_cast<unsigned short*>(ki.idx), const_cast<u32*>(ki.win),
+                             const_cast<u32*>(ki.cnt), fp.W, fp.H, fp.tiles_x, sa);
+            NR_CHECK(hipGetLastError());
+            S.kindexed = true;
+        }
         if (!S.evKey) S.evKey = sync_event();
         NR_CHECK(hipEventRecord(S.evKey, sa));
         S.keyState = KeyStage::Capturing;
@@ -822,6 +868,7 @@ static void pruned_enqueue(RenderContext* ctx, const FrameParams& fp, TriScratch
     ++sc.reusedBatches;
     ++sc.prunedBatches;
     if (kstep == 2) ++sc.keyCachedBatches;
+    if (kstep == 2 && va.kindex.idx) ++sc.keyIndexedBatches;
 }
 
 // List reuse: the schedule's last warm binning left its pair list in set
@@ -1192,6 +1239,25 @@ bool key_cache_totals(RenderContext* ctx, i64* out) {
     u32 tiles = 0, items = 0;
     if (!key_totals_seen(S, &tiles, &items)) return false;
     out[0] = tiles; out[1] = items; out[2] = (i64)tiles * (TH * TW) * (i64)sizeof(u64);
+    return true;
+}
+
+// Totals of the generation's key index -- indexed tiles, staged winners (the
+// sum of the slots' counts), KI_DIRECT pixels, bytes of the index -- false while
+// the generation has none (waits for the main stream).
+bool key_index_totals(RenderContext* ctx, i64* out) {
+    auto& S = ctx->tri.sched;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!S.valid || S.visState != VisStage::Pruned || !S.kindexed ||
+        (S.keyState != KeyStage::Capturing && S.keyState != KeyStage::Cached))
+        return false;
+    NR_CHECK(hipStreamSynchronize(ctx->stream));
+    std::vector<u32> cnt(2 * (size_t)S.ktiles);
+    if (S.ktiles)
+        NR_CHECK(hipMemcpy(cnt.data(), key_index_view(S).cnt, cnt.size() * sizeof(u32), hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < S.ktiles; ++s) { out[1] += cnt[2 * s]; out[2] += cnt[2 * s + 1]; }
+    out[0] = S.ktiles;
+    out[3] = (i64)S.ktiles * (i64)KI_SLOT_BYTES;
     return true;
 }
 

@@ -970,6 +970,25 @@ class RenderContext:
             return None
         return {"tiles": out[0], "items": out[1], "bytes": out[2]}
 
+    def set_key_index(self, mode: int):
+        """The key index -- a cached Gouraud draw shaded from its tiles' winner
+        index, built with the capture frame: 0 automatic (on), 2 off (the
+        cached keys alone; the index is kept)."""
+        lib.SetKeyIndex(self._ptr, int(mode))
+
+    def key_indexed_batch_count(self) -> int:
+        """Of the cached batches, those shaded from the key index."""
+        return lib.GetKeyIndexedBatchCount(self._ptr)
+
+    def key_index_totals(self) -> typing.Optional[dict]:
+        """Testing: totals of the current key index -- indexed tiles, staged
+        winners, pixels whose winner is loaded directly, bytes -- or None when
+        there is none.  Waits for the device."""
+        out = (ctypes.c_long * 4)()
+        if not lib.GetKeyIndexTotals(self._ptr, out):
+            return None
+        return {"tiles": out[0], "staged": out[1], "direct": out[2], "bytes": out[3]}
+
     def schedule_totals(self) -> typing.Optional[dict]:
         """Testing: totals of the context's warm schedule -- (tile, triangle)
         pairs, k_vis work items, slices of split tiles, dense tiles -- or None
