@@ -428,7 +428,15 @@ i64 GetKeyIndexedBatchCount(RenderContext* ctx);                         /* NEW 
 bool GetKeyIndexTotals(RenderContext* ctx, i64* out4);                   /* NEW (testing): the key index's tiles, staged
                                                                             winners, directly loaded pixels, bytes; false:
                                                                             none.  Waits for the device */
-bool GetScheduleTotals(RenderContext* ctx, i64* out4);                   /* NEW (testing): the warm schedule's pairs, work
+void SetDeferredStores(RenderContext* ctx, i64 mode);                    /* NEW: a cached Gouraud draw that writes the frame
+                                                                            output leaves its f64 and depth stores pending
+                                                                            until the buffers are used: 0 auto (only after
+                                                                            frames whose values nothing needed), 1 always,
+                                                                            2 off */
+void GetDeferredStoreCounts(RenderContext* ctx, i64* out4);              /* NEW (testing): batches deferred, resolves
+                                                                            launched, records superseded unread, the rule's
+                                                                            threshold.  Host state: no device wait */
+bool GetScheduleTotals(RenderContext* ctx, i64* out4);                  /* NEW (testing): the warm schedule's pairs, work
                                                                             items, split-tile slices, dense tiles; false: none */
 void SetWarmFaultInjection(RenderContext* ctx, i64 mode);                /* NEW (testing): fault in the next warm batch
                                  1 range overflow, 2 withheld token, 3 dropped pairs, 4 binning delayed past the

@@ -104,6 +104,23 @@ void nr_settle_all() {
     NR_CHECK(hipSetDevice(prev));
 }
 
+// The pending values of every live context whose deferred record was formed from `tb` (DestroyTriangleBuffer).
+void nr_deferred_resolve_buffer(const TriangleBuffer* tb) {
+    std::vector<RenderContext*> v;
+    {
+        std::lock_guard<std::mutex> lk(g_ctx_mu);
+        v = g_ctxs;
+    }
+    int prev = 0;
+    NR_CHECK(hipGetDevice(&prev));
+    for (RenderContext* c : v)
+        if (c->tri.deferred.live() && c->tri.deferred.tb == tb) {
+            NR_CHECK(hipSetDevice(c->device));
+            nr_deferred_resolve(c, true, true);
+        }
+    NR_CHECK(hipSetDevice(prev));
+}
+
 static int current_device() {
     int d = 0;
     NR_CHECK(hipGetDevice(&d));
@@ -382,6 +399,7 @@ void DestroyRenderContext(RenderContext* ctx) {
     NR_CHECK(hipSetDevice(ctx->device));
     nr_free_commands(ctx);   // queued draws of a destroyed context are dead
     nr_settle(ctx);
+    nr_deferred_free(ctx);   // (so are a deferred batch's pending values)
     {
         std::lock_guard<std::mutex> lk(g_ctx_mu);
         for (size_t i = 0; i < g_ctxs.size(); ++i)
@@ -423,7 +441,8 @@ void ResizeRenderContext(RenderContext* ctx, i64 width, i64 height) {
     }
     ctx->pendColor = ctx->pendDepth = false;
     ctx->tileColor = ctx->tileDepth = false;
-    ctx->tri.sched.listSet = -1;   // (list reuse: a resized context bins again, and marks its winners again)
+    nr_deferred_drop(ctx);   // (a deferred batch's pending values go with the contents)
+    ctx->tri.sched.listSet = -1;  // (list reuse: a resized context bins again, and marks its winners again)
     ctx->tri.sched.drop_visible();
     i64 n = GetBufferSize(ctx);
     NR_CHECK(hipMalloc(&ctx->buffer, (size_t)(n > 0 ? n : 1) * sizeof(f64)));
@@ -693,6 +712,7 @@ void SetColor(RenderContext* ctx, f64 r, f64 g, f64 b, f64 a) {
     NR_CHECK(hipSetDevice(ctx->device));
     nr_drop_commands(ctx);   // every value of the buffer is overwritten: queued draws are dead
     nr_settle(ctx);
+    nr_deferred_supersede(ctx, true, false);   // (uniform or not: every framebuffer value is overwritten)
     if (r == g && g == b && b == a) {
         // uniform clear: kept pending, consumed on chip by the tiled raster
         ctx->pendColor = true;

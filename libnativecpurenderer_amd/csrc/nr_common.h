@@ -11,6 +11,7 @@
 #include <cstddef>
 #include <vector>
 #include <climits>
+#include "nr_defer_policy.h"
 
 typedef long i64;
 typedef double f64;
@@ -139,6 +140,7 @@ struct BatchTotals {
 
 // Scratch of the triangle pipeline, grown on demand (never shrunk).  Each
 // struct's release() frees all it declares (DestroyRenderContext, streams idle).
+struct TriangleBuffer;
 struct TriScratch {
     DevArray<u64> cnt, off;                                             // per triangle (grown together)
     DevArray<f64> orec;   // ordered raster: per-triangle setup records (ORec doubles each)
@@ -330,6 +332,28 @@ struct TriScratch {
     int keyMode = 0;                        // key cache: 0 automatic (on), 2 off (SetKeyCache)
     u64 keyIndexedBatches = 0;              // of the cached ones, shaded from the key index (GetKeyIndexedBatchCount)
     int keyIndexMode = 0;                   // key index: 0 automatic (on), 2 off (SetKeyIndex)
+    // Deferred stores: the record of the context's last cached batch that ran k_keys_idx.  A steady frame's f64
+    // framebuffer and depth values of the cached tiles are read by nothing -- the next SetColor / ClearDepth
+    // supersede them, the frame's consumer takes the frame output -- so an eligible batch (pruned_enqueue) writes
+    // the frame output alone and leaves them pending here; the first use of the buffers (nr_materialize_tiles)
+    // writes them, bit for bit (the KO_RESOLVE kernel over the same items, slots and index).  A batch that
+    // stored its values itself leaves a record too (stored: it launches nothing), so that the rule
+    // (nr_defer_policy.h) sees whether the stores were ever needed.
+    // The snapshot's pointers stay those of the generation that made the record: every writer of the schedule's
+    // key memory (key_plan, the capture frame, k_key_index, key_cache_step's regrows) sits behind frame_params,
+    // which resolves the record first; so does every free but the three outside draws, which resolve
+    // (DestroyTriangleBuffer) or drop (ResizeRenderContext, DestroyRenderContext) it themselves.
+    struct DeferredStores {
+        bool colour = false, depth = false;  // live halves (depth: a LESS + write batch only); neither: no record
+        bool stored = true;                  // the batch wrote its values itself
+        bool wasNeeded = false;              // a half of this record has been needed (the rule hears once)
+        const TriangleBuffer* tb = nullptr;  // the buffer the snapshot's records are built from
+        void* snap = nullptr;                // nrtri::DeferredSnapshot (nr_free.h), kept from record to record
+        bool live() const { return colour || depth; }
+    } deferred;
+    nrdefer::Policy deferPolicy;
+    int deferMode = 0;                      // 0 automatic (the rule), 1 always, 2 off (SetDeferredStores)
+    u64 deferredBatches = 0, deferResolves = 0, deferSuperseded = 0;   // (GetDeferredStoreCounts)
     std::vector<u64> looseBanned;           // buffers whose loose binning overflowed a tile: not binned loose again
     // warm-batch checks (k_vis WarmCheck): host-mapped word a raster sets when
     // a warm batch failed them (1 binning check, 2 token timeout), read by
@@ -529,6 +553,15 @@ void nr_materialize(RenderContext* ctx);          // flush pending clears
 void nr_materialize_color(RenderContext* ctx);
 void nr_materialize_depth(RenderContext* ctx);
 void nr_materialize_tiles(RenderContext* ctx, bool color, bool depth);   // tile-granular pending clears
+// deferred stores (TriScratch::DeferredStores; nr_tri_free.hip): the record's live halves among (color, depth) are
+// needed -- written now if pending (nr_materialize_tiles calls it) -- or superseded by a clear; the record dropped
+// with the buffers' contents (a resize), and its snapshot released; resolved in every live context whose record
+// names `tb` (DestroyTriangleBuffer, nr_api.hip)
+void nr_deferred_resolve(RenderContext* ctx, bool color, bool depth);
+void nr_deferred_supersede(RenderContext* ctx, bool color, bool depth);
+void nr_deferred_drop(RenderContext* ctx);
+void nr_deferred_free(RenderContext* ctx);
+void nr_deferred_resolve_buffer(const TriangleBuffer* tb);
 void nr_ensure_depth(RenderContext* ctx);
 void nr_timing_begin(RenderContext* ctx, int kid, hipEvent_t* a, hipEvent_t* b);
 // The rasters time themselves on the device clock (FrameParams::tstamp,

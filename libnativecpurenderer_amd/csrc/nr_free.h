@@ -157,6 +157,18 @@ struct VisArgs {
     const u32* kplan = nullptr;
     // key index (below): non-null, a cached Gouraud batch is shaded by k_keys_idx from the slots' winner index
     KeyIndex kindex;
+    // deferred stores (nr_common.h DeferredStores): the k_keys_idx batch writes the frame output alone
+    bool defer = false;
+};
+
+// What a deferred batch's resolve runs over (TriScratch::DeferredStores::snap): the batch's snapshot by value --
+// the buffer's arrays, the transform, the colour transform, the clear values -- the key fields of its VisArgs
+// (kitems, kkeys, kplan, kindex), its grid and whether it ran the 512-thread instance.
+struct DeferredSnapshot {
+    FrameParams fp;
+    VisArgs va{};
+    u32 grid = 0;
+    bool wide = false;
 };
 
 // ---- launch functions ---------------------------------------------------
@@ -198,5 +210,11 @@ int z_mode(const FrameParams& fp);
 // k_vis (or, for a batch shaded from the key cache, k_keys / k_keys_idx) over `grid` workgroups
 void launch_vis_any(const FrameParams& fp, const TriScratch& sc, const BatchTotals& t, const VisArgs& va, u32 grid,
                     hipStream_t s, hipEvent_t start, hipEvent_t stop);
+// does a batch shaded from the key cache whose totals are t run the 512-thread instances?  (launch_vis' rule)
+bool keys_wide(const BatchTotals& t);
+// the pending f64 values (colour) and / or depths (depth; LESS + write batches only) of a deferred k_keys_idx
+// batch: its snapshot, its key fields of va, its grid and workgroup size
+void launch_keys_resolve(const FrameParams& fp, const VisArgs& va, u32 grid, bool wide, bool colour, bool depth,
+                         hipStream_t s);
 
 }  // namespace nrtri

@@ -1146,13 +1146,46 @@ __global__ __launch_bounds__(KI_NT) void k_key_index(const uint4* __restrict__ i
     }
 }
 
+// What a k_keys_idx instance writes (its head comment below).
+enum { KO_ALL = 0, KO_FRAME = 1, KO_RESOLVE = 2 };
+
+// A shaded pixel's value, by OUT: framebuffer + frame output, the frame output alone, or the framebuffer alone.
+template <int OUT>
+__device__ __forceinline__ void keys_idx_out(const FrameParams& fp, i64 p, i64 px, i64 py, f64 cr, f64 cg, f64 cb,
+                                             f64 ca) {
+    if constexpr (OUT == KO_ALL) {
+        store_colour(fp, p, px, py, cr, cg, cb, ca);
+    } else if constexpr (OUT == KO_FRAME) {
+        store_frame_out(fp, p, px, py, cr, cg, cb, ca);
+    } else {   // (store_colour's f64 stores)
+        const int ipp = fp.ipp;
+        f64* dst = fp.fb + p * ipp;
+        out_store<f64>(dst, cr); out_store<f64>(dst + 1, cg); out_store<f64>(dst + 2, cb);
+        if (ipp == 4) out_store<f64>(dst + 3, ca);
+    }
+}
+
 // The steady kernel of a cached Gouraud batch whose generation has its index
 // (launch_vis): k_keys' items, grid and empty-tile path; a cached item as the
 // head comment above says.  Every value is formed by nr_tri_shade.h's helpers
 // as shade_tile forms it, so a frame is the one k_keys gives, bit for bit.
 // LDS: the KI_RT records alone (35 KB: four 256-thread workgroups per CU).
+//
+// OUT: what a cached item writes (deferred stores).
+//   KO_ALL      everything, as above: the kernel as it was before the parameter (its code is unchanged).
+//   KO_FRAME    the frame output alone -- no key loads in the first round, no depth and no f64 stores: the
+//               steady kernel of a batch whose framebuffer and depth values stay pending (DeferredStores).  Only
+//               a KI_DIRECT pixel reads its key, for the id.
+//   KO_RESOLVE  the pending values of such a batch, when something needs the buffers, from the batch's own
+//               snapshot: the f64 values where fp.fb is set, the depths where fp.depth is (launch_keys_resolve
+//               clears the pointer of a half that is not wanted); no frame output, no tile stamp, empty items
+//               skipped (k_tile_clear owns those tiles).  A depth-only resolve builds no records.
+// A deferred batch has a uniform colour clear pending (fp.frameU8 is set only then), so apply_winner's read of
+// the destination (ca != 1 and no clear pending) is never reached on a deferred batch or its resolve: the f64
+// values a KO_FRAME launch leaves unwritten are read by neither.  KO_FRAME then KO_RESOLVE form every value by
+// the same helpers in the same order as KO_ALL: the buffers end up the same bit for bit.
 constexpr int KI_OVF_Q = 1;   // directly loaded records in flight per thread (their ids come from the keys again)
-template <int ZMODE, int MODEW, int NT>
+template <int ZMODE, int MODEW, int NT, int OUT = KO_ALL>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) void k_keys_idx(
     const FrameParams fp, const uint4* __restrict__ items, const u64* __restrict__ kkeys, const u32* __restrict__ kplan,
     const unsigned short* __restrict__ kidx, const u32* __restrict__ kwin, const u32* __restrict__ kcnt) {
@@ -1162,7 +1195,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
     constexpr int PPT = TH * TW / NT;
     static_assert(PPT <= 32, "overflow bitmask");
     __shared__ __attribute__((aligned(16))) f64 rec[KI_RT * REC];
-    raster_stamp_begin(fp);
+    if constexpr (OUT != KO_RESOLVE) raster_stamp_begin(fp);
     const u32 nitems = kplan[1];
     uint4 dnext = blockIdx.x < nitems ? items[blockIdx.x] : make_uint4(0, 0, 0, 0);
 #if NR_PROBE
@@ -1189,6 +1222,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         const int wlim = (int)(fp.W - x0 < TW ? fp.W - x0 : TW);
         const int hlim = (int)(fp.H - y0 < TH ? fp.H - y0 : TH);
         if (d.y == ~0u) {   // no kept pair: only the pending clears (as k_vis)
+            if constexpr (OUT == KO_RESOLVE) continue;
             if (fp.tileStamp) {
                 if (fp.frameU8 && fp.pendColor) {
                     const f64 v = fp.pendColorValue;
@@ -1216,8 +1250,23 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         const u32* const swin = kwin + slot * KI_RT;
         u64 kv[PPT];
         unsigned short di[PPT];
+        if constexpr (OUT == KO_RESOLVE) {
+            if (!fp.fb) {   // depths alone: from the keys, no records
 #pragma unroll
-        for (int k = 0; k < PPT; ++k) kv[k] = src[itid + k * NT];
+                for (int k = 0; k < PPT; ++k) kv[k] = src[itid + k * NT];
+#pragma unroll
+                for (int k = 0; k < PPT; ++k) {
+                    const int p = itid + k * NT, lx = p & (TW - 1), ly = p / TW;
+                    if (lx >= wlim || ly >= hlim) continue;
+                    store_depth<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, kv[k]);
+                }
+                continue;
+            }
+        }
+        if constexpr (OUT != KO_FRAME) {
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) kv[k] = src[itid + k * NT];
+        }
         // (unconditional loads from in-range addresses, as k_vis' chunk loads: a conditional load makes the
         // compiler wait for everything in flight on the spot.  Entries past the slot's count are never used)
         const u32 w0 = swin[itid < KI_RT ? itid : 0];
@@ -1227,11 +1276,22 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         for (int k = 0; k < PPT; ++k) di[k] = six[itid + k * NT];
         NR_PROBE_STAMP(1);
         NR_PROBE_STAMP(2);
+        if constexpr (OUT == KO_ALL) {
 #pragma unroll
-        for (int k = 0; k < PPT; ++k) {
-            const int p = itid + k * NT, lx = p & (TW - 1), ly = p / TW;
-            if (lx >= wlim || ly >= hlim) continue;
-            store_depth<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, kv[k]);
+            for (int k = 0; k < PPT; ++k) {
+                const int p = itid + k * NT, lx = p & (TW - 1), ly = p / TW;
+                if (lx >= wlim || ly >= hlim) continue;
+                store_depth<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, kv[k]);
+            }
+        } else if constexpr (OUT == KO_RESOLVE) {
+            if (fp.depth) {
+#pragma unroll
+                for (int k = 0; k < PPT; ++k) {
+                    const int p = itid + k * NT, lx = p & (TW - 1), ly = p / TW;
+                    if (lx >= wlim || ly >= hlim) continue;
+                    store_depth<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, kv[k]);
+                }
+            }
         }
         NR_PROBE_STAMP(4);
         static_assert(KI_RT <= 2 * NT, "two winners per thread cover the staged records");
@@ -1265,7 +1325,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
             if (dn == KI_NONE) {
                 if (fp.pendColor) {
                     const f64 v = fp.pendColorValue;
-                    store_colour(fp, gp, px, py, v, v, v, v);
+                    keys_idx_out<OUT>(fp, gp, px, py, v, v, v, v);
                 }
                 continue;
             }
@@ -1276,7 +1336,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
             f64 cr, cg, cb, ca;
             record_colour<MODE>(tv, rec + dn * REC, px, py, cr, cg, cb, ca);
             apply_winner(fp, gp, cr, cg, cb, ca);
-            store_colour(fp, gp, px, py, cr, cg, cb, ca);
+            keys_idx_out<OUT>(fp, gp, px, py, cr, cg, cb, ca);
         }
         // pixels whose winner is not staged (shade_tile's pass 3b), KI_OVF_Q at
         // a time: their ids' loads in flight together, then their records'
@@ -1308,14 +1368,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
                 f64 cr, cg, cb, ca;
                 record_colour<MODE>(tv, r, px, py, cr, cg, cb, ca);
                 apply_winner(fp, gp, cr, cg, cb, ca);
-                store_colour(fp, gp, px, py, cr, cg, cb, ca);
+                keys_idx_out<OUT>(fp, gp, px, py, cr, cg, cb, ca);
             }
         }
     }
 #if NR_PROBE
     if (tid == 0 && pr_item != ~0u) probe_item(pr_item, pr_d, pr_t0, __builtin_amdgcn_s_memrealtime(), NT);
 #endif
-    raster_stamp_end(fp);
+    if constexpr (OUT != KO_RESOLVE) raster_stamp_end(fp);
 }
 
 // The instance of a batch among its four shapes -- wide workgroups (never a counting batch) or not, the flattened
@@ -1359,6 +1419,12 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& 
             const bool w = wide || keys_wide_forced();
             if constexpr (G == ATTR_GOURAUD) {
                 if (va.kindex.idx) {   // (the generation has its index, and SetKeyIndex is on: pruned_enqueue)
+                    if (va.defer) {   // (its f64 and depth stores stay pending: DeferredStores)
+                        hipExtLaunchKernelGGL(w ? k_keys_idx<Z, G, 2 * VWG, KO_FRAME> : k_keys_idx<Z, G, VWG, KO_FRAME>,
+                                              dim3(grid), dim3(w ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.kitems,
+                                              va.kkeys, va.kplan, va.kindex.idx, va.kindex.win, va.kindex.cnt);
+                        return;
+                    }
                     hipExtLaunchKernelGGL(w ? k_keys_idx<Z, G, 2 * VWG> : k_keys_idx<Z, G, VWG>, dim3(grid),
                                           dim3(w ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.kitems, va.kkeys, va.kplan,
                                           va.kindex.idx, va.kindex.win, va.kindex.cnt);
@@ -1389,6 +1455,24 @@ void launch_key_index(const uint4* kitems, const u64* kkeys, u32 tiles, unsigned
                       i64 H, int tiles_x, hipStream_t s) {
     if (!tiles) return;
     hipLaunchKernelGGL(k_key_index, dim3(tiles), dim3(KI_NT), 0, s, kitems, kkeys, tiles, idx, win, cnt, W, H, tiles_x);
+}
+
+bool keys_wide(const BatchTotals& t) {   // (launch_vis' choice for a batch shaded from the key cache)
+    return (t.n != 0 && t.heavy > 0 && t.heavy < WIDE_HEAVY) || keys_wide_forced();
+}
+
+void launch_keys_resolve(const FrameParams& fp, const VisArgs& va, u32 grid, bool wide, bool colour, bool depth,
+                         hipStream_t s) {
+    const int zmode = z_mode(fp);
+    FrameParams fr = fp;   // (the kernel writes the halves whose destination it is given)
+    if (!colour) fr.fb = nullptr;
+    if (!depth || zmode != 1) fr.depth = nullptr;
+    if ((!fr.fb && !fr.depth) || !grid || zmode == 2) return;
+    auto kernel = wide ? k_keys_idx<0, ATTR_GOURAUD, 2 * VWG, KO_RESOLVE> : k_keys_idx<0, ATTR_GOURAUD, VWG, KO_RESOLVE>;
+    if (zmode == 1)
+        kernel = wide ? k_keys_idx<1, ATTR_GOURAUD, 2 * VWG, KO_RESOLVE> : k_keys_idx<1, ATTR_GOURAUD, VWG, KO_RESOLVE>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(wide ? 2 * VWG : VWG), 0, s, fr, va.kitems, va.kkeys, va.kplan,
+                       va.kindex.idx, va.kindex.win, va.kindex.cnt);
 }
 
 void launch_vis_any(const FrameParams& fp, const TriScratch& sc, const BatchTotals& t, const VisArgs& va,

@@ -273,6 +273,7 @@ void draw_textured(RenderContext* ctx, Texture* tex, Batch& b) {
 using namespace nrtri;
 
 void nr_materialize_tiles(RenderContext* ctx, bool color, bool depth) {
+    nr_deferred_resolve(ctx, color, depth);   // (a deferred batch's cached tiles; the stamped tiles are k_tile_clear's)
     const bool c = color && ctx->tileColor, d = depth && ctx->tileDepth && ctx->depth;
     if (!c && !d) return;
     if (c) ctx->tileColor = false;
@@ -405,6 +406,7 @@ void ClearDepth(RenderContext* ctx, u32 value) {
     ctx->pendDepth = true;
     ctx->pendDepthValue = value;
     ctx->tileDepth = false;   // (superseded)
+    nr_deferred_supersede(ctx, false, true);
 }
 
 // New: copy the W*H u32 depth buffer to the host.
@@ -547,6 +549,7 @@ void DestroyTriangleBuffer(TriangleBuffer* tb) {
     // a context's pending batch may reference tb: the stream sync below
     // completes it; an overflow re-run would need tb, so settle all first
     nr_settle_all();
+    nr_deferred_resolve_buffer(tb);   // (pending values are formed from tb's arrays: written before the frees)
     NR_CHECK(hipSetDevice(tb->device));
     NR_CHECK(hipStreamSynchronize(nr_stream_for(tb->device)));
     NR_CHECK(hipStreamSynchronize(nr_bin_stream_for(tb->device)));
@@ -665,6 +668,18 @@ i64 GetKeyIndexedBatchCount(RenderContext* ctx) { return (i64)ctx->tri.keyIndexe
 bool GetKeyIndexTotals(RenderContext* ctx, i64* out) {
     NR_CHECK(hipSetDevice(ctx->device));
     return nrtri::key_index_totals(ctx, out);
+}
+// New: deferred stores -- a cached Gouraud draw that writes the frame output itself leaves the cached tiles' f64
+// framebuffer values and depths pending until something uses the buffers -- 0 automatic (the rule
+// of nr_defer_policy.h: only after records in a row that nothing needed), 1 always (every eligible batch; tests
+// and A/B), 2 off.  Switching never touches a live record.
+void SetDeferredStores(RenderContext* ctx, i64 mode) { ctx->tri.deferMode = (int)(mode >= 0 && mode <= 2 ? mode : 0); }
+// New (testing): out[0..3] = batches that deferred, resolve kernels launched, records that ended superseded
+// (their values never needed), the rule's current threshold.  Host state: does not wait for the device.
+void GetDeferredStoreCounts(RenderContext* ctx, i64* out) {
+    const TriScratch& sc = ctx->tri;
+    out[0] = (i64)sc.deferredBatches; out[1] = (i64)sc.deferResolves; out[2] = (i64)sc.deferSuperseded;
+    out[3] = (i64)sc.deferPolicy.threshold;
 }
 // New (testing): totals of the context's warm schedule -- out[0..3] = (tile,
 // triangle) pairs, k_vis work items, slices of split tiles, dense tiles;

@@ -802,10 +802,58 @@ static int key_cache_step(RenderContext* ctx, const FrameParams& fp, int zm, int
     return 2;
 }
 
+// ---- deferred stores: host side (nr_common.h DeferredStores) ----------------------
+// May this k_keys_idx batch leave its f64 and depth stores pending?  It must write the frame output of every
+// owned pixel itself (fp.frameU8: a uniform colour clear is pending and the frame output is on and sized) with
+// the empty tiles stamped, and count nothing; then SetDeferredStores decides: 2 (or NR_DEFER_STORES=2 in the
+// environment) never, 1 always, 0 by the rule of nr_defer_policy.h.
+static bool defer_wanted(const TriScratch& sc, const FrameParams& fp) {
+    static const bool envOff = [] {
+        const char* e = getenv("NR_DEFER_STORES");
+        return e && atoi(e) == 2;
+    }();
+    if (!fp.frameU8 || !fp.tileStamp || fp.fragCounter || sc.deferMode == 2 || envOff) return false;
+    return sc.deferMode == 1 || sc.deferPolicy.allows();
+}
+
+// The record of the k_keys_idx batch just enqueued (defer: it ran the KO_FRAME kernel).
+static void deferred_record(RenderContext* ctx, const FrameParams& fp, const VisArgs& va, u32 grid, bool wide, int zm,
+                            const TriangleBuffer* tb, bool defer) {
+    TriScratch& sc = ctx->tri;
+    auto& D = sc.deferred;   // (no live record: frame_params resolved it, a batch starts from resolved buffers)
+    if (defer) {
+        if (!D.snap) D.snap = new DeferredSnapshot();
+        DeferredSnapshot& s = *static_cast<DeferredSnapshot*>(D.snap);
+        s.fp = fp;
+        s.fp.tstamp = nullptr;
+        s.va = VisArgs{};
+        s.va.kkeys = va.kkeys; s.va.kitems = va.kitems; s.va.kplan = va.kplan; s.va.kindex = va.kindex;
+        s.grid = grid;
+        s.wide = wide;
+        ++sc.deferredBatches;
+    }
+    D.colour = true;
+    D.depth = zm == 1;
+    D.stored = !defer;
+    D.wasNeeded = false;
+    D.tb = tb;
+}
+
+// The end of a record with no live half.
+static void deferred_end(TriScratch& sc) {
+    auto& D = sc.deferred;
+    if (!D.wasNeeded) {
+        sc.deferPolicy.superseded();
+        ++sc.deferSuperseded;
+    }
+    D.tb = nullptr;
+}
+
 // A reused batch of the pruned list in its depth mode zm (reuse_enqueue): the
 // visible list, the visible plan and the key cache.  F: the set of the kept
 // full list, whose events the batch takes.
-static void pruned_enqueue(RenderContext* ctx, const FrameParams& fp, TriScratch::FreeSet& F, int zm, int ntiles) {
+static void pruned_enqueue(RenderContext* ctx, const FrameParams& fp, TriScratch::FreeSet& F, int zm, int ntiles,
+                           const TriangleBuffer* tb) {
     TriScratch& sc = ctx->tri;
     auto& S = sc.sched;
     const BatchTotals& T = S.totals;
@@ -850,7 +898,16 @@ static void pruned_enqueue(RenderContext* ctx, const FrameParams& fp, TriScratch
     if (kstep == 2) grid = std::min<u32>(std::max<u32>(S.knitems, 1), 8192);
     FrameParams fpk = fp;
     if (kstep == 1) fpk.kcap = reinterpret_cast<const KeyCaptureTable*>(S.ktile.p);
+    // Deferred stores: a k_keys_idx batch leaves its record, and when it may (defer_wanted) its f64 and depth
+    // stores pending.
+    const bool indexed = kstep == 2 && va.kindex.idx;
+    const bool wide = indexed && keys_wide(sc.last);
+    if (indexed) {
+        nr_deferred_resolve(ctx, true, true);   // (nothing to do behind frame_params; before the raster in any case)
+        va.defer = defer_wanted(sc, fp);
+    }
     vis_tail(ctx, F, fpk, va, grid);
+    if (indexed) deferred_record(ctx, fp, va, grid, wide, zm, tb, va.defer);
     if (kstep == 1) {   // the capture frame: its end, for key_cache_step
         if (S.kindex.p && S.kindex.cap >= std::max<size_t>(S.ktiles, 1) * KI_SLOT_BYTES) {
             // the key index from the keys just captured, in stream order: the event below covers both
@@ -883,7 +940,7 @@ static void pruned_enqueue(RenderContext* ctx, const FrameParams& fp, TriScratch
 // schedule is gone (warm_poll).  Stream order puts this raster after the one
 // that first waited for the list; vis_tail re-records F.evVis, so the set's
 // next binning waits for the last reader.  An injected fault bins.
-static void reuse_enqueue(RenderContext* ctx, const FrameParams& fp, int ntiles) {
+static void reuse_enqueue(RenderContext* ctx, const FrameParams& fp, int ntiles, const TriangleBuffer* tb) {
     TriScratch& sc = ctx->tri;
     auto& S = sc.sched;
     const BatchTotals& T = S.totals;
@@ -900,7 +957,7 @@ static void reuse_enqueue(RenderContext* ctx, const FrameParams& fp, int ntiles)
     const bool pruning = sc.pruneMode != 2 && !fp.fragCounter;
     if (pruning && S.visState == VisStage::Marking) visible_prune(ctx, ntiles);
     if (pruning && S.visState == VisStage::Pruned && S.visZ == zm) {
-        pruned_enqueue(ctx, fp, F, zm, ntiles);
+        pruned_enqueue(ctx, fp, F, zm, ntiles, tb);
         return;
     }
     FrameParams fpm = fp;
@@ -935,7 +992,7 @@ static bool warm_enqueue(RenderContext* ctx, const FrameParams& fp, const BinPar
     hipStream_t sb = warm_inline(bp.src.n, fp.period, fp.mask, fp.W, fp.H) ? sa : nr_bin_stream_for(ctx->device);
     const int ntiles = fp.tiles_x * fp.tiles_y;
     if (!loose && S.listSet >= 0 && sc.reuseMode != 2 && !sc.warmInject) {
-        reuse_enqueue(ctx, fp, ntiles);
+        reuse_enqueue(ctx, fp, ntiles, tb);
         return true;
     }
     const int si = sc.fnext;
@@ -1261,5 +1318,52 @@ bool key_index_totals(RenderContext* ctx, i64* out) {
     return true;
 }
 
+// Something needs the context's framebuffer (color) and / or depth buffer (depth): the record's live halves among
+// them are written now, if the batch had left them pending, and are dead either way.
+void deferred_resolve(RenderContext* ctx, bool color, bool depth) {
+    TriScratch& sc = ctx->tri;
+    auto& D = sc.deferred;
+    const bool c = color && D.colour, d = depth && D.depth;
+    if (!c && !d) return;
+    if (!D.stored && D.snap) {
+        const DeferredSnapshot& s = *static_cast<const DeferredSnapshot*>(D.snap);
+        hipEvent_t a, b;
+        nr_timing_begin(ctx, NRK_FILL, &a, &b);
+        launch_keys_resolve(s.fp, s.va, s.grid, s.wide, c, d, ctx->stream);
+        NR_CHECK(hipGetLastError());
+        nr_timing_end(ctx, NRK_FILL, a, b);
+        ++sc.deferResolves;
+    }
+    if (!D.wasNeeded) {
+        D.wasNeeded = true;
+        sc.deferPolicy.needed(!D.stored);
+    }
+    if (c) D.colour = false;
+    if (d) D.depth = false;
+    if (!D.live()) deferred_end(sc);
+}
+
+// A clear has overwritten every value of the framebuffer (color) or of the depth buffer (depth).
+void deferred_supersede(RenderContext* ctx, bool color, bool depth) {
+    auto& D = ctx->tri.deferred;
+    if (!D.live()) return;
+    if (color) D.colour = false;
+    if (depth) D.depth = false;
+    if (!D.live()) deferred_end(ctx->tri);
+}
+
 }  // namespace nrtri
+
+void nr_deferred_resolve(RenderContext* ctx, bool color, bool depth) { nrtri::deferred_resolve(ctx, color, depth); }
+void nr_deferred_supersede(RenderContext* ctx, bool color, bool depth) { nrtri::deferred_supersede(ctx, color, depth); }
+void nr_deferred_drop(RenderContext* ctx) {   // (the contents are discarded: the rule hears nothing)
+    auto& D = ctx->tri.deferred;
+    D.colour = D.depth = false;
+    D.tb = nullptr;
+}
+void nr_deferred_free(RenderContext* ctx) {
+    nr_deferred_drop(ctx);
+    delete static_cast<nrtri::DeferredSnapshot*>(ctx->tri.deferred.snap);
+    ctx->tri.deferred.snap = nullptr;
+}
 

@@ -989,6 +989,21 @@ class RenderContext:
             return None
         return {"tiles": out[0], "staged": out[1], "direct": out[2], "bytes": out[3]}
 
+    def set_deferred_stores(self, mode: int):
+        """Deferred stores -- a cached Gouraud draw that writes the frame output
+        leaves the cached tiles' f64 framebuffer values and depths pending until
+        something uses the buffers: 0 automatic (only after frames in a row
+        whose values nothing needed), 1 always (every eligible batch), 2 off."""
+        lib.SetDeferredStores(self._ptr, int(mode))
+
+    def deferred_store_counts(self) -> dict:
+        """Testing: batches that deferred, resolve kernels launched, records
+        superseded with their values never needed, the rule's current
+        threshold.  Host state: does not wait for the device."""
+        out = (ctypes.c_long * 4)()
+        lib.GetDeferredStoreCounts(self._ptr, out)
+        return {"deferred": out[0], "resolves": out[1], "superseded": out[2], "threshold": out[3]}
+
     def schedule_totals(self) -> typing.Optional[dict]:
         """Testing: totals of the context's warm schedule -- (tile, triangle)
         pairs, k_vis work items, slices of split tiles, dense tiles -- or None
