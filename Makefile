@@ -14,7 +14,7 @@ OBJS = $(patsubst $(SRC)/%.hip,$(OBJ)/%.o,$(SRCS))
 all: $(LIB) oracle
 
 $(OBJ)/%.o: $(SRC)/%.hip $(SRC)/nr_common.h $(SRC)/nr_tri.h $(SRC)/nr_tri_shade.h $(SRC)/nr_free.h $(SRC)/nr_mesh.h \
-             $(SRC)/nr_mesh_stage.h $(SRC)/nr_defer_policy.h
+             $(SRC)/nr_mesh_stage.h $(SRC)/nr_defer_policy.h $(SRC)/nr_key_records.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

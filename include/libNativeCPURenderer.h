@@ -428,6 +428,13 @@ i64 GetKeyIndexedBatchCount(RenderContext* ctx);                         /* NEW 
 bool GetKeyIndexTotals(RenderContext* ctx, i64* out4);                   /* NEW (testing): the key index's tiles, staged
                                                                             winners, directly loaded pixels, bytes; false:
                                                                             none.  Waits for the device */
+void SetKeyRecords(RenderContext* ctx, i64 mode);                        /* NEW: an indexed Gouraud draw shaded from its winners'
+                                                                            shading records, built once per generation, 0 auto
+                                                                            (on), 2 off (the key index; the records are kept) */
+i64 GetKeyRecordBatchCount(RenderContext* ctx);                          /* NEW (testing): of the indexed batches, shaded from
+                                                                            the key records */
+bool GetKeyRecordTotals(RenderContext* ctx, i64* out3);                  /* NEW (testing): the key records' slots, records,
+                                                                            bytes; false: none.  Waits for the device */
 void SetDeferredStores(RenderContext* ctx, i64 mode);                    /* NEW: a cached Gouraud draw that writes the frame
                                                                             output leaves its f64 and depth stores pending
                                                                             until the buffers are used: 0 auto (only after

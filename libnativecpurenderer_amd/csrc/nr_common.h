@@ -301,13 +301,29 @@ struct TriScratch {
         // Gouraud batches are then shaded by k_keys_idx.  No memory: the generation stays on k_keys
         DevArray<unsigned char> kindex;                  // ktiles x (u16 idx[TH*TW]) | ktiles x (u32 win[KI_RT]) | ktiles x (u32 cnt[2])
         bool kindexed = false;                           // this generation's index is enqueued (with its capture frame)
+        // key records (nr_free.h KeyRecords): the Gouraud shading record of every distinct winner of every cached
+        // slot -- a function of the buffer and the binning key's transform alone.  k_key_index also leaves the
+        // slots' distinct counts, a scan behind it their offsets and (hkrec) their total; once the host has seen
+        // the total (no wait) the store is sized, capped (nr_key_records.h) and filled by k_key_records, and the
+        // cached Gouraud batches after that one are shaded by k_keys_rec.  No memory, or over the cap: nothing
+        // latched, the generation stays on k_keys_idx
+        DevArray<u32> kroff;                             // ktiles distinct counts | ktiles + 1 record offsets
+        DevArray<f64> krec;                              // the records (+ a tail: nr_key_records.h room_doubles)
+        SeqWords hkrec;                                  // the scan's total (1 word), numbered by itself
+        enum class RecStage { None, Scanned /* offsets enqueued with the index */, Ready /* records enqueued */ };
+        RecStage recState = RecStage::None;
+        u64 krecords = 0;                                // (Ready) records in the store
+        const u32* kdist() const { return kroff.p; }
+        u32* roff() const { return kroff.p + (ktiles > 1 ? ktiles : 1); }
         void drop_visible() {
             visState = VisStage::None; replanState = ReplanStage::None; keyState = KeyStage::None; kindexed = false;
+            recState = RecStage::None;
         }
         void release() {
             off.release(); items.release(); off2.release();
             vlist.release(); vcnt.release(); vmask.release(); vitems.release();
             kkeys.release(); kitems.release(); ktile.release(); kindex.release();
+            kroff.release(); krec.release(); hkrec.release();
             if (kplan) NR_CHECK(hipFree(kplan));
             hkplan.release();
             if (evKey) NR_CHECK(hipEventDestroy(evKey));
@@ -332,6 +348,8 @@ struct TriScratch {
     int keyMode = 0;                        // key cache: 0 automatic (on), 2 off (SetKeyCache)
     u64 keyIndexedBatches = 0;              // of the cached ones, shaded from the key index (GetKeyIndexedBatchCount)
     int keyIndexMode = 0;                   // key index: 0 automatic (on), 2 off (SetKeyIndex)
+    u64 keyRecordBatches = 0;               // of the indexed ones, shaded from the key records (GetKeyRecordBatchCount)
+    int keyRecordMode = 0;                  // key records: 0 automatic (on), 2 off (SetKeyRecords)
     // Deferred stores: the record of the context's last cached batch that ran k_keys_idx.  A steady frame's f64
     // framebuffer and depth values of the cached tiles are read by nothing -- the next SetColor / ClearDepth
     // supersede them, the frame's consumer takes the frame output -- so an eligible batch (pruned_enqueue) writes
@@ -340,7 +358,7 @@ struct TriScratch {
     // stored its values itself leaves a record too (stored: it launches nothing), so that the rule
     // (nr_defer_policy.h) sees whether the stores were ever needed.
     // The snapshot's pointers stay those of the generation that made the record: every writer of the schedule's
-    // key memory (key_plan, the capture frame, k_key_index, key_cache_step's regrows) sits behind frame_params,
+    // key memory (key_plan, the capture frame, k_key_index, k_key_records, key_cache_step's regrows) sits behind frame_params,
     // which resolves the record first; so does every free but the three outside draws, which resolve
     // (DestroyTriangleBuffer) or drop (ResizeRenderContext, DestroyRenderContext) it themselves.
     struct DeferredStores {

@@ -136,11 +136,22 @@ constexpr int KI_RT = 280;                   // staged winners per tile (whateve
 constexpr unsigned short KI_NONE = 0xFFFF;   // the pixel has no winner ((u32)key == 0, or it lies past the frame edge)
 constexpr unsigned short KI_DIRECT = 0xFFFE; // its winner is not staged: the record is loaded directly
 struct KeyIndex {
-    const unsigned short* idx = nullptr;   // [s][TH * TW], p = ly * TW + lx: d < cnt[2 s], KI_NONE or KI_DIRECT
+    const unsigned short* idx = nullptr;   // [s][TH * TW], p = ly * TW + lx: the winner's dense number d (staged:
+                                           // d < cnt[2 s]; else its record is loaded directly), or KI_NONE
     const u32* win = nullptr;              // [s][KI_RT]: the staged winners' ids (1-based, as the keys'), dense order
     const u32* cnt = nullptr;              // [s][2]: min(distinct winners, KI_RT), KI_DIRECT pixels
 };
 constexpr size_t KI_SLOT_BYTES = (size_t)TH * TW * 2 + (size_t)KI_RT * 4 + 8;   // of the index, per cached tile
+
+// The key records of a key cache (k_key_records, once per generation, after the host has seen their total): the
+// Gouraud shading record of every distinct winner of every cached slot, slot s's from record roff[s] in dense
+// order -- a function of the buffer and the transform (part of the binning key) alone, so k_keys_rec copies a
+// slot's staged records where k_keys_idx gathers their sources and builds them, and reads a record past KI_RT
+// by its pixel's dense number.  Sizes: nr_key_records.h.
+struct KeyRecords {
+    const f64* rec = nullptr;    // [roff[slots] + 1][16] (nr_key_records.h room_doubles)
+    const u32* roff = nullptr;   // [slots + 1]
+};
 
 // The k_vis inputs of one batch: its work items, pair list and plan totals
 // (a binning set's, or the warm schedule's).
@@ -157,7 +168,9 @@ struct VisArgs {
     const u32* kplan = nullptr;
     // key index (below): non-null, a cached Gouraud batch is shaded by k_keys_idx from the slots' winner index
     KeyIndex kindex;
-    // deferred stores (nr_common.h DeferredStores): the k_keys_idx batch writes the frame output alone
+    // key records (below): non-null, the k_keys_idx batch is shaded by k_keys_rec from the slots' records
+    KeyRecords krec;
+    // deferred stores (nr_common.h DeferredStores): the k_keys_idx / k_keys_rec batch writes the frame output alone
     bool defer = false;
 };
 
@@ -203,8 +216,14 @@ void launch_key_plan(const u32* vcnt, int ntiles, int tiles_x, int period, u64 m
 
 // nr_free_vis.hip
 // the key index of `tiles` cached slots (one workgroup each) from their captured keys; W, H, tiles_x: the frame's
-void launch_key_index(const uint4* kitems, const u64* kkeys, u32 tiles, unsigned short* idx, u32* win, u32* cnt, i64 W,
-                      i64 H, int tiles_x, hipStream_t s);
+// (dist, when given: every slot's distinct winner count, uncapped)
+void launch_key_index(const uint4* kitems, const u64* kkeys, u32 tiles, unsigned short* idx, u32* win, u32* cnt,
+                      u32* dist, i64 W, i64 H, int tiles_x, hipStream_t s);
+// the record offsets roff[tiles + 1] of the slots' distinct counts, and their total into host_total under seq
+void launch_key_record_scan(const u32* dist, u32 tiles, u32* roff, u64* host_total, u32 seq, hipStream_t s);
+// the records of `tiles` cached slots (one workgroup each) from their keys and index, under fp's buffer and transform
+void launch_key_records(const FrameParams& fp, const u64* kkeys, u32 tiles, const unsigned short* idx, const u32* roff,
+                        f64* rec, hipStream_t s);
 // k_vis' ZMODE of a batch: 0 no test, 1 LESS + write, 2 LESS without write
 int z_mode(const FrameParams& fp);
 // k_vis (or, for a batch shaded from the key cache, k_keys / k_keys_idx) over `grid` workgroups

@@ -1059,7 +1059,11 @@ __global__ __launch_bounds__(NT) void k_keys(const FrameParams fp, const uint4* 
 // The build is deterministic: the winners are numbered by their first pixel in
 // p order (p = ly * TW + lx), so the staged ones of a tile with more than KI_RT
 // are those whose first pixel comes first.  The table has two slots per pixel
-// and is probed without a limit, so cnt is exactly min(distinct, KI_RT).
+// and is probed without a limit, so cnt is exactly min(distinct, KI_RT).  Every
+// pixel's entry is its winner's true dense number, staged or not (a number from
+// KI_RT on is what k_keys_idx takes as "not staged", and where k_keys_rec finds
+// the record in the slot's part of the record store); kdist, when given, gets
+// the uncapped distinct count (the record scan's input).
 constexpr int KI_HS = 2 * TH * TW;   // hash slots of k_key_index (power of two)
 constexpr int KI_NT = 256;           // its workgroup: thread t numbers pixels [t * KI_PPT, (t + 1) * KI_PPT)
 constexpr int KI_PPT = TH * TW / KI_NT;
@@ -1067,7 +1071,8 @@ static_assert(TH * TW < KI_DIRECT, "a dense number fits the index entry");
 
 __global__ __launch_bounds__(KI_NT) void k_key_index(const uint4* __restrict__ items, const u64* __restrict__ kkeys,
                                                      u32 tiles, unsigned short* __restrict__ kidx, u32* __restrict__ kwin,
-                                                     u32* __restrict__ kcnt, i64 W, i64 H, int tiles_x) {
+                                                     u32* __restrict__ kcnt, u32* __restrict__ kdist, i64 W, i64 H,
+                                                     int tiles_x) {
     __shared__ u32 ht[KI_HS];               // winner ids (0: free)
     __shared__ u32 hfirst[KI_HS];           // per table slot: the winner's first pixel
     __shared__ unsigned short hd[KI_HS];    // ... and then its dense number
@@ -1134,7 +1139,7 @@ __global__ __launch_bounds__(KI_NT) void k_key_index(const uint4* __restrict__ i
         unsigned short v = KI_NONE;
         if (id[k]) {
             v = hd[hs[k]];
-            if (v >= KI_RT) { v = KI_DIRECT; ++direct; }
+            if (v >= KI_RT) ++direct;
         }
         kidx[(size_t)slot * (TH * TW) + tid * KI_PPT + k] = v;
     }
@@ -1143,6 +1148,79 @@ __global__ __launch_bounds__(KI_NT) void k_key_index(const uint4* __restrict__ i
     if (tid == 0) {
         kcnt[2 * (size_t)slot] = distinct < (u32)KI_RT ? distinct : (u32)KI_RT;
         kcnt[2 * (size_t)slot + 1] = nDirect;
+        if (kdist) kdist[slot] = distinct;
+    }
+}
+
+// ---- key records --------------------------------------------------------------
+// The record offsets of the cached slots: roff[s] = the distinct winners of the
+// slots before s, roff[tiles] their total, which also goes to the host under
+// seq (SeqWords).  One workgroup: thread t sums a contiguous run of slots.
+constexpr int KR_SCAN_NT = 256;
+__global__ __launch_bounds__(KR_SCAN_NT) void k_key_record_scan(const u32* __restrict__ kdist, u32 tiles,
+                                                                u32* __restrict__ roff, u64* __restrict__ host_total,
+                                                                u32 seq) {
+    __shared__ u32 scan[KR_SCAN_NT];
+    const int tid = threadIdx.x;
+    const u32 per = (tiles + KR_SCAN_NT - 1) / KR_SCAN_NT;
+    const u32 lo = min((u32)tid * per, tiles), hi = min(lo + per, tiles);
+    u32 mine = 0;
+    for (u32 s = lo; s < hi; ++s) mine += kdist[s];
+    scan[tid] = mine;
+    __syncthreads();
+    for (int o = 1; o < KR_SCAN_NT; o <<= 1) {   // inclusive scan
+        const u32 v = tid >= o ? scan[tid - o] : 0u;
+        __syncthreads();
+        scan[tid] += v;
+        __syncthreads();
+    }
+    u32 run = scan[tid] - mine;
+    for (u32 s = lo; s < hi; ++s) {
+        roff[s] = run;
+        run += kdist[s];
+    }
+    if (tid == KR_SCAN_NT - 1) {
+        roff[tiles] = scan[tid];
+        __hip_atomic_store(host_total, ((u64)seq << 32) | scan[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// The records of one cached slot (a workgroup each, once per generation): the
+// first pixel of each winner in p order builds the winner's record, with the
+// helpers k_keys_idx builds it with, at its dense number in the slot's part of
+// the store.
+__global__ __launch_bounds__(KI_NT) void k_key_records(const FrameParams fp, const u64* __restrict__ kkeys, u32 tiles,
+                                                       const unsigned short* __restrict__ kidx,
+                                                       const u32* __restrict__ roff, f64* __restrict__ krec) {
+    constexpr int MODE = ATTR_GOURAUD;
+    constexpr int REC = RecLen<MODE>::REC;
+    __shared__ u32 first[TH * TW];   // per dense number: the winner's first pixel
+    const u32 slot = blockIdx.x;
+    if (slot >= tiles) return;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < TH * TW; i += KI_NT) first[i] = ~0u;
+    __syncthreads();
+    const unsigned short* const six = kidx + (size_t)slot * (TH * TW);
+    const u64* const src = kkeys + (size_t)slot * (TH * TW);
+    const u32 base = roff[slot], count = roff[slot + 1] - base;
+    unsigned short d[KI_PPT];
+#pragma unroll
+    for (int k = 0; k < KI_PPT; ++k) {
+        const int p = tid + k * KI_NT;
+        d[k] = six[p];
+        if (d[k] < count) atomicMin(&first[d[k]], (u32)p);   // (KI_NONE is past every count)
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int k = 0; k < KI_PPT; ++k) {
+        const int p = tid + k * KI_NT;
+        if (d[k] >= count || first[d[k]] != (u32)p) continue;
+        const u32 id = (u32)src[p];
+        f64 r[REC];
+        make_record<MODE>(fp, (i64)id - 1, r);
+        f64* const dst = krec + ((size_t)base + d[k]) * REC;
+#pragma unroll
+        for (int j = 0; j < REC; ++j) dst[j] = r[j];
     }
 }
 
@@ -1338,6 +1416,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
             apply_winner(fp, gp, cr, cg, cb, ca);
             keys_idx_out<OUT>(fp, gp, px, py, cr, cg, cb, ca);
         }
+        NR_PROBE_STAMP(6);   // (probe builds: the pixel pass ends, the overflow loop begins)
         // pixels whose winner is not staged (shade_tile's pass 3b), KI_OVF_Q at
         // a time: their ids' loads in flight together, then their records'
 #pragma unroll 1
@@ -1376,6 +1455,193 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
     if (tid == 0 && pr_item != ~0u) probe_item(pr_item, pr_d, pr_t0, __builtin_amdgcn_s_memrealtime(), NT);
 #endif
     if constexpr (OUT != KO_RESOLVE) raster_stamp_end(fp);
+}
+
+// The steady kernel of a cached Gouraud batch whose generation has its records
+// (launch_vis): k_keys_idx' items, grid, empty-item path, pixel pass and
+// outputs (OUT: KO_ALL or KO_FRAME; a resolve stays with k_keys_idx), but a
+// cached item's records come from the generation's record store (KeyRecords),
+// where k_key_records left them built by the same helpers: the staged ones as
+// one coalesced copy into LDS -- its addresses depend on the item's two record
+// offsets alone, so the winner ids, the gather of their sources and the build
+// are gone from the item's dependent chain; the offsets are a dependent (scalar)
+// load of their own, so the chain is still item -> offsets -> records, two
+// memory rounds -- and the record of a pixel whose
+// dense number is KI_RT or more straight from the store, by that number: no
+// key, no gather, no build.  LDS as k_keys_idx.
+constexpr int KR_OVF_Q = 2;   // directly loaded records in flight per thread
+template <int ZMODE, int MODEW, int NT, int OUT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) void k_keys_rec(
+    const FrameParams fp, const uint4* __restrict__ items, const u64* __restrict__ kkeys, const u32* __restrict__ kplan,
+    const unsigned short* __restrict__ kidx, const u32* __restrict__ roff, const f64* __restrict__ krec) {
+    constexpr int MODE = attr_base(MODEW);
+    static_assert(MODE == ATTR_GOURAUD && !attr_wraps(MODEW), "Gouraud batches only");
+    static_assert(OUT == KO_ALL || OUT == KO_FRAME, "a resolve runs k_keys_idx");
+    constexpr int REC = RecLen<MODE>::REC;
+    static_assert(REC % 2 == 0, "records are copied in 16-byte units");
+    constexpr int RU = REC / 2;                  // 16-byte units of a record
+    constexpr int UNITS = KI_RT * RU;            // ... of the staged records
+    constexpr int CPT = (UNITS + NT - 1) / NT;   // ... of a thread's share of them
+    constexpr int PPT = TH * TW / NT;
+    static_assert(PPT <= 32, "overflow bitmask");
+    __shared__ __attribute__((aligned(16))) f64 rec[KI_RT * REC];
+    raster_stamp_begin(fp);
+    const u32 nitems = kplan[1];
+    uint4 dnext = blockIdx.x < nitems ? items[blockIdx.x] : make_uint4(0, 0, 0, 0);
+#if NR_PROBE
+    const int tid = threadIdx.x;
+    u64 pr_t0 = 0;
+    u32 pr_item = ~0u;
+    uint4 pr_d = make_uint4(0, 0, 0, 0);
+#endif
+    for (u32 item = blockIdx.x; item < nitems; item += gridDim.x) {
+        const uint4 d = dnext;
+        if (item + gridDim.x < nitems) dnext = items[item + gridDim.x];
+#if NR_PROBE
+        if (tid == 0) {
+            const u64 now = __builtin_amdgcn_s_memrealtime();
+            if (pr_item != ~0u) probe_item(pr_item, pr_d, pr_t0, now, NT);
+            pr_t0 = now; pr_item = item; pr_d = make_uint4(d.x, 0u, d.z, 1u);
+        }
+#endif
+        __syncthreads();   // (the last item's pixels have read its records)
+        const int itid = opaque_tid();
+        const int tile = (int)d.x;
+        const int tx = tile % fp.tiles_x, ty = tile / fp.tiles_x;
+        const i64 x0 = (i64)tx * TW, y0 = (i64)ty * TH;
+        const int wlim = (int)(fp.W - x0 < TW ? fp.W - x0 : TW);
+        const int hlim = (int)(fp.H - y0 < TH ? fp.H - y0 : TH);
+        if (d.y == ~0u) {   // no kept pair: only the pending clears (as k_keys_idx)
+            if (fp.tileStamp) {
+                if (fp.frameU8 && fp.pendColor) {
+                    const f64 v = fp.pendColorValue;
+                    for (int p = itid; p < TH * TW; p += NT) {
+                        const int lx = p & (TW - 1), ly = p / TW;
+                        if (lx < wlim && ly < hlim)
+                            store_frame_out(fp, (y0 + ly) * fp.W + x0 + lx, x0 + lx, y0 + ly, v, v, v, v);
+                    }
+                }
+                if (itid == 0) fp.tileStamp[tile] = fp.tileEpoch;
+                continue;
+            }
+            for (int p = itid; p < TH * TW; p += NT) {
+                const int lx = p & (TW - 1), ly = p / TW;
+                if (lx < wlim && ly < hlim)
+                    store_clear<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, x0 + lx, y0 + ly);
+            }
+            continue;
+        }
+        // every load of the item in flight together: the index entries, (KO_ALL) the keys, and this thread's
+        // share of the slot's staged records.  Unconditional loads from in-range addresses (as k_keys_idx): a
+        // unit past the slot's staged records reads their last unit again -- the same line, no new bytes -- or,
+        // in a slot without winners, the store's tail (nr_key_records.h room_doubles)
+        const size_t slot = (u32)__builtin_amdgcn_readfirstlane((int)d.y);   // (uniform: the offsets are scalar loads)
+        const u64* const src = kkeys + slot * (TH * TW);
+        const unsigned short* const six = kidx + slot * (TH * TW);
+        const u32 r0 = roff[slot], r1 = roff[slot + 1];
+        const u32 U = min(r1 - r0, (u32)KI_RT);
+        const f64* const sbase = krec + (size_t)r0 * REC;
+        const double2* const srec = reinterpret_cast<const double2*>(sbase);
+        const u32 ulast = max(U * RU, 1u) - 1;
+        u64 kv[PPT];
+        unsigned short di[PPT];
+        double2 cp[CPT];
+        if constexpr (OUT == KO_ALL) {
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) kv[k] = src[itid + k * NT];
+        }
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) cp[j] = srec[min((u32)(itid + j * NT), ulast)];
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) di[k] = six[itid + k * NT];
+        NR_PROBE_STAMP(1);
+        NR_PROBE_STAMP(2);
+        if constexpr (OUT == KO_ALL) {
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) {
+                const int p = itid + k * NT, lx = p & (TW - 1), ly = p / TW;
+                if (lx >= wlim || ly >= hlim) continue;
+                store_depth<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, kv[k]);
+            }
+        }
+        NR_PROBE_STAMP(4);
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) {
+            const u32 u = (u32)(itid + j * NT);
+            if (u < U * RU) reinterpret_cast<double2*>(rec)[u] = cp[j];
+        }
+        __syncthreads();
+        NR_PROBE_STAMP(5);
+        const TexView& tv = fp.tex;
+        u32 ovf = 0;   // bit k: pixel k's winner is not staged
+#pragma unroll 1
+        for (int k = 0; k < PPT; ++k) {
+            const int p = itid + k * NT, lx = p & (TW - 1), ly = p / TW;
+            if (lx >= wlim || ly >= hlim) continue;
+            const i64 px = x0 + lx, py = y0 + ly;
+            const i64 gp = py * fp.W + px;
+            u32 dn = KI_NONE;
+#pragma unroll
+            for (int q = 0; q < PPT; ++q)
+                if (q == k) dn = di[q];   // static register index
+            if (dn == KI_NONE) {
+                if (fp.pendColor) {
+                    const f64 v = fp.pendColorValue;
+                    keys_idx_out<OUT>(fp, gp, px, py, v, v, v, v);
+                }
+                continue;
+            }
+            if (dn >= U) {
+                ovf |= 1u << k;
+                continue;
+            }
+            f64 cr, cg, cb, ca;
+            record_colour<MODE>(tv, rec + dn * REC, px, py, cr, cg, cb, ca);
+            apply_winner(fp, gp, cr, cg, cb, ca);
+            keys_idx_out<OUT>(fp, gp, px, py, cr, cg, cb, ca);
+        }
+        NR_PROBE_STAMP(6);
+        // pixels whose winner is not staged, KR_OVF_Q at a time: their records' loads in flight together (a
+        // thread with fewer left reads the slot's first record again and shades nothing from it)
+#pragma unroll 1
+        while (ovf) {
+            int kq[KR_OVF_Q];
+            double2 r2[KR_OVF_Q][RU];
+#pragma unroll
+            for (int j = 0; j < KR_OVF_Q; ++j) {
+                kq[j] = -1;
+                u32 dn = 0;
+                if (ovf) {
+                    kq[j] = __builtin_ctz(ovf);
+                    ovf &= ovf - 1;
+#pragma unroll
+                    for (int q = 0; q < PPT; ++q)
+                        if (q == kq[j]) dn = di[q];   // static register index
+                }
+                const double2* const q2 = srec + (size_t)dn * RU;
+#pragma unroll
+                for (int i = 0; i < RU; ++i) r2[j][i] = q2[i];
+            }
+#pragma unroll
+            for (int j = 0; j < KR_OVF_Q; ++j) {
+                if (kq[j] < 0) continue;
+                const int p = itid + kq[j] * NT, lx = p & (TW - 1), ly = p / TW;
+                const i64 px = x0 + lx, py = y0 + ly;
+                const i64 gp = py * fp.W + px;
+                f64 r[REC];
+#pragma unroll
+                for (int i = 0; i < RU; ++i) { r[2 * i] = r2[j][i].x; r[2 * i + 1] = r2[j][i].y; }
+                f64 cr, cg, cb, ca;
+                record_colour<MODE>(tv, r, px, py, cr, cg, cb, ca);
+                apply_winner(fp, gp, cr, cg, cb, ca);
+                keys_idx_out<OUT>(fp, gp, px, py, cr, cg, cb, ca);
+            }
+        }
+    }
+#if NR_PROBE
+    if (tid == 0 && pr_item != ~0u) probe_item(pr_item, pr_d, pr_t0, __builtin_amdgcn_s_memrealtime(), NT);
+#endif
+    raster_stamp_end(fp);
 }
 
 // The instance of a batch among its four shapes -- wide workgroups (never a counting batch) or not, the flattened
@@ -1418,6 +1684,17 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& 
         if (va.kkeys) {
             const bool w = wide || keys_wide_forced();
             if constexpr (G == ATTR_GOURAUD) {
+                if (va.kindex.idx && va.krec.rec) {   // (... and its records, and SetKeyRecords is on)
+                    if (va.defer)
+                        hipExtLaunchKernelGGL(w ? k_keys_rec<Z, G, 2 * VWG, KO_FRAME> : k_keys_rec<Z, G, VWG, KO_FRAME>,
+                                              dim3(grid), dim3(w ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.kitems,
+                                              va.kkeys, va.kplan, va.kindex.idx, va.krec.roff, va.krec.rec);
+                    else
+                        hipExtLaunchKernelGGL(w ? k_keys_rec<Z, G, 2 * VWG, KO_ALL> : k_keys_rec<Z, G, VWG, KO_ALL>,
+                                              dim3(grid), dim3(w ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.kitems,
+                                              va.kkeys, va.kplan, va.kindex.idx, va.krec.roff, va.krec.rec);
+                    return;
+                }
                 if (va.kindex.idx) {   // (the generation has its index, and SetKeyIndex is on: pruned_enqueue)
                     if (va.defer) {   // (its f64 and depth stores stay pending: DeferredStores)
                         hipExtLaunchKernelGGL(w ? k_keys_idx<Z, G, 2 * VWG, KO_FRAME> : k_keys_idx<Z, G, VWG, KO_FRAME>,
@@ -1451,10 +1728,21 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& 
 // k_vis' ZMODE of a batch: 0 no test, 1 LESS + write, 2 LESS without write
 int z_mode(const FrameParams& fp) { return fp.depthTest ? (fp.depthWrite ? 1 : 2) : 0; }
 
-void launch_key_index(const uint4* kitems, const u64* kkeys, u32 tiles, unsigned short* idx, u32* win, u32* cnt, i64 W,
-                      i64 H, int tiles_x, hipStream_t s) {
+void launch_key_index(const uint4* kitems, const u64* kkeys, u32 tiles, unsigned short* idx, u32* win, u32* cnt,
+                      u32* dist, i64 W, i64 H, int tiles_x, hipStream_t s) {
     if (!tiles) return;
-    hipLaunchKernelGGL(k_key_index, dim3(tiles), dim3(KI_NT), 0, s, kitems, kkeys, tiles, idx, win, cnt, W, H, tiles_x);
+    hipLaunchKernelGGL(k_key_index, dim3(tiles), dim3(KI_NT), 0, s, kitems, kkeys, tiles, idx, win, cnt, dist, W, H,
+                       tiles_x);
+}
+
+void launch_key_record_scan(const u32* dist, u32 tiles, u32* roff, u64* host_total, u32 seq, hipStream_t s) {
+    hipLaunchKernelGGL(k_key_record_scan, dim3(1), dim3(KR_SCAN_NT), 0, s, dist, tiles, roff, host_total, seq);
+}
+
+void launch_key_records(const FrameParams& fp, const u64* kkeys, u32 tiles, const unsigned short* idx, const u32* roff,
+                        f64* rec, hipStream_t s) {
+    if (!tiles) return;
+    hipLaunchKernelGGL(k_key_records, dim3(tiles), dim3(KI_NT), 0, s, fp, kkeys, tiles, idx, roff, rec);
 }
 
 bool keys_wide(const BatchTotals& t) {   // (launch_vis' choice for a batch shaded from the key cache)

@@ -772,6 +772,7 @@ void settle(RenderContext* ctx);
 i64 visible_pairs(RenderContext* ctx);   // pairs kept in the schedule's visible list (0: none)
 bool visible_plan_totals(RenderContext* ctx, i64* out4);   // the visible plan's pairs, items, split slices, dense tiles
 bool key_cache_totals(RenderContext* ctx, i64* out3);      // the key cache's cached tiles, key items, bytes of keys
+bool key_record_totals(RenderContext* ctx, i64* out3);     // the key records' slots, records, bytes
 bool key_index_totals(RenderContext* ctx, i64* out4);      // the key index's tiles, staged winners, direct pixels, bytes
 
 // the batch entry points behind every triangle draw call (nr_tri.hip), shared with the mesh front end

@@ -669,6 +669,18 @@ bool GetKeyIndexTotals(RenderContext* ctx, i64* out) {
     NR_CHECK(hipSetDevice(ctx->device));
     return nrtri::key_index_totals(ctx, out);
 }
+// New (testing / A-B measurement): the key records -- an indexed Gouraud draw shaded from the winners' shading
+// records, built once per generation (k_keys_rec) -- 0 automatic (on), 2 off (such draws run k_keys_idx; the
+// records are kept and used again at once after a switch back to 0).
+void SetKeyRecords(RenderContext* ctx, i64 mode) { ctx->tri.keyRecordMode = mode == 2 ? 2 : 0; }
+// New (testing): of the indexed batches, those shaded from the key records.
+i64 GetKeyRecordBatchCount(RenderContext* ctx) { return (i64)ctx->tri.keyRecordBatches; }
+// New (testing): totals of the current key records -- out[0..2] = slots, records (the sum of the tiles' distinct
+// winners), bytes of records; false (and zeros) while the generation has none.  Waits for the device.
+bool GetKeyRecordTotals(RenderContext* ctx, i64* out) {
+    NR_CHECK(hipSetDevice(ctx->device));
+    return nrtri::key_record_totals(ctx, out);
+}
 // New: deferred stores -- a cached Gouraud draw that writes the frame output itself leaves the cached tiles' f64
 // framebuffer values and depths pending until something uses the buffers -- 0 automatic (the rule
 // of nr_defer_policy.h: only after records in a row that nothing needed), 1 always (every eligible batch; tests

@@ -35,6 +35,7 @@
 // nr_free_bin.hip, those of 4 and 5 in nr_free_vis.hip; nr_free.h declares
 // their launch functions and what host and kernels share.
 #include "nr_free.h"
+#include "nr_key_records.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -47,6 +48,7 @@ namespace {
 using VisStage = TriScratch::Schedule::VisStage;
 using ReplanStage = TriScratch::Schedule::ReplanStage;
 using KeyStage = TriScratch::Schedule::KeyStage;
+using RecStage = TriScratch::Schedule::RecStage;
 
 // Events of a batch carried by the kernels' own completion signals
 // (hipExtLaunchKernel stop events) instead of separate marker packets: every
@@ -718,6 +720,45 @@ static KeyIndex key_index_view(const TriScratch::Schedule& S) {
     return ki;
 }
 
+// Does an indexed batch run k_keys_rec?  SetKeyRecords 2: no; 0 (the default): yes, unless NR_KEY_RECORDS=2 in
+// the environment (A/B runs against k_keys_idx in one build).  The store is kept either way.
+static bool key_records_wanted(int mode) {
+    static const bool envOff = [] {
+        const char* e = getenv("NR_KEY_RECORDS");
+        return e && atoi(e) == 2;
+    }();
+    return mode != 2 && !envOff;
+}
+
+// The record store of a generation whose offsets are enqueued (RecStage::Scanned), for a Gouraud batch of it:
+// once the host has seen the total (no wait; it sits in stream order before the capture frame's event, so the
+// first cached batch sees it), room for the records -- a regrow waits for the stream: a queued batch of an
+// earlier generation may still read them -- and k_key_records, here, behind frame_params.  Batches after this
+// one are shaded from the records.  Over the cap, or no memory: the error is cleared, nothing is latched and the
+// generation stays on k_keys_idx.
+static void key_records_step(RenderContext* ctx, const FrameParams& fp) {
+    auto& S = ctx->tri.sched;
+    u32 total = 0;
+    if (!S.hkrec.read(&total, 1)) return;
+    S.recState = RecStage::None;   // (whatever follows, this generation polls no more)
+    if (!nrkrec::fits(total, fp.W, fp.H, fp.ipp)) return;
+    const size_t need = (size_t)nrkrec::room_doubles(total);
+    if (S.krec.needs(need)) {
+        NR_CHECK(hipStreamSynchronize(ctx->stream));
+        S.krec.release();
+        if (hipMalloc((void**)&S.krec.p, need * sizeof(f64)) != hipSuccess) {
+            (void)hipGetLastError();
+            S.krec.p = nullptr;
+            return;
+        }
+        S.krec.cap = need;
+    }
+    launch_key_records(fp, S.kkeys, S.ktiles, key_index_view(S).idx, S.roff(), S.krec, ctx->stream);
+    NR_CHECK(hipGetLastError());
+    S.krecords = total;
+    S.recState = RecStage::Ready;
+}
+
 static void key_plan(RenderContext* ctx, const FrameParams& fp, int ntiles) {
     auto& S = ctx->tri.sched;
     const size_t tn = std::max<size_t>((size_t)ntiles, 1);
@@ -762,6 +803,7 @@ static int key_cache_step(RenderContext* ctx, const FrameParams& fp, int zm, int
         // the key index beside the keys.  No room: not an error and nothing latched -- the generation's cached
         // batches run k_keys
         S.kindexed = false;
+        S.recState = RecStage::None;
         const size_t ineed = std::max<size_t>(S.ktiles, 1) * KI_SLOT_BYTES;
         if (S.kindex.needs(ineed)) {
             NR_CHECK(hipStreamSynchronize(ctx->stream));   // (as key_plan)
@@ -771,6 +813,18 @@ static int key_cache_step(RenderContext* ctx, const FrameParams& fp, int zm, int
             } else {
                 (void)hipGetLastError();
                 S.kindex.p = nullptr;
+            }
+        }
+        // the slots' distinct counts and record offsets (key records), under the same rules
+        const size_t rneed = 2 * std::max<size_t>(S.ktiles, 1) + 1;
+        if (S.kroff.needs(rneed)) {
+            NR_CHECK(hipStreamSynchronize(ctx->stream));   // (as key_plan)
+            S.kroff.release();
+            if (hipMalloc((void**)&S.kroff.p, rneed * sizeof(u32)) == hipSuccess) {
+                S.kroff.cap = rneed;
+            } else {
+                (void)hipGetLastError();
+                S.kroff.p = nullptr;
             }
         }
         // the slots' address into the capture table, in stream order before the capture frame (an 8-byte copy
@@ -797,8 +851,19 @@ static int key_cache_step(RenderContext* ctx, const FrameParams& fp, int zm, int
     va.kitems = S.kitems;
     va.kplan = S.kplan;
     // a Gouraud batch of a generation that has its index: k_keys_idx, when SetKeyIndex says so
-    if (S.kindexed && fp.src.mode == ATTR_GOURAUD && key_index_wanted(sc.keyIndexMode))
+    if (S.kindexed && fp.src.mode == ATTR_GOURAUD && key_index_wanted(sc.keyIndexMode)) {
         va.kindex = key_index_view(S);
+        // ... that has its records: k_keys_rec, when SetKeyRecords says so.  A generation whose records are not
+        // built yet builds them here, for the batches after this one
+        if (S.recState == RecStage::Ready) {
+            if (key_records_wanted(sc.keyRecordMode)) {
+                va.krec.rec = S.krec;
+                va.krec.roff = S.roff();
+            }
+        } else if (S.recState == RecStage::Scanned) {
+            key_records_step(ctx, fp);
+        }
+    }
     return 2;
 }
 
@@ -912,10 +977,16 @@ static void pruned_enqueue(RenderContext* ctx, const FrameParams& fp, TriScratch
         if (S.kindex.p && S.kindex.cap >= std::max<size_t>(S.ktiles, 1) * KI_SLOT_BYTES) {
             // the key index from the keys just captured, in stream order: the event below covers both
             const KeyIndex ki = key_index_view(S);
+            const bool scan = S.ktiles && S.kroff.p && S.kroff.cap >= 2 * (size_t)S.ktiles + 1 && S.hkrec.ensure();
             launch_key_index(S.kitems, S.kkeys, S.ktiles, const_cast<unsigned short*>(ki.idx), const_cast<u32*>(ki.win),
-                             const_cast<u32*>(ki.cnt), fp.W, fp.H, fp.tiles_x, sa);
+                             const_cast<u32*>(ki.cnt), scan ? S.kroff.p : nullptr, fp.W, fp.H, fp.tiles_x, sa);
             NR_CHECK(hipGetLastError());
             S.kindexed = true;
+            if (scan) {   // the record offsets and their total, behind the index: key_records_step polls for it
+                launch_key_record_scan(S.kdist(), S.ktiles, S.roff(), S.hkrec.dev(), S.hkrec.next(), sa);
+                NR_CHECK(hipGetLastError());
+                S.recState = RecStage::Scanned;
+            }
         }
         if (!S.evKey) S.evKey = sync_event();
         NR_CHECK(hipEventRecord(S.evKey, sa));
@@ -926,6 +997,7 @@ static void pruned_enqueue(RenderContext* ctx, const FrameParams& fp, TriScratch
     ++sc.prunedBatches;
     if (kstep == 2) ++sc.keyCachedBatches;
     if (kstep == 2 && va.kindex.idx) ++sc.keyIndexedBatches;
+    if (kstep == 2 && va.krec.rec) ++sc.keyRecordBatches;
 }
 
 // List reuse: the schedule's last warm binning left its pair list in set
@@ -1315,6 +1387,21 @@ bool key_index_totals(RenderContext* ctx, i64* out) {
     for (size_t s = 0; s < S.ktiles; ++s) { out[1] += cnt[2 * s]; out[2] += cnt[2 * s + 1]; }
     out[0] = S.ktiles;
     out[3] = (i64)S.ktiles * (i64)KI_SLOT_BYTES;
+    return true;
+}
+
+// Totals of the generation's key records -- slots, records, bytes of records -- false while the generation has
+// none (waits for the main stream).
+bool key_record_totals(RenderContext* ctx, i64* out) {
+    auto& S = ctx->tri.sched;
+    out[0] = out[1] = out[2] = 0;
+    if (!S.valid || S.visState != VisStage::Pruned || !S.kindexed || S.keyState != KeyStage::Cached ||
+        S.recState != RecStage::Ready)
+        return false;
+    NR_CHECK(hipStreamSynchronize(ctx->stream));
+    out[0] = S.ktiles;
+    out[1] = (i64)S.krecords;
+    out[2] = (i64)nrkrec::bytes(S.krecords);
     return true;
 }
 

@@ -989,6 +989,24 @@ class RenderContext:
             return None
         return {"tiles": out[0], "staged": out[1], "direct": out[2], "bytes": out[3]}
 
+    def set_key_records(self, mode: int):
+        """The key records -- an indexed Gouraud draw shaded from its winners'
+        shading records, built once per generation: 0 automatic (on), 2 off
+        (the key index alone; the records are kept)."""
+        lib.SetKeyRecords(self._ptr, int(mode))
+
+    def key_record_batch_count(self) -> int:
+        """Of the indexed batches, those shaded from the key records."""
+        return lib.GetKeyRecordBatchCount(self._ptr)
+
+    def key_record_totals(self) -> typing.Optional[dict]:
+        """Testing: totals of the current key records -- slots, records,
+        bytes -- or None when there are none.  Waits for the device."""
+        out = (ctypes.c_long * 3)()
+        if not lib.GetKeyRecordTotals(self._ptr, out):
+            return None
+        return {"slots": out[0], "records": out[1], "bytes": out[2]}
+
     def set_deferred_stores(self, mode: int):
         """Deferred stores -- a cached Gouraud draw that writes the frame output
         leaves the cached tiles' f64 framebuffer values and depths pending until

@@ -8,7 +8,9 @@ one more frame and prints, for that frame's items: key init (item start -> stamp
 keys are in LDS, so its "key init" is the key load and its raster is zero.
 
 Run from the repository root (the tree whose bench.py and package are to be used):
-    NR_LIB=tools/exp/probe.so python tools/exp/key_phases.py [config] [shards] [frames]"""
+    NR_LIB=tools/exp/probe.so python tools/exp/key_phases.py [config] [shards] [frames] [frame]
+"frame": the probed frame is the steady frame of bench.py -- the frame output on, SetDeferredStores(1), no readback,
+so a cached Gouraud batch runs its frame-only (KO_FRAME) instance."""
 import ctypes
 import os
 import sys
@@ -27,6 +29,7 @@ from libnativecpurenderer_amd import libNativeCPURendererPybind as R  # noqa: E4
 name = sys.argv[1] if len(sys.argv) > 1 else "c3"
 shards = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 frames = int(sys.argv[3]) if len(sys.argv) > 3 else 10
+steady = len(sys.argv) > 4 and sys.argv[4] == "frame"
 cfg = bench.CONFIGS[name]
 xy, z, c = bench.make_scene(cfg)
 ctx = R.RenderContext(cfg["W"], cfg["H"], False)
@@ -39,19 +42,26 @@ lib.NrProbeRead.restype = ctypes.c_long
 lib.NrProbeRead.argtypes = [ctypes.c_void_p, ctypes.c_long]
 
 
-def frame():
+if steady:
+    ctx.set_deferred_stores(1)
+    ctx.set_frame_format("yuv420p")
+    ctx.gather_frame_u8()
+
+
+def frame(read=True):
     ctx.set_color(0, 0, 0, 0)
     ctx.set_depth_state(True, cfg.get("write", True))
     ctx.clear_depth()
     ctx.draw_triangle_buffer(buf)
     ctx.flush()
-    ctx.get_depth_buffer()   # (a readback: the device is drained and the host polls its stages at the next draw)
+    if read:
+        ctx.get_depth_buffer()   # (a readback: the device is drained and the host polls its stages at the next draw)
 
 
 for _ in range(frames):
     frame()
 lib.NrProbeReset()
-frame()
+frame(read=not steady)
 out = np.zeros(65536 * 8, np.uint64)
 n = lib.NrProbeRead(out.ctypes.data, 65536)
 e = out[: 8 * n].reshape(n, 8)
@@ -93,3 +103,25 @@ ne = L > 0
 print(f"summed item time: all {dur.sum():.0f} us, non-empty {dur[ne].sum():.0f} us; single-slice items before stamp 2 "
       f"{tot_before:.0f} us = {tot_before / max(dur.sum(), 1e-9):.3f} of all item time "
       f"({tot_before / max(tot_all, 1e-9):.3f} of the single-slice items')")
+
+# Items shaded from the key cache (k_keys_idx, k_keys_rec): stamp 2 once the item's first-round loads are issued, 4
+# after the depth stores (KO_ALL), 5 past the barrier (the staged records are in LDS: loads waited for, records built
+# or copied), 6 at the end of the pixel pass (the overflow loop follows).
+ovf = ph[:, 5]
+if not np.isnan(ovf).all():
+    print("cached items by kept pairs: count | head (start -> loads issued) | records (-> in LDS, barrier) | pixel pass | "
+          "overflow loop | item (us, means)")
+    for lo, hi in ((1, 64), (64, 128), (128, 256), (256, 512), (512, 1025), (1025, 1 << 30)):
+        m = (L >= lo) & (L < hi) & ~np.isnan(ras) & ~np.isnan(rec) & ~np.isnan(ovf)
+        if not m.any():
+            continue
+        a = [ras[m].mean(), (rec[m] - ras[m]).mean(), (ovf[m] - rec[m]).mean(), (dur[m] - ovf[m]).mean()]
+        print(f"  [{lo:5d},{hi:6d}) {m.sum():5d} | " + " | ".join(f"{v:6.2f}" for v in a) + f" | {dur[m].mean():6.2f}")
+    first = t0.min()
+    print(f"the 16 densest items against the kernel span ({span:.1f} us): kept pairs | start | head | records | pixel pass | "
+          "overflow loop | item | end (us)")
+    for i in np.argsort(-L, kind="stable")[:16]:
+        print(f"  {L[i]:6d} | {t0[i] - first:6.2f} | {ras[i]:6.2f} | {rec[i] - ras[i]:6.2f} | {ovf[i] - rec[i]:6.2f} | "
+              f"{dur[i] - ovf[i]:6.2f} | {dur[i]:6.2f} | {t0[i] - first + dur[i]:6.2f}")
+    if hasattr(ctx, "key_record_batch_count"):
+        print(f"key record batches {ctx.key_record_batch_count()}, totals {ctx.key_record_totals()}")
