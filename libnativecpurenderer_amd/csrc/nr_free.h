@@ -146,12 +146,27 @@ constexpr size_t KI_SLOT_BYTES = (size_t)TH * TW * 2 + (size_t)KI_RT * 4 + 8;   
 // The key records of a key cache (k_key_records, once per generation, after the host has seen their total): the
 // Gouraud shading record of every distinct winner of every cached slot, slot s's from record roff[s] in dense
 // order -- a function of the buffer and the transform (part of the binning key) alone, so k_keys_rec copies a
-// slot's staged records where k_keys_idx gathers their sources and builds them, and reads a record past KI_RT
-// by its pixel's dense number.  Sizes: nr_key_records.h.
+// slot's staged records where k_keys_idx gathers their sources and builds them, and reads a record past KR_RT
+// (below) by its pixel's dense number.  Sizes: nr_key_records.h.
 struct KeyRecords {
     const f64* rec = nullptr;    // [roff[slots] + 1][16] (nr_key_records.h room_doubles)
     const u32* roff = nullptr;   // [slots + 1]
+    u32 cached = 0, items = 0;   // the key plan's totals {cached tiles, items} as the host has seen them (kplan's words)
 };
+// k_keys_rec's own staging: the first KR_RT records of a slot are copied into LDS (the index's KI_RT is not
+// involved: k_key_index writes true dense numbers and roff is uncapped, so a pixel whose number is KR_RT or more
+// loads its record from the store).  248: 8 copy units per thread of a 256-thread workgroup exactly, and C3
+// measured 1.5 % faster than at 280 (profiles/key_records/ab_experiments.txt (c), profiles/steady_rec).
+constexpr int KR_RT = 248;
+// The LDS stride of a staged record, in 16-byte units: a record's 8, and one of padding -- at 128 bytes every
+// record starts on bank 0 or 32, at 144 sixteen consecutive records start on sixteen different banks.
+constexpr int KR_LU = 9;
+// Work units of a k_keys_rec launch: one per cached item, then one per run of (workgroup size / 64) empty items --
+// the key plan puts the empty items last, and a wave clears one.
+inline u32 keys_rec_units(u32 cached, u32 items, bool wide) {
+    const u32 e = (u32)(wide ? 2 * VWG : VWG) / 64;
+    return cached + (items - cached + e - 1) / e;
+}
 
 // The k_vis inputs of one batch: its work items, pair list and plan totals
 // (a binning set's, or the warm schedule's).

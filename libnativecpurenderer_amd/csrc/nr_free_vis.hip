@@ -1464,15 +1464,89 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
 // where k_key_records left them built by the same helpers: the staged ones as
 // one coalesced copy into LDS -- its addresses depend on the item's two record
 // offsets alone, so the winner ids, the gather of their sources and the build
-// are gone from the item's dependent chain; the offsets are a dependent (scalar)
-// load of their own, so the chain is still item -> offsets -> records, two
-// memory rounds -- and the record of a pixel whose
-// dense number is KI_RT or more straight from the store, by that number: no
-// key, no gather, no build.  LDS as k_keys_idx.
+// are gone from the item's dependent chain, which is {item, offsets} -> records
+// (work units, below) -- and the record of a pixel whose
+// dense number is KR_RT or more straight from the store, by that number: no
+// key, no gather, no build.
+//
+// Work units (nr_free.h keys_rec_units; the grid is their count, and the kernel
+// strides over them whatever the grid): unit v < nc is cached item v, whose slot
+// is v (k_key_plan), so the record offsets are loaded beside the item and not
+// behind it; a unit from nc on is a run of NT / 64 empty items, one per wave
+// (keys_rec_empty).  nc, nit: the key plan's totals {cached tiles, items} as the
+// host has seen them (kplan's words, by value: no load of them ahead of the item's).
+//
+// LDS: KR_RT records at a stride of KR_LU 16-byte units (35 712 B: four
+// 256-thread workgroups per CU).
 constexpr int KR_OVF_Q = 2;   // directly loaded records in flight per thread
+
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+
+// The pending clear of an empty item (no kept pair: as k_keys_idx' empty-tile path), by one wave: lane 0..63.
+// Under a tile stamp only the frame output is written, and every byte of it is one of three constants (the
+// pending colour is uniform: Y, U, V; under RGB one byte value).  A tile wholly inside the frame whose rows'
+// byte addresses in the frame output are 16-byte aligned is written in 16-byte words; every other tile pixel
+// by pixel, with store_frame_out.
+template <int ZMODE>
+__device__ __forceinline__ void keys_rec_empty(const FrameParams& fp, int tile, int lane) {
+    const int tx = tile % fp.tiles_x, ty = tile / fp.tiles_x;
+    const i64 x0 = (i64)tx * TW, y0 = (i64)ty * TH;
+    const int wlim = (int)(fp.W - x0 < TW ? fp.W - x0 : TW);
+    const int hlim = (int)(fp.H - y0 < TH ? fp.H - y0 : TH);
+    if (!fp.tileStamp) {
+        for (int p = lane; p < TH * TW; p += 64) {
+            const int lx = p & (TW - 1), ly = p / TW;
+            if (lx < wlim && ly < hlim) store_clear<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, x0 + lx, y0 + ly);
+        }
+        return;
+    }
+    if (fp.frameU8 && fp.pendColor) {
+        const f64 v = fp.pendColorValue;
+        const bool inside = wlim == TW && hlim == TH && !(reinterpret_cast<uintptr_t>(fp.frameU8) & 15);
+        const int b8 = nr_to_u8(v);
+        if (inside && fp.frameYUV && !(fp.W & 31)) {
+            // Y: TH rows of TW / 16 words; U, V: TH / 2 rows of TW / 32 words each (W is a multiple of 32, so
+            // the planes' bases W * H and W * H + (W / 2) * (H / 2) and the chroma rows are aligned as well)
+            constexpr int YW = TH * TW / 16, CW = TH * TW / 64;
+            static_assert(YW % 64 == 0 && 2 * CW == 64, "two words of Y and one of chroma per lane");
+            const u32 yb = nr_y_of(b8, b8, b8) * 0x01010101u, ub = nr_u_of(b8, b8, b8) * 0x01010101u;
+            const u32 vb = nr_v_of(b8, b8, b8) * 0x01010101u;
+#pragma unroll
+            for (int j = 0; j < YW / 64; ++j) {
+                const int w = lane + 64 * j;
+                iu8* const q = fp.frameU8 + (y0 + w / (TW / 16)) * fp.W + x0 + (w % (TW / 16)) * 16;
+                out_store<u32x4>(reinterpret_cast<u32x4*>(q), u32x4{yb, yb, yb, yb});
+            }
+            const i64 cw = fp.W >> 1;
+            const int w = lane & (CW - 1);
+            iu8* q = fp.frameU8 + fp.W * fp.H + ((y0 >> 1) + w / (TW / 32)) * cw + (x0 >> 1) + (w % (TW / 32)) * 16;
+            if (lane >= CW) q += cw * (fp.H >> 1);
+            const u32 cb = lane >= CW ? vb : ub;
+            out_store<u32x4>(reinterpret_cast<u32x4*>(q), u32x4{cb, cb, cb, cb});
+        } else if (inside && !fp.frameYUV && !((fp.W * fp.ipp) & 15)) {
+            // TH rows of TW * ipp / 16 words (12 or 16): six or eight words per lane
+            const int wpr = TW * fp.ipp / 16, words = TH * wpr;
+            const u32 cb = (u32)b8 * 0x01010101u;
+#pragma unroll
+            for (int j = 0; j < TH * TW * 4 / 16 / 64; ++j) {
+                const int w = lane + 64 * j;
+                iu8* const q = fp.frameU8 + ((y0 + w / wpr) * fp.W + x0) * fp.ipp + (w % wpr) * 16;
+                if (w < words) out_store<u32x4>(reinterpret_cast<u32x4*>(q), u32x4{cb, cb, cb, cb});
+            }
+        } else {
+            for (int p = lane; p < TH * TW; p += 64) {
+                const int lx = p & (TW - 1), ly = p / TW;
+                if (lx < wlim && ly < hlim)
+                    store_frame_out(fp, (y0 + ly) * fp.W + x0 + lx, x0 + lx, y0 + ly, v, v, v, v);
+            }
+        }
+    }
+    if (lane == 0) fp.tileStamp[tile] = fp.tileEpoch;
+}
+
 template <int ZMODE, int MODEW, int NT, int OUT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) void k_keys_rec(
-    const FrameParams fp, const uint4* __restrict__ items, const u64* __restrict__ kkeys, const u32* __restrict__ kplan,
+    const FrameParams fp, const uint4* __restrict__ items, const u64* __restrict__ kkeys, const u32 nc, const u32 nit,
     const unsigned short* __restrict__ kidx, const u32* __restrict__ roff, const f64* __restrict__ krec) {
     constexpr int MODE = attr_base(MODEW);
     static_assert(MODE == ATTR_GOURAUD && !attr_wraps(MODEW), "Gouraud batches only");
@@ -1480,23 +1554,32 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
     constexpr int REC = RecLen<MODE>::REC;
     static_assert(REC % 2 == 0, "records are copied in 16-byte units");
     constexpr int RU = REC / 2;                  // 16-byte units of a record
-    constexpr int UNITS = KI_RT * RU;            // ... of the staged records
+    constexpr int LU = KR_LU;                    // ... of its place in LDS
+    static_assert(LU >= RU && (RU & (RU - 1)) == 0, "a padded record; the unit's place by shifts");
+    constexpr int UNITS = KR_RT * RU;            // ... of the staged records
     constexpr int CPT = (UNITS + NT - 1) / NT;   // ... of a thread's share of them
     constexpr int PPT = TH * TW / NT;
+    constexpr int RSTEP = NT / TW;               // rows between a thread's pixels: p = itid + k * NT is one column
     static_assert(PPT <= 32, "overflow bitmask");
-    __shared__ __attribute__((aligned(16))) f64 rec[KI_RT * REC];
+    static_assert(NT % TW == 0 && PPT % 2 == 0, "a column per thread; index entries in pairs");
+    constexpr int EW = NT / 64;                  // empty items of a unit
+    __shared__ __attribute__((aligned(16))) double2 rec[KR_RT * LU];
     raster_stamp_begin(fp);
-    const u32 nitems = kplan[1];
-    uint4 dnext = blockIdx.x < nitems ? items[blockIdx.x] : make_uint4(0, 0, 0, 0);
+    const u32 units = nc + (nit - nc + EW - 1) / EW;
+    const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    auto item_of = [&](u32 v) { return v < nc ? v : nc + (v - nc) * EW + wave; };   // (past nit: nothing to do)
+    uint4 dnext = make_uint4(0, 0, 0, 0);
+    if (blockIdx.x < units && item_of(blockIdx.x) < nit) dnext = items[item_of(blockIdx.x)];
 #if NR_PROBE
     const int tid = threadIdx.x;
     u64 pr_t0 = 0;
     u32 pr_item = ~0u;
     uint4 pr_d = make_uint4(0, 0, 0, 0);
 #endif
-    for (u32 item = blockIdx.x; item < nitems; item += gridDim.x) {
+    for (u32 v = blockIdx.x; v < units; v += gridDim.x) {
         const uint4 d = dnext;
-        if (item + gridDim.x < nitems) dnext = items[item + gridDim.x];
+        const u32 item = item_of(v);
+        if (v + gridDim.x < units && item_of(v + gridDim.x) < nit) dnext = items[item_of(v + gridDim.x)];
 #if NR_PROBE
         if (tid == 0) {
             const u64 now = __builtin_amdgcn_s_memrealtime();
@@ -1504,42 +1587,21 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
             pr_t0 = now; pr_item = item; pr_d = make_uint4(d.x, 0u, d.z, 1u);
         }
 #endif
-        __syncthreads();   // (the last item's pixels have read its records)
         const int itid = opaque_tid();
-        const int tile = (int)d.x;
-        const int tx = tile % fp.tiles_x, ty = tile / fp.tiles_x;
-        const i64 x0 = (i64)tx * TW, y0 = (i64)ty * TH;
-        const int wlim = (int)(fp.W - x0 < TW ? fp.W - x0 : TW);
-        const int hlim = (int)(fp.H - y0 < TH ? fp.H - y0 : TH);
-        if (d.y == ~0u) {   // no kept pair: only the pending clears (as k_keys_idx)
-            if (fp.tileStamp) {
-                if (fp.frameU8 && fp.pendColor) {
-                    const f64 v = fp.pendColorValue;
-                    for (int p = itid; p < TH * TW; p += NT) {
-                        const int lx = p & (TW - 1), ly = p / TW;
-                        if (lx < wlim && ly < hlim)
-                            store_frame_out(fp, (y0 + ly) * fp.W + x0 + lx, x0 + lx, y0 + ly, v, v, v, v);
-                    }
-                }
-                if (itid == 0) fp.tileStamp[tile] = fp.tileEpoch;
-                continue;
-            }
-            for (int p = itid; p < TH * TW; p += NT) {
-                const int lx = p & (TW - 1), ly = p / TW;
-                if (lx < wlim && ly < hlim)
-                    store_clear<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, x0 + lx, y0 + ly);
-            }
+        if (v >= nc) {   // a run of empty items: only the pending clears, a wave each
+            if (item < nit) keys_rec_empty<ZMODE>(fp, (int)d.x, itid & 63);
             continue;
         }
+        __syncthreads();   // (the last item's pixels have read its records)
         // every load of the item in flight together: the index entries, (KO_ALL) the keys, and this thread's
         // share of the slot's staged records.  Unconditional loads from in-range addresses (as k_keys_idx): a
         // unit past the slot's staged records reads their last unit again -- the same line, no new bytes -- or,
         // in a slot without winners, the store's tail (nr_key_records.h room_doubles)
-        const size_t slot = (u32)__builtin_amdgcn_readfirstlane((int)d.y);   // (uniform: the offsets are scalar loads)
+        const size_t slot = v;   // (uniform: the offsets are scalar loads, in flight beside the item's)
         const u64* const src = kkeys + slot * (TH * TW);
         const unsigned short* const six = kidx + slot * (TH * TW);
         const u32 r0 = roff[slot], r1 = roff[slot + 1];
-        const u32 U = min(r1 - r0, (u32)KI_RT);
+        const u32 U = min(r1 - r0, (u32)KR_RT);
         const f64* const sbase = krec + (size_t)r0 * REC;
         const double2* const srec = reinterpret_cast<const double2*>(sbase);
         const u32 ulast = max(U * RU, 1u) - 1;
@@ -1556,34 +1618,53 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
         for (int k = 0; k < PPT; ++k) di[k] = six[itid + k * NT];
         NR_PROBE_STAMP(1);
         NR_PROBE_STAMP(2);
+        const int tile = (int)d.x;
+        const int tx = tile % fp.tiles_x, ty = tile / fp.tiles_x;
+        const int lx = itid & (TW - 1), ly0 = itid / TW;
+        const int xi = tx * TW + lx, yi0 = ty * TH + ly0;   // the thread's column and its first row (below 2^31)
+        const int wlim = (int)(fp.W - (i64)tx * TW < TW ? fp.W - (i64)tx * TW : TW);
+        const int hlim = (int)(fp.H - (i64)ty * TH < TH ? fp.H - (i64)ty * TH : TH);
+        const i64 gp0 = (i64)yi0 * fp.W + xi, gstep = (i64)RSTEP * fp.W;
         if constexpr (OUT == KO_ALL) {
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
-                const int p = itid + k * NT, lx = p & (TW - 1), ly = p / TW;
-                if (lx >= wlim || ly >= hlim) continue;
-                store_depth<ZMODE>(fp, (y0 + ly) * fp.W + x0 + lx, kv[k]);
+                if (lx >= wlim || ly0 + k * RSTEP >= hlim) continue;
+                store_depth<ZMODE>(fp, gp0 + k * gstep, kv[k]);
             }
         }
         NR_PROBE_STAMP(4);
+        // the loaded units pinned here, all of them: without it the compiler sinks each load into the block of
+        // its guarded store below and waits for it there -- CPT dependent memory rounds in place of one
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) asm volatile("" : "+v"(cp[j].x), "+v"(cp[j].y));
 #pragma unroll
         for (int j = 0; j < CPT; ++j) {
             const u32 u = (u32)(itid + j * NT);
-            if (u < U * RU) reinterpret_cast<double2*>(rec)[u] = cp[j];
+            if (u < U * RU) rec[(u / RU) * LU + (u & (RU - 1))] = cp[j];
         }
+        // the index entries in pairs, as a ring of PPT / 2 words that the pixel loop turns by one entry per
+        // pixel: no select chain over the eight registers, and after PPT turns the ring is as it was
+        u32 dw[PPT / 2];
+#pragma unroll
+        for (int q = 0; q < PPT / 2; ++q) dw[q] = (u32)di[2 * q] | ((u32)di[2 * q + 1] << 16);
         __syncthreads();
         NR_PROBE_STAMP(5);
         const TexView& tv = fp.tex;
         u32 ovf = 0;   // bit k: pixel k's winner is not staged
+        i64 gp = gp0 - gstep;
 #pragma unroll 1
         for (int k = 0; k < PPT; ++k) {
-            const int p = itid + k * NT, lx = p & (TW - 1), ly = p / TW;
-            if (lx >= wlim || ly >= hlim) continue;
-            const i64 px = x0 + lx, py = y0 + ly;
-            const i64 gp = py * fp.W + px;
-            u32 dn = KI_NONE;
+            gp += gstep;
+            const u32 dn = dw[0] & 0xFFFFu;
+            {
+                const u32 first = dw[0];
 #pragma unroll
-            for (int q = 0; q < PPT; ++q)
-                if (q == k) dn = di[q];   // static register index
+                for (int q = 0; q + 1 < PPT / 2; ++q) dw[q] = __builtin_amdgcn_alignbit(dw[q + 1], dw[q], 16);
+                dw[PPT / 2 - 1] = __builtin_amdgcn_alignbit(first, dw[PPT / 2 - 1], 16);
+            }
+            const int yi = yi0 + k * RSTEP;
+            if (lx >= wlim || ly0 + k * RSTEP >= hlim) continue;
+            const i64 px = xi, py = yi;
             if (dn == KI_NONE) {
                 if (fp.pendColor) {
                     const f64 v = fp.pendColorValue;
@@ -1595,8 +1676,18 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
                 ovf |= 1u << k;
                 continue;
             }
+            // the record's eight reads issued before the first use (pinned: left alone, the compiler reads it
+            // in four groups through the same registers, with a wait behind each)
+            double2 rr[RU];
+#pragma unroll
+            for (int i = 0; i < RU; ++i) rr[i] = rec[dn * LU + i];
+#pragma unroll
+            for (int i = 0; i < RU; ++i) asm volatile("" : "+v"(rr[i].x), "+v"(rr[i].y));
+            f64 r[REC];
+#pragma unroll
+            for (int i = 0; i < RU; ++i) { r[2 * i] = rr[i].x; r[2 * i + 1] = rr[i].y; }
             f64 cr, cg, cb, ca;
-            record_colour<MODE>(tv, rec + dn * REC, px, py, cr, cg, cb, ca);
+            record_colour<MODE>(tv, r, px, py, cr, cg, cb, ca);
             apply_winner(fp, gp, cr, cg, cb, ca);
             keys_idx_out<OUT>(fp, gp, px, py, cr, cg, cb, ca);
         }
@@ -1614,9 +1705,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
                 if (ovf) {
                     kq[j] = __builtin_ctz(ovf);
                     ovf &= ovf - 1;
+                    u32 w = 0;
 #pragma unroll
-                    for (int q = 0; q < PPT; ++q)
-                        if (q == kq[j]) dn = di[q];   // static register index
+                    for (int q = 0; q < PPT / 2; ++q)
+                        if (q == kq[j] >> 1) w = dw[q];   // static register index (the ring is back at its start)
+                    dn = (w >> ((kq[j] & 1) * 16)) & 0xFFFFu;
                 }
                 const double2* const q2 = srec + (size_t)dn * RU;
 #pragma unroll
@@ -1625,9 +1718,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VIS_WPE))) v
 #pragma unroll
             for (int j = 0; j < KR_OVF_Q; ++j) {
                 if (kq[j] < 0) continue;
-                const int p = itid + kq[j] * NT, lx = p & (TW - 1), ly = p / TW;
-                const i64 px = x0 + lx, py = y0 + ly;
-                const i64 gp = py * fp.W + px;
+                const i64 px = xi, py = yi0 + kq[j] * RSTEP;
+                const i64 gp = gp0 + kq[j] * gstep;
                 f64 r[REC];
 #pragma unroll
                 for (int i = 0; i < RU; ++i) { r[2 * i] = r2[j][i].x; r[2 * i + 1] = r2[j][i].y; }
@@ -1685,14 +1777,17 @@ void launch_vis(const FrameParams& fp, const TriScratch& sc, const BatchTotals& 
             const bool w = wide || keys_wide_forced();
             if constexpr (G == ATTR_GOURAUD) {
                 if (va.kindex.idx && va.krec.rec) {   // (... and its records, and SetKeyRecords is on)
+                    // a workgroup per work unit: the cached items, then the empty ones in runs (keys_rec_units)
+                    const u32 nc = va.krec.cached, nit = va.krec.items;
+                    const u32 rgrid = std::min<u32>(std::max<u32>(keys_rec_units(nc, nit, w), 1), 8192);
                     if (va.defer)
                         hipExtLaunchKernelGGL(w ? k_keys_rec<Z, G, 2 * VWG, KO_FRAME> : k_keys_rec<Z, G, VWG, KO_FRAME>,
-                                              dim3(grid), dim3(w ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.kitems,
-                                              va.kkeys, va.kplan, va.kindex.idx, va.krec.roff, va.krec.rec);
+                                              dim3(rgrid), dim3(w ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.kitems,
+                                              va.kkeys, nc, nit, va.kindex.idx, va.krec.roff, va.krec.rec);
                     else
                         hipExtLaunchKernelGGL(w ? k_keys_rec<Z, G, 2 * VWG, KO_ALL> : k_keys_rec<Z, G, VWG, KO_ALL>,
-                                              dim3(grid), dim3(w ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.kitems,
-                                              va.kkeys, va.kplan, va.kindex.idx, va.krec.roff, va.krec.rec);
+                                              dim3(rgrid), dim3(w ? 2 * VWG : VWG), 0, s, start, stop, 0, fp, va.kitems,
+                                              va.kkeys, nc, nit, va.kindex.idx, va.krec.roff, va.krec.rec);
                     return;
                 }
                 if (va.kindex.idx) {   // (the generation has its index, and SetKeyIndex is on: pruned_enqueue)

@@ -859,6 +859,8 @@ static int key_cache_step(RenderContext* ctx, const FrameParams& fp, int zm, int
             if (key_records_wanted(sc.keyRecordMode)) {
                 va.krec.rec = S.krec;
                 va.krec.roff = S.roff();
+                va.krec.cached = S.ktiles;   // (the plan's totals, seen at KeyStage::Planned: k_keys_rec's grid
+                va.krec.items = S.knitems;   // and its split into cached and empty items)
             }
         } else if (S.recState == RecStage::Scanned) {
             key_records_step(ctx, fp);
