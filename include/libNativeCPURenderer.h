@@ -384,6 +384,41 @@ bool PoseMeshDevice(RenderContext* ctx, Mesh* m, MeshSkin* s, const f64* palette
 bool GetMeshPositions(Mesh* m, f64* out);                                /* NEW: nv*3 to the host; a sync point */
 bool GetMeshNormals(Mesh* m, f64* out);                                  /* NEW: a lit mesh only (else false, error
                                  latched) */
+/* NEW: morph targets (DESIGN §3 "Morph targets"): blend shapes on the device, alone or fused with skinning.  A
+   MeshMorph keeps nv base positions and T (1 .. 1024) target-major position deltas dP[t][v] (T*nv*3), and either
+   both or neither of base normals and normal deltas dN[t][v].  A call supplies T weights and one kernel rewrites
+   the mesh's positions (and normals).  Per vertex and component, in f64, every product and sum rounded in the order
+   written (no FMA, no division, no renormalisation):
+     X = px;  for t = 0 .. T-1 in index order:  if w_t == 0.0 skip the target;  X = X + w_t * dPx[t][v]
+   (Y, Z, and NX, NY, NZ from the base normal and dN, likewise).  The skip is part of the definition: a target under
+   a zero weight of either sign contributes nothing, NaN or infinite deltas included, and with every weight zero the
+   result is the base bit for bit; a NaN weight is not zero.  Weights and deltas are not validated.
+   PoseMeshMorphed evaluates this in registers and feeds the result to PoseMesh's expressions in place of the skin's
+   bind position and normal (the skin's own bind arrays are not read): it equals MorphMesh, a read-back, a skin
+   created with that as its bind pose and PoseMesh, bit for bit.  Positions are always written; normals when the
+   mesh is lit AND the morph has normals (fused: whether or not the skin has bind normals); otherwise a lit mesh
+   keeps its own.  PoseMesh after MorphMesh starts from the skin's bind pose, as always, and overwrites the morph.
+   Ordering is PoseMesh's: draws issued before a call keep the old vertices, draws issued after it see the new ones,
+   on any context of the device, and the host waits for nothing.  Each error latches a message under the entry
+   point's name and changes nothing: NULL arguments, nv < 0 or beyond 32 bits, T < 1 or > 1024, exactly one of
+   baseNormal / deltaNormal, mesh, morph and skin of different vertex counts, objects not all on one device, a
+   device pointer that is not 16-byte aligned.  nv == 0 is valid and does nothing. */
+typedef struct MeshMorph MeshMorph;
+MeshMorph* CreateMeshMorph(i64 nv, const f64* basePos, const f64* baseNormal, i64 T, const f64* deltaPos,
+                           const f64* deltaNormal);                      /* NEW: host arrays, the caller's again on
+                                 return; baseNormal and deltaNormal both NULL: positions only */
+void DestroyMeshMorph(MeshMorph* mo);                                    /* NEW: waits for the device's stream */
+i64 GetMeshMorphTargetCount(MeshMorph* mo);                              /* NEW */
+bool MorphMesh(RenderContext* ctx, Mesh* m, MeshMorph* mo, const f64* weights);   /* NEW: host weights T, the
+                                 caller's again on return (one asynchronous copy through a pinned buffer) */
+bool MorphMeshDevice(RenderContext* ctx, Mesh* m, MeshMorph* mo, const f64* weights);   /* NEW: device pointer,
+                                 16-byte aligned, valid and unchanged until the call's kernel has executed */
+bool PoseMeshMorphed(RenderContext* ctx, Mesh* m, MeshSkin* s, const f64* palette, MeshMorph* mo,
+                     const f64* weights);                                /* NEW: morph then skin in one kernel; host
+                                 palette nb*12 and weights T, through ONE pinned buffer */
+bool PoseMeshMorphedDevice(RenderContext* ctx, Mesh* m, MeshSkin* s, const f64* palette, MeshMorph* mo,
+                           const f64* weights);                          /* NEW: palette and weights both device
+                                 pointers, 16-byte aligned, under PoseMeshDevice's lifetime rule */
 void SetFragmentCounting(RenderContext* ctx, bool on);                   /* NEW: covered-fragment counter */
 i64 GetFragmentCount(RenderContext* ctx);                                /* NEW */
 i64 GetLastRasterPath(RenderContext* ctx);                               /* NEW: 1 order-free tiled, 2 ordered */

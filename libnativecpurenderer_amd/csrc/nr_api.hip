@@ -353,7 +353,7 @@ static const char* kKernelNames[NRK_COUNT_] = {"tri_count", "tri_scan",    "tri_
                                                "mesh_inst_clip_scan", "mesh_inst_clip_emit",
                                                "mesh_light", "mesh_lit_attr",
                                                "mesh_inst_light", "mesh_inst_lit_attr",
-                                               "mesh_skin"};
+                                               "mesh_skin", "mesh_morph", "mesh_morph_skin"};
 
 extern "C" {
 
@@ -819,7 +819,7 @@ void EnableKernelTiming(RenderContext* ctx, bool on) {
 // Sum and count of the named kernel's durations since the last reset
 // (names: tri_count tri_scan tri_emit tri_sort tile_ranges tile_raster prim fill resolve vis_init output gather
 // mesh_vertex mesh_assemble mesh_clip_vertex mesh_clip_count mesh_clip_scan mesh_clip_emit, their mesh_inst_*
-// forms, mesh_light mesh_lit_attr mesh_inst_light mesh_inst_lit_attr, mesh_skin).
+// forms, mesh_light mesh_lit_attr mesh_inst_light mesh_inst_lit_attr, mesh_skin, mesh_morph, mesh_morph_skin).
 bool GetKernelTiming(RenderContext* ctx, const char* name, f64* total_ms, i64* count) {
     NR_CHECK(hipSetDevice(ctx->device));
     timing_collect(ctx);

@@ -412,7 +412,7 @@ enum NRKernelId { NRK_TRI_COUNT = 0, NRK_TRI_SCAN, NRK_TRI_EMIT, NRK_TRI_SORT, N
                   NRK_MESH_CLIP_EMIT, NRK_MESH_INST_VERTEX, NRK_MESH_INST_ASSEMBLE, NRK_MESH_INST_CLIP_VERTEX,
                   NRK_MESH_INST_CLIP_COUNT, NRK_MESH_INST_CLIP_SCAN, NRK_MESH_INST_CLIP_EMIT,
                   NRK_MESH_LIGHT, NRK_MESH_LIT_ATTR, NRK_MESH_INST_LIGHT, NRK_MESH_INST_LIT_ATTR, NRK_MESH_SKIN,
-                  NRK_COUNT_ };
+                  NRK_MESH_MORPH, NRK_MESH_MORPH_SKIN, NRK_COUNT_ };
 
 // The light state of a context's lit mesh draws (SetMeshLights; DESIGN.md §3 "Vertex lighting"): the ambient
 // colour and up to MESH_MAX_LIGHTS directional lights (dx, dy, dz, cr, cg, cb), d towards the light.  51 doubles

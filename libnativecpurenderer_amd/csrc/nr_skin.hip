@@ -29,48 +29,7 @@
 #include <cstdint>
 #include <cstring>
 
-struct MeshSkin {
-    i64 nv = 0, nb = 0;
-    int device = 0;
-    f64* pos = nullptr;        // bind positions nv*3
-    f64* normal = nullptr;     // bind normals nv*3, or null
-    u32* joints = nullptr;     // nv*4, every entry < nb
-    f64* weights = nullptr;    // nv*4
-    f64* palette = nullptr;    // nb*12: where a host palette lands (PoseMesh)
-    int variant = 0;           // kernel: 0 automatic, 1 palette from global memory, 2 staged in LDS (SetMeshSkinVariant)
-};
-
 namespace {
-
-struct Bone { f64 m[12]; };   // only ever indexed by constants: registers
-
-// Entries of bone j as six 16-byte loads; lanes of a wave that share a bone hit the same lines (cache-resident:
-// the palette is nb*96 bytes).
-__device__ __forceinline__ Bone load_bone(const double2* __restrict__ palette, u32 j) {
-    const double2* p = palette + (size_t)j * 6;
-    Bone B;
-#pragma unroll
-    for (int e = 0; e < 6; ++e) {
-        const double2 q = p[e];
-        B.m[2 * e] = q.x;
-        B.m[2 * e + 1] = q.y;
-    }
-    return B;
-}
-
-// The LDS variant: the block first copies the whole palette (nb <= SKIN_LDS_MAX_BONES) into LDS, a bone every
-// SKIN_LDS_STRIDE doubles -- 13, odd, so that lanes reading the same entry of different bones with 8-byte reads
-// spread over the banks -- and every lane then reads its four bones from there.
-constexpr int SKIN_LDS_MAX_BONES = 128;
-constexpr int SKIN_LDS_STRIDE = 13;
-
-__device__ __forceinline__ Bone load_bone_lds(const f64* sh, u32 j) {
-    const f64* p = sh + j * (u32)SKIN_LDS_STRIDE;
-    Bone B;
-#pragma unroll
-    for (int e = 0; e < 12; ++e) B.m[e] = p[e];
-    return B;
-}
 
 // One thread per vertex: 24 B of bind position, one 16-byte load of joints, two of weights, four bones of 96 B
 // through the per-lane joints, 24 B out; NRM: the same for the normal under each bone's 3x3.

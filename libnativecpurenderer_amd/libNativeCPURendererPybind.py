@@ -736,6 +736,60 @@ class RenderContext:
         if not lib.PoseMeshDevice(self._ptr, mesh._ptr, skin._ptr, addr):
             raise RuntimeError("PoseMeshDevice failed: " + _lib.last_error())
 
+    # morph targets (DESIGN.md §3 "Morph targets"): one kernel rewrites the
+    # mesh's positions (and normals) from the morph's base and its weighted
+    # deltas, alone or fused with skinning; no host wait
+    @staticmethod
+    def _morph_args(mesh, morph, weights=None):
+        if mesh.vertex_count != morph.vertex_count:
+            raise ValueError("the Mesh and the MeshMorph differ in their vertex count")
+        if weights is None:
+            return None
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim != 1 or w.shape[0] != morph.target_count:
+            raise ValueError("weights must be (target_count,)")
+        return w
+
+    def morph_mesh(self, mesh: "Mesh", morph: "MeshMorph", weights):
+        """Morphs `mesh`: base + the sum of weights[t] * delta[t] over the
+        targets whose weight is not zero, in index order.  Draws already
+        issued keep the old vertices, later draws -- on any context -- see
+        the new ones; the array is the caller's again on return."""
+        w = self._morph_args(mesh, morph, weights)
+        if not lib.MorphMesh(self._ptr, mesh._ptr, morph._ptr, _f64_ptr(w)):
+            raise RuntimeError("MorphMesh failed: " + _lib.last_error())
+
+    def morph_mesh_device(self, mesh: "Mesh", morph: "MeshMorph", weights):
+        """morph_mesh with the weights (target_count f64, 16-byte aligned)
+        already in HBM: a device address or an object with .data_ptr() --
+        keep it alive and unchanged until the call's kernel has executed."""
+        self._morph_args(mesh, morph)
+        addr = weights.data_ptr() if hasattr(weights, "data_ptr") else int(weights)
+        if not lib.MorphMeshDevice(self._ptr, mesh._ptr, morph._ptr, addr):
+            raise RuntimeError("MorphMeshDevice failed: " + _lib.last_error())
+
+    def pose_mesh_morphed(self, mesh: "Mesh", skin: "MeshSkin", palette, morph: "MeshMorph", weights):
+        """Morph, then pose, in one kernel: the morph's result takes the place
+        of `skin`'s bind pose (palette and weights as for pose_mesh and
+        morph_mesh)."""
+        self._pose_args(mesh, skin)
+        w = self._morph_args(mesh, morph, weights)
+        pal = np.ascontiguousarray(palette, dtype=np.float64)
+        if pal.size != skin.bone_count * 12 or pal.ndim < 2 or pal.shape[0] != skin.bone_count:
+            raise ValueError("palette must be (bone_count, 12) or (bone_count, 3, 4)")
+        if not lib.PoseMeshMorphed(self._ptr, mesh._ptr, skin._ptr, _f64_ptr(pal), morph._ptr, _f64_ptr(w)):
+            raise RuntimeError("PoseMeshMorphed failed: " + _lib.last_error())
+
+    def pose_mesh_morphed_device(self, mesh: "Mesh", skin: "MeshSkin", palette, morph: "MeshMorph", weights):
+        """pose_mesh_morphed with the palette and the weights already in HBM
+        (both 16-byte aligned, as for pose_mesh_device)."""
+        self._pose_args(mesh, skin)
+        self._morph_args(mesh, morph)
+        pa = palette.data_ptr() if hasattr(palette, "data_ptr") else int(palette)
+        wa = weights.data_ptr() if hasattr(weights, "data_ptr") else int(weights)
+        if not lib.PoseMeshMorphedDevice(self._ptr, mesh._ptr, skin._ptr, pa, morph._ptr, wa):
+            raise RuntimeError("PoseMeshMorphedDevice failed: " + _lib.last_error())
+
     # ---- additions: sync, device interop, measurement ------------------
     def flush(self):
         lib.Flush(self._ptr)
@@ -1541,6 +1595,47 @@ class MeshSkin:
     def __del__(self):
         if getattr(self, "_can_release", False):
             lib.DestroyMeshSkin(self._ptr)
+            self._can_release = False
+
+
+class MeshMorph:
+    """Device-resident morph targets of a Mesh (new): base positions and
+    target_count position deltas, optionally base normals and normal deltas
+    (RenderContext.morph_mesh, pose_mesh_morphed)."""
+
+    def __init__(self, base_positions, delta_positions, base_normals=None, delta_normals=None):
+        """base_positions: (nv, 3); delta_positions: (T, nv, 3), 1 <= T <=
+        1024; base_normals (nv, 3) and delta_normals (T, nv, 3): both or
+        neither -- also morph a lit Mesh's normals.  Nothing is validated."""
+        pos = np.ascontiguousarray(base_positions, dtype=np.float64).reshape(-1, 3)
+        nv = pos.shape[0]
+        dp = np.ascontiguousarray(delta_positions, dtype=np.float64)
+        if dp.ndim != 3 or dp.shape[1:] != (nv, 3):
+            raise ValueError("delta_positions must be (T, nv, 3)")
+        if (base_normals is None) != (delta_normals is None):
+            raise ValueError("base_normals and delta_normals go together")
+        nrm = dn = None
+        if base_normals is not None:
+            nrm = np.ascontiguousarray(base_normals, dtype=np.float64)
+            if nrm.size != nv * 3:
+                raise ValueError("base_normals must be (nv, 3)")
+            dn = np.ascontiguousarray(delta_normals, dtype=np.float64)
+            if dn.shape != dp.shape:
+                raise ValueError("delta_normals must be (T, nv, 3)")
+        self._can_release = False
+        self.vertex_count = nv
+        self.has_normals = nrm is not None
+        self._ptr = _check(lib.CreateMeshMorph(nv, _f64_ptr(pos), None if nrm is None else _f64_ptr(nrm), dp.shape[0],
+                                               _f64_ptr(dp), None if dn is None else _f64_ptr(dn)), "CreateMeshMorph")
+        self._can_release = True
+
+    @property
+    def target_count(self) -> int:
+        return lib.GetMeshMorphTargetCount(self._ptr)
+
+    def __del__(self):
+        if getattr(self, "_can_release", False):
+            lib.DestroyMeshMorph(self._ptr)
             self._can_release = False
 
 
