@@ -15,7 +15,7 @@ knobs       dict, GPU only, applied right after the context is created:
 resources   dict made before the first operation:
             texs    [(w, h, channels, "u8" | "f64", seed, (rw, rh) | None)]
             bufs    [("c", n, seed, spread, gouraud, blended) |
-                     ("t", n, seed, spread, "const" | "free")]   TriangleBuffers
+                     ("t", n, seed, spread, "const" | "tiled" | "free")]   TriangleBuffers
             meshes  [("c", space, rows, cols, seed, gouraud, blended) |
                      ("l", space, rows, cols, seed, gouraud, blended) |
                      ("tu", space, n, seed, spread) | ("ts", space, rows, cols, seed)]
@@ -37,7 +37,8 @@ recording, runs each operation:
   colour soup ("tri": draw_triangles / draw_triangles_device on torch tensors,
       aligned or offset by 8 bytes; "buf" on a colour TriangleBuffer)
           -> draw_triangles of the same arrays
-  textured soup, one (u, v) per triangle ("ttri" / "buf" with uv "const")
+  textured soup, one (u, v) per triangle ("ttri" / "buf" with uv "const", or
+      "tiled": the same over [-2w, 3w) x [-2h, 3h), wrap_ref.tiled_uv's range)
           -> flat draw_triangles with textured_ref.flat_colours(texels, uv)
   textured soup, free UVs on a 2x2 texture (uv "free": every sample is texel
       (0, 0))     -> flat draw_triangles with that texel
@@ -54,12 +55,16 @@ recording, runs each operation:
   begin / end / flush (command recording), gather (gather_frame_u8), knobs
           -> nothing
 
-The five sticky states of the mesh and textured draws -- near plane, cull mode,
-mesh perspective, triangle texture filter, lights -- are tracked by the
-interpreter itself (near, cull, persp, filt, ambient, lights), identically on
-both sides; the lowerings read that tracked state and never ask the library.
+The six sticky states of the mesh and textured draws -- near plane, cull mode,
+mesh perspective, triangle texture filter, lights, texture wrap -- are tracked
+by the interpreter itself (near, cull, persp, filt, ambient, lights, wrap),
+identically on both sides; the lowerings read that tracked state and never ask
+the library.  The wrap is tracked, set and checked here; the lowerings that
+sample under a wrap other than clamp, and the modulated, posed and morphed
+draws, are tests/frame_anim.py's, which extends this interpreter (this module
+never imports it: see _stable_seed).
 A state operation calls the setter on the GPU and nothing on the oracle, and a
-GPU run ends by asserting that the five getters return the tracked state: no
+GPU run ends by asserting that the six getters return the tracked state: no
 resize, save / restore, set_color, recording or draw between may have touched
 them (DESIGN.md documents no operation that resets one).  Operation by
 operation, all bit-exact:
@@ -92,11 +97,13 @@ operation, all bit-exact:
           -> texel (0, 0), as before
 
 The one substitution rule.  No exact lowering exists for free UVs under the
-bilinear filter (uv "free" soups and buffers, the "ts" mesh) nor for a "tu"
-mesh with the mesh perspective on under a perspective or behind-eye matrix
-(an instanced draw: under any such matrix).  For such a draw the interpreter
-switches the offending state off on the GPU side (set_triangle_texture_filter(0)
-or set_mesh_perspective(False)), draws, and switches it back on; the tracked
+bilinear filter or under a wrap other than clamp (uv "free" soups and buffers,
+the "ts" mesh: under repeat the 2x2 texture no longer always yields texel
+(0, 0)) nor for a "tu" mesh with the mesh perspective on under a perspective or
+behind-eye matrix (an instanced draw: under any such matrix).  For such a draw
+the interpreter switches the offending state off on the GPU side
+(set_triangle_texture_filter(0), set_triangle_texture_wrap(0, 0) or
+set_mesh_perspective(False)), draws, and switches it back; the tracked
 state is unchanged and the lowering uses the state as drawn.
 
 Rules of the interpreter, the same on both sides: a draw whose texture is
@@ -142,8 +149,8 @@ BATCH_OPS = ("tri", "ttri", "buf", "buf2", "mesh", "mesh2", "meshi", "lmesh", "l
 STATE5_OPS = ("near", "cull", "mpersp", "filter", "lights")
 OPS = """
 ("tri", src, n, seed, spread, gouraud, blended)       colour soup; src "host" | "dev" | "dev8"
-("ttri", src, n, seed, spread, uvkind, texref)        textured soup; uvkind "const" | "free" (texref then "tiny")
-("buf", i, texref)                                    resource buffer i (texref: textured buffers, uv "const")
+("ttri", src, n, seed, spread, uvkind, texref)        textured soup; uvkind "const" | "tiled" | "free" (texref then "tiny")
+("buf", i, texref)                                    resource buffer i (texref: textured buffers, uv "const" / "tiled")
 ("buf2", i, texref, dx)                               the same twice, translate(dx, 0) between (0: the second is warm)
 ("mesh", i, mat, texref)                              resource mesh i; mat indexes the matrices of its space
 ("mesh2", i, mat, texref, seed)                       draw, update_positions(seed), draw
@@ -158,6 +165,9 @@ OPS = """
 ("near", w) ("cull", mode) ("mpersp", on) ("filter", mode)   the sticky states: w in NEAR_VALUES, mode 0 | 1 | 2, 0 | 1
 ("lights", seed, nl)                                  set_mesh_lights(*mesh_light_ref.random_lights(nl, seed)), nl in 0..8;
                                                       seed None: (None, None), the default lights
+("wrap", u, v)                                        the sixth state, set_triangle_texture_wrap(u, v), u and v in 0..2
+                                                      (generated by tests/frame_anim.py, whose OPS table lists the
+                                                      modulated, posed and morphed draws)
 ("fill", c) ("rect", c, g) ("line", c, g) ("circle", c, g) ("grd", c, g)
 ("tex", texref, g) ("stex", texref, g, uv4) ("setpx", x, y, c) ("applypx", x, y, c)
 ("snap", which, shared)                               take the snapshot of that slot (again)
@@ -192,12 +202,16 @@ def colour_soup(n, W, H, seed, spread, gouraud, blended):
 
 def textured_soup(n, W, H, seed, spread, uvkind, size):
     """(xy, z, uv): uv "const": one (u, v) per triangle, uniform in
-    [-3, w+3] x [-3, h+3] of `size`; "free": any UVs per vertex."""
+    [-3, w+3] x [-3, h+3] of `size`; "tiled": the same over [-2w, 3w) x
+    [-2h, 3h); "free": any UVs per vertex."""
     xy, z, _ = scenes.triangle_soup(n, W, H, spread, seed=seed, zrange=ZRANGE)
     g = scenes.rng(seed + 1)
     w, h = size
     if uvkind == "const":
         uv = np.stack([g.uniform(-3, w + 3, n), g.uniform(-3, h + 3, n)], axis=1)
+        uv = np.repeat(uv[:, None, :], 3, axis=1)
+    elif uvkind == "tiled":         # (wrap_ref.tiled_uv's range, one (u, v) per triangle)
+        uv = np.stack([g.uniform(-2.0 * w, 3.0 * w, n), g.uniform(-2.0 * h, 3.0 * h, n)], axis=1)
         uv = np.repeat(uv[:, None, :], 3, axis=1)
     else:
         uv = g.uniform(-3, 5, size=(n, 3, 2))
@@ -405,6 +419,8 @@ def tile_pairs(xy, m, W, H):
 # the interpreter
 # ---------------------------------------------------------------------------
 class _Run:
+    batch_ops = BATCH_OPS
+
     def __init__(self, fac, frame, triangles=True):
         self.fac = fac
         self.gpu = fac.name != "oracle"
@@ -419,9 +435,10 @@ class _Run:
         # the five sticky states, tracked here and never read back from the library before the run's end
         self.near, self.cull, self.persp, self.filt = 0.0, 0, False, 0
         self.ambient = self.lights = None
+        self.wrap = self.wrap_drawn = (0, 0)    # the sixth: the texture wrap, and the wrap the current draw is issued under
         self.counts = []                        # (full, rasterised) triangle counts of the mesh draws
         self.over_cap = False                   # a batch of more than 50 tile pairs since the last synchronisation
-        self.changed_over_cap = 0               # changes of the five states while such a batch may be pending
+        self.changed_over_cap = 0               # changes of the six states while such a batch may be pending
         if self.gpu:
             from libnativecpurenderer_amd import libNativeCPURendererPybind as R
             self.R = R
@@ -473,14 +490,23 @@ class _Run:
             self.bufs.append((spec, arrays, gbuf))
         self.meshes = []
         for spec in self.res.get("meshes", []):
-            mesh = mesh_dict(spec, W, H)
+            mesh = self.mesh_dict(spec)
             gm = None
             if self.gpu and self.triangles:
-                gm = (self.R.Mesh(mesh["pos"], mesh["idx"], uv=mesh["uv"]) if "uv" in mesh else
+                gm = (self.R.Mesh(mesh["pos"], mesh["idx"], uv=mesh["uv"], colors=mesh.get("colors"),
+                                  normals=mesh.get("normals")) if "uv" in mesh else
                       self.R.Mesh(mesh["pos"], mesh["idx"], colors=mesh["colors"], gouraud=mesh["gouraud"],
                                   normals=mesh.get("normals")))
             self.meshes.append([spec, mesh, gm])
         self.lit = [e for e in self.meshes if e[0][0] == "l"]
+
+    def mesh_dict(self, spec):
+        return mesh_dict(spec, self.W, self.H)
+
+    def flat(self, texels, uv, filt):
+        """The flat colours of a constant-UV draw issued under wrap_drawn."""
+        assert self.wrap_drawn == (0, 0), "the wrapped lowering is frame_anim's"
+        return textured_colours(texels, uv, filt)
 
     def texture(self, ref, prim=False):
         if prim and not self.gpu and ref[0] == "snap" and ref[1] == "main" and ref[2]:
@@ -546,21 +572,30 @@ class _Run:
         self._note("colour", xy, ctx)
 
     def _nearest_for(self, free):
-        """The substitution rule for free UVs: the filter as drawn, and, on the
-        GPU side under the bilinear filter, the setter calls around the draw."""
-        if not (free and self.filt):
-            return self.filt, False
-        if self.gpu:
+        """The substitution rule for free UVs: the filter as drawn (the wrap as
+        drawn goes to wrap_drawn), and a function that restores what the GPU
+        side switched off: the bilinear filter, a wrap other than clamp."""
+        filt_off, wrap_off = bool(free and self.filt), free and self.wrap != (0, 0)
+        self.wrap_drawn = (0, 0) if wrap_off else self.wrap
+        if self.gpu and filt_off:
             self.ctx.set_triangle_texture_filter(0)
-        return 0, self.gpu
+        if self.gpu and wrap_off:
+            self.ctx.set_triangle_texture_wrap(0, 0)
+
+        def restore():
+            if self.gpu and filt_off:
+                self.ctx.set_triangle_texture_filter(1)
+            if self.gpu and wrap_off:
+                self.ctx.set_triangle_texture_wrap(*self.wrap)
+        return (0 if filt_off else self.filt), restore
 
     def textured_batch(self, tex, xy, z, uv, uvkind, src="host", gbuf=None, q=None):
         if not self.triangles or tex.width < 2 or tex.height < 2:
             return
-        assert uvkind == "const" or (tex.width, tex.height) == (2, 2), "free UVs are lowered on 2x2 textures only"
-        filt, back = self._nearest_for(uvkind != "const")
+        assert uvkind != "free" or (tex.width, tex.height) == (2, 2), "free UVs are lowered on 2x2 textures only"
+        filt, restore = self._nearest_for(uvkind == "free")
         if not self.gpu:
-            flat = textured_colours(self.texels(tex), uv, filt)
+            flat = self.flat(self.texels(tex), uv, filt)
             self.ctx.draw_triangles(xy, flat, z=z, gouraud=False)
         elif src == "host":
             self.ctx.draw_textured_triangles(tex, xy, uv, z=z, q=q)
@@ -571,8 +606,7 @@ class _Run:
             tz, = self._device((z,), False)
             tq = None if q is None else self._device((q,), src == "dev8")[0]
             self.ctx.draw_textured_triangles_device(tex, txy, tuv, xy.shape[0], z=tz, q=tq)
-        if back:
-            self.ctx.set_triangle_texture_filter(1)
+        restore()
         self._note("textured", xy)
 
     def draw_buffer(self, i, texref):
@@ -583,7 +617,7 @@ class _Run:
         if spec[0] == "c":
             self.colour_batch(xy, z, a, spec[4], "buf", gbuf)
         else:
-            ref = texref if spec[4] == "const" else ("tiny", spec[2], 3 + spec[2] % 2)
+            ref = texref if spec[4] != "free" else ("tiny", spec[2], 3 + spec[2] % 2)
             self.textured_batch(self.texture(ref), xy, z, a, spec[4], "buf", gbuf)
 
     def _mesh_texture(self, spec, texref):
@@ -603,8 +637,7 @@ class _Run:
             self.ctx.set_mesh_perspective(False)
 
         def restore():
-            if back:
-                self.ctx.set_triangle_texture_filter(1)
+            back()
             if off:
                 self.ctx.set_mesh_perspective(True)
         return filt, restore
@@ -616,7 +649,7 @@ class _Run:
         if tex is None:
             self.ctx.draw_triangles(xy, attr, z=z, gouraud=bool(mesh["gouraud"]))
         else:
-            self.ctx.draw_triangles(xy, textured_colours(self.texels(tex), attr, filt), z=z, gouraud=False)
+            self.ctx.draw_triangles(xy, self.flat(self.texels(tex), attr, filt), z=z, gouraud=False)
 
     def _note_mesh(self, kind, full, xy):
         self.counts.append((full, xy.shape[0]))
@@ -704,7 +737,7 @@ class _Run:
         self._note_mesh("lit", K * mesh["idx"].shape[0], soup[0])
 
     def set_state(self, k, op):
-        ctx, before = self.ctx, (self.near, self.cull, self.persp, self.filt, self.ambient, self.lights)
+        ctx, before = self.ctx, (self.near, self.cull, self.persp, self.filt, self.ambient, self.lights, self.wrap)
         if k == "near":
             self.near = float(op[1])
             if self.gpu:
@@ -721,19 +754,23 @@ class _Run:
             self.filt = int(op[1])
             if self.gpu:
                 ctx.set_triangle_texture_filter(self.filt)
+        elif k == "wrap":
+            self.wrap = (int(op[1]), int(op[2]))
+            if self.gpu:
+                ctx.set_triangle_texture_wrap(*self.wrap)
         else:
             self.ambient, self.lights = light_state(op[1], op[2])
             if self.gpu:
                 ctx.set_mesh_lights(self.ambient, self.lights)
-        after = (self.near, self.cull, self.persp, self.filt, self.ambient, self.lights)
+        after = (self.near, self.cull, self.persp, self.filt, self.ambient, self.lights, self.wrap)
         self.changed_over_cap += self.over_cap and repr(before) != repr(after)
 
     def check_states(self):
-        """The five getters against the tracked state (GPU side)."""
+        """The six getters against the tracked state (GPU side)."""
         ctx = self.ctx
         got = (ctx.get_mesh_near_plane(), ctx.get_mesh_cull(), ctx.mesh_perspective(), ctx.get_triangle_texture_filter(),
-               ctx.get_mesh_light_count())
-        want = (self.near, self.cull, self.persp, self.filt, 0 if self.lights is None else len(self.lights))
+               ctx.get_mesh_light_count(), tuple(ctx.get_triangle_texture_wrap()))
+        want = (self.near, self.cull, self.persp, self.filt, 0 if self.lights is None else len(self.lights), self.wrap)
         assert got == want, f"sticky states {got} != tracked {want}"
 
     # ---- one operation --------------------------------------------------------
@@ -779,7 +816,7 @@ class _Run:
             tex = self.texture(texref)
             xy, z, uv, q = perspective_soup(n, W0, H0, seed, spread, (tex.width, tex.height))
             self.textured_batch(tex, xy, z, uv, "const", src, q=q)
-        elif k in STATE5_OPS:
+        elif k in STATE5_OPS or k == "wrap":
             self.set_state(k, op)
         elif k == "fill":
             ctx.fill_color(*op[1])
@@ -871,7 +908,7 @@ class _Run:
         ctx.set_depth_state(True, True)
         ctx.clear_depth()
         for op in self.ops:
-            if op[0] in BATCH_OPS and not self.triangles:
+            if op[0] in self.batch_ops and not self.triangles:
                 continue
             self.op(op)
         out = {}
@@ -897,7 +934,7 @@ def run(fac, frame, triangles=True):
     format), probes (list of arrays), batches [(kind, raster path, tile
     pairs)] (kind colour, textured, mesh, instanced or lit), warm, counts
     [(full, rasterised triangles)] of the mesh draws, changed_over_cap (how
-    often one of the five states changed after a batch of more than 50 tile
+    often one of the six states changed after a batch of more than 50 tile
     pairs and before the next flush, gather or probe).  triangles=False leaves
     the triangle operations out."""
     return _Run(fac, frame, triangles).run()
